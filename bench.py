@@ -1,14 +1,20 @@
 #!/usr/bin/env python3
 """bench.py -- local-energy throughput of the MI355X determinant engine (one process per GPU).
 
-    python bench.py [--gpus N] [--steps K] [--warmup W] [--workload NAME]
+    python bench.py [--gpus N] [--steps K] [--warmup W] [--workload NAME] [--dump-outputs DIR] [--full]
     python -m torch.distributed.run --nnodes=1 --nproc-per-node N ... bench.py --gpus N ...
 
 A "step" is one pass of the hot path over one batch of walkers (every rank works on its own shard of
 `--walkers` walkers: weak scaling).  W untimed warm-up steps, then exactly K steps bracketed by
 barrier + torch.cuda.synchronize(); the maximum over ranks is the step time.  Rank 0 prints ONE JSON
-line (the contract of the build prompt) with `roofline` (dominant kernel, live HIP-event timing) and
-`cpu_baseline` (reference/oracle timed on the host cores, rank 0, N = 1 only).
+line with `ms_per_step` and `roofline` (dominant kernel, live HIP-event timing of the same steps).
+--dump-outputs DIR: after the timed steps rank 0 writes what its last step computed (the arrays a caller of the
+timed path receives) as DIR/<name>.npy, float64 or float32, complex as [..., 2] (real, imaginary); past 64 MB in
+all, a fixed seeded sample of the walkers (DIR/sample_walkers.npy).  The inputs of the timed steps are the same
+from run to run (the semi-stochastic draws are re-seeded after the untimed pre-heat).
+A plain run does nothing else.  --full adds the checks and the secondary measurements: `parity` (the last step
+against the CPU oracle), `cpu_baseline` (reference/oracle timed on the host cores, rank 0, N = 1 only; not with
+--no-cpu-baseline) and, for the default workload, `extra` (not with --no-extra).
 
 Workloads (config.workload):
   fe2s2_reduce_vmc_step (default)   one COMPLETE local-energy step of a VMC iteration with the method the Fe2S2 example runs: semi-stochastic
@@ -27,8 +33,8 @@ Workloads (config.workload):
                  kernel + packed all-reduce.
   fe2s2_eloc_rbm / syn<sorb>_eloc_rbm   complete SIMPLE local energies with a real RBM (alpha = 2) evaluated inside the
                  kernel; the RBM table is rebuilt every step (parameters change every optimisation step).
-With the default workload and N = 1 the line also carries `extra`: the drop-in rows/s, the other fused workloads, the larger systems, the
-REDUCE compaction throughput and the generic PyTorch-module paths, each measured in the same run.
+With --full, the default workload and N = 1 the line also carries `extra`: the drop-in rows/s, the other fused workloads, the larger systems,
+the REDUCE compaction throughput and the generic PyTorch-module paths, each measured in the same run.
 Inputs are resident in HBM before the timed region.  Nothing here reads /root/reference.
 """
 from __future__ import annotations
@@ -130,6 +136,50 @@ class Workload:
     def step(self):  # enqueue one pass; returns (start_event, end_event) around the dominant kernel
         raise NotImplementedError
 
+    def outputs(self):  # what a caller of the timed path receives from the last step: name -> tensor (--dump-outputs)
+        raise NotImplementedError
+
+
+def stats_output(stats):
+    """(mean, var, sd, standard error) of dist_stats_moments as float64 [mean.real, mean.imag, var, sd, se]"""
+    mean = stats[0]
+    im = mean.imag if mean.is_complex() else torch.zeros_like(mean)
+    return torch.stack([mean.real, im, stats[1], stats[2], stats[3]]).double()
+
+
+def grad_outputs(module):
+    return {f"grad_{k}": p.grad for k, p in module.named_parameters() if p.grad is not None}
+
+
+DUMP_LIMIT_BYTES = 64 * 1000 * 1000  # --dump-outputs: all files together, .npy headers included
+
+
+def dump_outputs(w, path):
+    """--dump-outputs: the last step's outputs as path/<name>.npy -- float32 and integers of up to 16 bits as float32, the rest as float64,
+    complex as [..., 2] real/imaginary pairs.  Past 64 MB in all, every array whose first axis is the walker axis keeps the same fixed,
+    seeded sample of walkers, whose indices go to path/sample_walkers.npy."""
+    arrs = {k: torch.as_tensor(t).detach() for k, t in w.outputs().items()}
+    arrs = {k: torch.view_as_real(t.resolve_conj()) if t.is_complex() else t for k, t in arrs.items()}
+    f32 = lambda t: t.dtype == torch.float32 or (not t.is_floating_point() and t.element_size() <= 2)  # noqa: E731
+    nbytes = lambda t: t.numel() * (4 if f32(t) else 8)  # noqa: E731  (as written)
+    total = sum(nbytes(t) for t in arrs.values())
+    budget = DUMP_LIMIT_BYTES - 1024 * (len(arrs) + 1)  # (a header of at most 1 KiB per file, sample_walkers.npy's among them)
+    if total > budget:
+        per_walker = [k for k, t in arrs.items() if t.dim() > 0 and t.size(0) == w.n]
+        row_bytes = sum(nbytes(arrs[k][0]) for k in per_walker) + 8  # (+ the walker's index)
+        keep = int((budget - (total - (row_bytes - 8) * w.n)) // row_bytes)
+        if keep < 1:
+            raise SystemExit(f"--dump-outputs: one walker's outputs do not fit {DUMP_LIMIT_BYTES} bytes")
+        idx = np.sort(np.random.default_rng(2024).choice(w.n, size=keep, replace=False))
+        sel = torch.from_numpy(idx)
+        for k in per_walker:
+            arrs[k] = arrs[k].index_select(0, sel.to(arrs[k].device))
+        arrs["sample_walkers"] = torch.from_numpy(idx.astype(np.float64))
+    os.makedirs(path, exist_ok=True)
+    for k, t in arrs.items():
+        np.save(os.path.join(path, k + ".npy"), t.to(torch.float32 if f32(t) else torch.float64).cpu().numpy())
+    return sorted(arrs)
+
 
 class DropinFused(Workload):
     """get_comb_hij_fused: enumerate + <x|H|x'>, comb and Hmat written to HBM (reference API shape)."""
@@ -181,6 +231,9 @@ class DropinFused(Workload):
         e1.record(st)
         self.N.check(rc, "pynqs_comb_hij_fused")
         return e0, e1
+
+    def outputs(self):  # (comb: the packed determinants' bytes, written as float32)
+        return {"hmat": self.hmat, "comb": self.comb} if self.comb_ptr is not None else {"hmat": self.hmat}
 
     def parity_gate(self):
         """max |dH| against the CPU oracle on the first walkers (SURVEY.md 8d 'parity gate')."""
@@ -345,6 +398,9 @@ class SampleSpaceFused(Workload):
         self.stats = dist_stats_moments(self.eloc, self.prob, None, get_world_size())
         return e0, e1
 
+    def outputs(self):
+        return {"eloc": self.eloc, "psi0": self.psi0, "stats": stats_output(self.stats)}
+
     def parity_gate(self):
         from oracle import oracle as O
 
@@ -423,6 +479,9 @@ class RbmFused(Workload):
 
         self.stats = dist_stats_moments(self.eloc, self.prob, None, get_world_size())
         return e0, e1
+
+    def outputs(self):
+        return {"eloc": self.eloc, "psi": self.psi, "stats": stats_output(self.stats)}
 
     def _oracle(self, m, nthreads=0):
         from oracle import oracle as O
@@ -517,6 +576,9 @@ class VmcStep(SampleSpaceFused):
         ev[3].record(st)
         self.phase_events.append(ev)
         return ev[0], ev[1]
+
+    def outputs(self):
+        return {**super().outputs(), "loss": self.loss, **grad_outputs(self.module)}
 
     def phases_ms(self):
         """Mean GPU-timeline duration of (E_loc kernel, moments + all-reduce, states + gradient estimator) over the recorded steps."""
@@ -649,7 +711,7 @@ class ReduceVmcStep(Workload):
         self.distinct_calibrated = nu
         self.from_parents = os.environ.get("PYNQS_BENCH_RBM_FROM_SCRATCH") != "1" and cx.rbm_forward_children_supported(sorb, sorb, "complex")
         self.psi_u = torch.zeros(self.front.cap_unique, dtype=torch.complex128, device=dev)
-        self.seed = 12345
+        self.seed = self.seed0 = 12345  # (every step draws with the next seed; timed() restarts the count after the pre-heat)
         self.prob = torch.full((self.n,), 1.0 / self.n, dtype=torch.float64, device=dev)
         # the estimator's gradient: for an RBM analytically from the packed walkers (pynqs_rbm_grad; --autograd-grad: the module's forward +
         # backward replayed from a HIP graph, what any other ansatz gets); either way one all-reduce of the flat gradient buffer
@@ -707,6 +769,9 @@ class ReduceVmcStep(Workload):
         ev[5].record(st)
         self.phase_events.append(ev)
         return ev[0], ev[1]
+
+    def outputs(self):
+        return {"eloc": self.eloc, "psi_x": self.psi_x, "stats": stats_output(self.stats), "loss": self.loss, **grad_outputs(self.module)}
 
     def phases_ms(self):
         evs, self.phase_events = self.phase_events, []
@@ -906,6 +971,9 @@ class ReduceTotalEnergy(Workload):
 
         self.stats = dist_stats_moments(self.eloc, self.prob, None, get_world_size())
         return e0, e1
+
+    def outputs(self):
+        return {"eloc": self.eloc, "stats": stats_output(self.stats)}
 
     def kernel_only(self, reps=5):
         """the front-end kernel alone on the first chunk (what local_energy launches for it), HIP events around the launch"""
@@ -1120,8 +1188,10 @@ def main():
     ap.add_argument("--eager-grad", action="store_true", help="fe2s2_vmc_step: gradient estimator by grad() under DistributedDataParallel instead of the HIP-graph replay")
     ap.add_argument("--autograd-grad", action="store_true", help="fe2s2_[reduce_]vmc_step: gradient estimator by the module's forward + backward replayed from a HIP graph instead of the analytic RBM gradient kernel")
     ap.add_argument("--torch-amplitudes", action="store_true", help="fe2s2_reduce_vmc_step: psi on the distinct x' by the PyTorch module instead of the fused RBM forward kernel")
-    ap.add_argument("--no-cpu-baseline", action="store_true")
-    ap.add_argument("--no-extra", action="store_true", help="skip the secondary workloads reported under 'extra'")
+    ap.add_argument("--full", action="store_true", help="also the oracle parity of the last step, the CPU baseline and the secondary workloads under 'extra'")
+    ap.add_argument("--no-cpu-baseline", action="store_true", help="--full: skip the CPU baseline")
+    ap.add_argument("--no-extra", action="store_true", help="--full: skip the secondary workloads reported under 'extra'")
+    ap.add_argument("--dump-outputs", metavar="DIR", help="write the last timed step's outputs (rank 0's shard) as DIR/<name>.npy")
     args = ap.parse_args()
 
     # The contract is ONE JSON line on stdout.  Libraries write there too (RCCL 2.26 prints a five-line version banner on its
@@ -1209,6 +1279,8 @@ def main():
 
     def timed(w, warmup, steps):
         preheat(w)
+        if hasattr(w, "seed0"):  # (the pre-heat's length depends on the clock: the steps after it draw the same from run to run)
+            w.seed = w.seed0
         for _ in range(warmup):
             w.step()
         if hasattr(w, "phase_events"):
@@ -1316,10 +1388,11 @@ def main():
         return out
 
     el, kern_ms = timed(wl, args.warmup, args.steps)
-    phases = wl.phases_ms() if hasattr(wl, "phases_ms") else None
+    phases = wl.phases_ms() if hasattr(wl, "phases_ms") else None   # (the REDUCE steps: also the overflow check of the run)
+    if args.dump_outputs and rank == 0:
+        dump_outputs(wl, args.dump_outputs)
 
     if rank == 0:
-        ok_c, dh = wl.parity_gate()
         total_walkers = (args.total_walkers if args.scaling == "strong" else wl.n * world) * args.steps
         out = {
             "metric": "local energies/sec (whole node)" if not isinstance(wl, DropinFused) else "S+D rows/sec: enumerate + <x|H|x'> materialised, no psi (whole node)",
@@ -1348,9 +1421,11 @@ def main():
                            if isinstance(wl, (VmcStep, ReduceVmcStep)) else "; packed RCCL all-reduce of (sum p E_loc, sum p |E_loc|^2, sum p)" if hasattr(wl, "stats")
                            else "; no data-path collective")},
             "roofline": roofline(wl, kern_ms),
-            "parity": {"exact_part_bit_exact": bool(ok_c), "max_abs_diff_vs_oracle": dh} if ok_c is not None
-                      else "oracle too slow at this size (tests/ cover the kernel at sizes it finishes)",
         }
+        if args.full:
+            ok_c, dh = wl.parity_gate()
+            out["parity"] = ({"exact_part_bit_exact": bool(ok_c), "max_abs_diff_vs_oracle": dh} if ok_c is not None
+                             else "oracle too slow at this size (tests/ cover the kernel at sizes it finishes)")
         if isinstance(wl, (VmcStep, ReduceVmcStep)):
             if phases is not None:
                 # what crosses xGMI per step: one packed all-reduce of the moments, one of the flat gradient buffer (+ the loss)
@@ -1370,13 +1445,14 @@ def main():
                                   "amplitudes_on_distinct_rows": ("pynqs_rbm_forward_children (from the parent walkers' hidden-unit factors by table multiplications)" if getattr(wl, "from_parents", False) else "pynqs_rbm_forward (one kernel, from the packed determinants)") if wl.fused_amplitudes
                                   else "the PyTorch module on the +-1 rows"})
         if isinstance(wl, ReduceTotalEnergy):
-            out["roofline"]["kernel_only"] = wl.kernel_only()
+            if args.full:
+                out["roofline"]["kernel_only"] = wl.kernel_only()
             out["config"].update({"method": "REDUCE (vmc/energy/eloc.py:205-324) through total_energy (etot.py:24-169)", "eps": wl.eps, "walkers_per_local_energy_call": wl.walkers_per_call,
                                   "amplitude_module": "real RBM, alpha = 1 (stand-in for the config's Transformer), amplitudes of the distinct x' by pynqs_rbm_forward_children"})
-        if world == 1 and not args.no_cpu_baseline:
+        if args.full and world == 1 and not args.no_cpu_baseline:
             out["cpu_baseline"] = wl.cpu_baseline()
-    # secondary measurements (same run, N = 1 only): drop-in rows, the other fused local energies and the larger word counts
-    if world == 1 and not args.no_extra and args.workload in ("fe2s2_dropin", "fe2s2_vmc_step", "fe2s2_reduce_vmc_step"):
+    # secondary measurements (--full, same run, N = 1 only): drop-in rows, the other fused local energies and the larger word counts
+    if args.full and world == 1 and not args.no_extra and args.workload in ("fe2s2_dropin", "fe2s2_vmc_step", "fe2s2_reduce_vmc_step"):
         extra = {}
         for name, nw, steps in (("fe2s2_vmc_step", args.walkers, 300), ("fe2s2_dropin", args.walkers, 2000), ("fe2s2_eloc_sample_space", args.walkers, 1000), ("fe2s2_eloc_rbm", args.walkers, 500),
                                 ("syn56_eloc_rbm", 4096, 200), ("syn120_dropin", 64, 500), ("syn184_dropin", 16, 200),

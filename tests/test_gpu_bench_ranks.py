@@ -49,7 +49,7 @@ def test_two_ranks_agree_with_one_rank_on_the_concatenated_shard():
 
 
 def test_the_default_reduce_step_runs_on_two_ranks():
-    out = _run(["--steps", "2", "--warmup", "1", "--no-extra", "--no-cpu-baseline", "--walkers", "256"], 2, {"PYNQS_BENCH_REHEARSAL": "1"})
+    out = _run(["--steps", "2", "--warmup", "1", "--full", "--no-extra", "--no-cpu-baseline", "--walkers", "256"], 2, {"PYNQS_BENCH_REHEARSAL": "1"})
     assert out["n_gpus"] == 2 and out["config"]["workload"] == "fe2s2_reduce_vmc_step" and out["config"]["eps_sample"] == 1000
     assert out["value"] > 0 and np.isfinite(out["check"]["grad_l2"]) and out["parity"]["exact_part_bit_exact"]
 
