@@ -461,6 +461,45 @@ int pynqs_rbm_grad(const uint64_t *onv, int64_t n, int sorb, const double *weigh
                    int eloc_is_complex, const double *e_total, const double *pow, double *grad_weights,
                    double *grad_hidden_bias, double *grad_visible_bias, double *loss, void *workspace, void *stream);
 
+/* ---- many-chain Metropolis sampling (vmc/sample.py:480-569, Sampler.MCMC; the reference runs one chain in a Python loop) -------------
+ * Semantics shared by both entry points (and by pynqs_amd/mcmc.py, which drives them):
+ *  - nchains independent chains; chain i of a call has the global index c = chain_base + i (c < 2^32).  Steps are numbered t = 0, 1, ...
+ *    from the sampler's start, so successive calls continue the random streams.
+ *  - Proposal of step t, chain c: pynqs_spin_flip_rand's draw with offset = (t << 32) + chain_base and the chain as the launch index,
+ *      r0 = umulhi(mix64(mix64(seed) ^ mix64((t << 32) + c)), nsd + 1),   mix64 = the splitmix64 finaliser (pynqs_amd/csrc/mix64.h);
+ *    r0 == 0 keeps the state, any other r0 applies excitation rank r0 - 1 (a uniform single or double excitation, or no move).
+ *  - No Hastings factor: the proposal is symmetric.  nsd depends only on (sorb, noA, noB), and rank -> excitation is a bijection onto
+ *    the singles and doubles of any determinant with noA alpha and noB beta electrons (the reference's same-spin `idx % noAA` quirk is a
+ *    cyclic shift of the hole-pair index inside each virtual pair, still a bijection), so x -> x' and x' -> x have the same probability.
+ *  - Acceptance draw: u = ((h >> 11) + 0.5) * 2^-53 in (0, 1] (double arithmetic, in this order),
+ *      h = mix64(mix64(seed ^ PYNQS_MCMC_ACCEPT_KEY) ^ mix64((t << 32) + c)).
+ *    The proposal is accepted iff u <= |psi(x')|^2 / |psi(x)|^2 (the reference's random() <= min(1, ratio)); if |psi(x)| == 0 every
+ *    proposal is accepted (the reference's ratio is inf or nan there, and min(1.0, .) accepts).
+ *  - Recording (pynqs_amd/mcmc.py): the first n_therm steps are discarded, then n_sample steps run and the state after every
+ *    `every`-th of them is recorded; accepted moves are counted over those n_sample steps only.  With nchains = 1 and every = 1 this is
+ *    Sampler.MCMC step for step, except for the random numbers (the reference's mt19937 / XORWOW statics cannot be reproduced anyway).
+ *
+ *   pynqs_mcmc_rbm : `nsteps` steps t = t0 .. t0 + nsteps - 1 of every chain in ONE launch, psi an RBM amplitude (flavours of
+ *        pynqs_rbm_forward): states uint64[nchains][len], read and written in place.  table: the RBM table (pynqs_rbm_table_build) for
+ *        PYNQS_RBM_REAL / TANH / PHASE, the complex table (pynqs_crbm_table_build) for PYNQS_RBM_COMPLEX.  records (may be NULL):
+ *        uint64[nsteps / every][nchains][len], row r = the states after step t0 + (r + 1) every - 1 (chain fastest).  n_accept (may be
+ *        NULL): int64[nchains], += the moves accepted in this launch.  lnpsi (may be NULL): double[nchains] <- ln|psi| of the final
+ *        states (pRBM: 0; every pRBM proposal is accepted, |psi| = 1).  Each chain's hidden-unit state is recomputed from the parameters
+ *        at the start of the launch; keep launches short (the Python layer bounds the steps per launch).
+ *   pynqs_mcmc_rbm_supported : 1 if (sorb, nhidden, flavour) has a fused kernel (nhidden <= 512, a valid table layout), else 0.
+ *   pynqs_mcmc_accept : step t of any ansatz, after pynqs_spin_flip_rand(states, ..., seed, (t << 32) + chain_base, proposals).
+ *        psi / psi_proposals: double[nchains] or, with is_complex, (re, im) pairs; states and psi take the proposals' values where the
+ *        move is accepted; n_accept (may be NULL) is bumped there; record_row (may be NULL): uint64[nchains][len] <- the states after
+ *        the step.                                                                                                                      */
+#define PYNQS_MCMC_ACCEPT_KEY 0x243F6A8885A308D3ull
+int pynqs_mcmc_rbm_supported(int sorb, int nhidden, int flavour);
+int pynqs_mcmc_rbm(uint64_t *states, int64_t nchains, int sorb, int noA, int noB, const void *table, int nhidden, int flavour,
+                   uint64_t seed, uint64_t chain_base, uint64_t t0, int nsteps, int every, uint64_t *records, int64_t *n_accept,
+                   double *lnpsi, void *stream);
+int pynqs_mcmc_accept(uint64_t *states, double *psi, const uint64_t *proposals, const double *psi_proposals, int64_t nchains,
+                      int sorb, int is_complex, uint64_t seed, uint64_t chain_base, uint64_t t, uint64_t *record_row,
+                      int64_t *n_accept, void *stream);
+
 #ifdef __cplusplus
 }
 #endif

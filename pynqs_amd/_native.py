@@ -98,7 +98,9 @@ SIGNATURES.update({
     "pynqs_rbm_forward_children_supported": (_int, [_int, _int, _int]),
     "pynqs_rbm_grad_workspace": (_i64, [_i64, _int, _int, _int]),
     "pynqs_rbm_grad": (_int, [_vp, _i64, _int, _vp, _vp, _vp, _int, _int, _vp, _vp, _int, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp]),
-    "pynqs_reduce_contract": (_int, [_i64, _int, _int, _int, _int, _int, _int, C.POINTER(ReduceIO), _vp, _vp, _int, _int, _vp, _vp, _vp]),
+    "pynqs_reduce_contract": (_int, [_i64, _int, _int, _int, _int, _int, _int, C.POINTER(ReduceIO), _vp, _vp, _int, _int, _vp, _vp, _vp]),    "pynqs_mcmc_rbm_supported": (_int, [_int, _int, _int]),
+    "pynqs_mcmc_rbm": (_int, [_vp, _i64, _int, _int, _int, _vp, _int, _int, C.c_uint64, C.c_uint64, C.c_uint64, _int, _int, _vp, _vp, _vp, _vp]),
+    "pynqs_mcmc_accept": (_int, [_vp, _vp, _vp, _vp, _i64, _int, _int, C.c_uint64, C.c_uint64, C.c_uint64, _vp, _vp, _vp]),
 })
 
 _lib = None

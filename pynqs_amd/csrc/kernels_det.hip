@@ -5,6 +5,7 @@
 // Reference behaviour: cpp_src/cpu/*.cpp, cpp_src/tensor/cpu_tensor.cpp (cited per kernel).
 #include "detcore.h"
 #include "launch.h"
+#include "mix64.h"
 
 namespace pynqs {
 
@@ -422,13 +423,6 @@ extern "C" int pynqs_wavefunction_lut(const uint64_t *keys, int64_t nkeys, const
 // The random stream is a counter-based hash of (seed, call offset, walker index): reproducible for a given
 // seed, but -- like the reference's own CPU (mt19937) and CUDA (XORWOW) paths -- a different stream from either.
 namespace pynqs {
-
-__device__ __forceinline__ uint64_t mix64(uint64_t z) {  // splitmix64 finaliser
-  z += 0x9e3779b97f4a7c15ull;
-  z = (z ^ (z >> 30)) * 0xbf58476d1ce4e5b9ull;
-  z = (z ^ (z >> 27)) * 0x94d049bb133111ebull;
-  return z ^ (z >> 31);
-}
 
 template <int LEN>
 __global__ __launch_bounds__(kBlock) void spin_flip_rand_kernel(const uint64_t *__restrict__ bra, uint64_t n, SDParams p,

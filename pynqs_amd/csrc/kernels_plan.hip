@@ -75,27 +75,27 @@ typedef uint64_t u64x2 __attribute__((ext_vector_type(2)));
 // NT: non-temporal stores.  The outputs are written once and never read by the kernel.  When the plan does not fit
 // the L2 (large systems) keeping the output stream out of the caches leaves them to the gathers: sorb 120 0.637 ->
 // 0.517 ms.  When it does fit (Fe2S2, 2 MiB) ordinary stores are faster (0.252 vs 0.285 ms): the host picks.
-#define PYNQS_STORE(ptr, val) do { if constexpr (NT) __builtin_nontemporal_store((val), (ptr)); else *(ptr) = (val); } while (0)
+#define PYNQS_PUT(ptr, val) do { if constexpr (NT) __builtin_nontemporal_store((val), (ptr)); else *(ptr) = (val); } while (0)
 
 template <bool NT, typename T>
 __device__ __forceinline__ void store_h(T *__restrict__ hrow, uint32_t col, T v) {
-  PYNQS_STORE(reinterpret_cast<T *>(reinterpret_cast<char *>(hrow) + (size_t)(col * (uint32_t)sizeof(T))), v);
+  PYNQS_PUT(reinterpret_cast<T *>(reinterpret_cast<char *>(hrow) + (size_t)(col * (uint32_t)sizeof(T))), v);
 }
 template <bool NT, typename T>
 __device__ __forceinline__ void store_h2(T *__restrict__ hrow, uint32_t col, T v0, T v1) {
   typedef T T2 __attribute__((ext_vector_type(2)));
   T2 v = {v0, v1};
-  PYNQS_STORE(reinterpret_cast<T2 *>(reinterpret_cast<char *>(hrow) + (size_t)(col * (uint32_t)sizeof(T))), v);
+  PYNQS_PUT(reinterpret_cast<T2 *>(reinterpret_cast<char *>(hrow) + (size_t)(col * (uint32_t)sizeof(T))), v);
 }
 template <bool NT, int LEN>
 __device__ __forceinline__ void store_ket(uint64_t *__restrict__ crow, uint32_t col, const uint64_t (&ket)[LEN]) {
   char *dst = reinterpret_cast<char *>(crow) + (size_t)(col * (uint32_t)(8 * LEN));
   if constexpr (LEN == 2) {  // one 16-byte store (rows of two-word kets are 16-byte aligned)
     u64x2 v = {ket[0], ket[1]};
-    PYNQS_STORE(reinterpret_cast<u64x2 *>(dst), v);
+    PYNQS_PUT(reinterpret_cast<u64x2 *>(dst), v);
   } else {
 #pragma unroll
-    for (int i = 0; i < LEN; ++i) PYNQS_STORE(reinterpret_cast<uint64_t *>(dst) + i, ket[i]);
+    for (int i = 0; i < LEN; ++i) PYNQS_PUT(reinterpret_cast<uint64_t *>(dst) + i, ket[i]);
   }
 }
 // two consecutive kets = 2*LEN words = LEN 16-byte stores; (row base + col) is even, so the address is
@@ -108,7 +108,7 @@ __device__ __forceinline__ void store_ket2(uint64_t *__restrict__ crow, uint32_t
 #pragma unroll
   for (int i = 0; i < LEN; ++i) { w[i] = k0[i]; w[LEN + i] = k1[i]; }
 #pragma unroll
-  for (int i = 0; i < LEN; ++i) { u64x2 v = {w[2 * i], w[2 * i + 1]}; PYNQS_STORE(dst + i, v); }
+  for (int i = 0; i < LEN; ++i) { u64x2 v = {w[2 * i], w[2 * i + 1]}; PYNQS_PUT(dst + i, v); }
 }
 
 // The drop-in kernel: every column of the walker's range goes to HBM (comb and Hmat in the reference layout).
@@ -146,7 +146,7 @@ struct StoreSink {
           __builtin_amdgcn_wave_barrier();
           uint64_t *dst = crow + (size_t)((half ? c1 : c0) - lane) * 3;
 #pragma unroll
-          for (int k = 0; k < 3; ++k) PYNQS_STORE(dst + lane + 64 * k, (uint64_t)st[lane + 64 * k]);
+          for (int k = 0; k < 3; ++k) PYNQS_PUT(dst + lane + 64 * k, (uint64_t)st[lane + 64 * k]);
           __builtin_amdgcn_wave_barrier();
         }
       } else {

@@ -19,6 +19,7 @@
 #include "launch.h"
 #include "plan.h"
 #include "plan_dev.h"
+#include "rbm.h"
 
 namespace pynqs {
 
@@ -32,25 +33,6 @@ __device__ __forceinline__ cplx cexp(cplx z) {
   sincos(z.y, &sn, &cs);
   const double e = exp(z.x);
   return cplx{e * cs, e * sn};
-}
-
-// Table in caller-owned memory, complex double = 2 doubles, hidden index fastest, row stride Hs (odd: consecutive rows start in
-// different 16-byte bank groups):  Wt [sorb][Hs] | E4p = exp(+4W) [sorb][Hs] | E4m = exp(-4W) [sorb][Hs] | hb [Hs] | vb [sorb]
-struct CrbmLayout {
-  int sorb, H, Hloop, Hs;  // Hloop = H rounded up to 2 (the hidden-unit loop), Hs = Hloop + 1
-  int64_t offWt, offE4p, offE4m, offHb, offVb, total;  // in complex elements
-};
-
-static inline bool make_crbm_layout(int sorb, int H, CrbmLayout *L) {
-  if (sorb < 1 || sorb > 192 || H < 1 || H > 4096) return false;
-  L->sorb = sorb; L->H = H;
-  L->Hloop = (H + 1) & ~1;
-  L->Hs = L->Hloop + 1;
-  const int64_t row = (int64_t)sorb * L->Hs;
-  L->offWt = 0; L->offE4p = row; L->offE4m = 2 * row; L->offHb = 3 * row;
-  L->offVb = L->offHb + L->Hs;
-  L->total = L->offVb + sorb;
-  return true;
 }
 
 // W[H][sorb][2], hb[H][2], vb[sorb][2] (the reference's params_weights / params_hidden_bias / params_visible_bias) -> table

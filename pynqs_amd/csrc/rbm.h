@@ -33,4 +33,23 @@ inline bool make_rbm_layout(int sorb, int H, RbmLayout *L) {
   return true;
 }
 
+// The table of an RBM with COMPLEX parameters (pynqs_crbm_table_build), in caller-owned memory, complex double = 2 doubles, hidden index fastest, row stride Hs (odd: consecutive rows start in
+// different 16-byte bank groups):  Wt [sorb][Hs] | E4p = exp(+4W) [sorb][Hs] | E4m = exp(-4W) [sorb][Hs] | hb [Hs] | vb [sorb]
+struct CrbmLayout {
+  int sorb, H, Hloop, Hs;  // Hloop = H rounded up to 2 (the hidden-unit loop), Hs = Hloop + 1
+  int64_t offWt, offE4p, offE4m, offHb, offVb, total;  // in complex elements
+};
+
+inline bool make_crbm_layout(int sorb, int H, CrbmLayout *L) {
+  if (sorb < 1 || sorb > 192 || H < 1 || H > 4096) return false;
+  L->sorb = sorb; L->H = H;
+  L->Hloop = (H + 1) & ~1;
+  L->Hs = L->Hloop + 1;
+  const int64_t row = (int64_t)sorb * L->Hs;
+  L->offWt = 0; L->offE4p = row; L->offE4m = 2 * row; L->offHb = 3 * row;
+  L->offVb = L->offHb + L->Hs;
+  L->total = L->offVb + sorb;
+  return true;
+}
+
 }  // namespace pynqs
