@@ -474,7 +474,11 @@ int pynqs_rbm_grad(const uint64_t *onv, int64_t n, int sorb, const double *weigh
  *  - Acceptance draw: u = ((h >> 11) + 0.5) * 2^-53 in (0, 1] (double arithmetic, in this order),
  *      h = mix64(mix64(seed ^ PYNQS_MCMC_ACCEPT_KEY) ^ mix64((t << 32) + c)).
  *    The proposal is accepted iff u <= |psi(x')|^2 / |psi(x)|^2 (the reference's random() <= min(1, ratio)); if |psi(x)| == 0 every
- *    proposal is accepted (the reference's ratio is inf or nan there, and min(1.0, .) accepts).
+ *    proposal is accepted (the reference's ratio is inf or nan there, and min(1.0, .) accepts).  The ratio is that of the amplitudes
+ *    for every finite nonzero |psi(x)|, however small or large (not of their squares in double, which under- or overflow).
+ *    Non-finite amplitudes (a part inf or nan; only pynqs_mcmc_accept can be given one): a proposal with one is rejected, also from a
+ *    state of amplitude zero, and a state with one accepts every proposal of finite amplitude, as a state of amplitude zero does.  (The
+ *    reference's min(1.0, nan) accepts, its finite / inf = 0 rejects: a chain would enter such states and could stick there.)
  *  - Recording (pynqs_amd/mcmc.py): the first n_therm steps are discarded, then n_sample steps run and the state after every
  *    `every`-th of them is recorded; accepted moves are counted over those n_sample steps only.  With nchains = 1 and every = 1 this is
  *    Sampler.MCMC step for step, except for the random numbers (the reference's mt19937 / XORWOW statics cannot be reproduced anyway).

@@ -11,11 +11,15 @@
 //   q'_h = q_h prod_{o in F} exp(-4 s_h x'_o W_ho)            (the table's E4m / E4p entries: no exponential),
 //   if the sign of Re theta_h changed (decided on theta, which is tracked too):  q'_h <- 1 / q'_h  (= exp(-2 s'_h theta'_h) again; deciding
 //   on |q'_h| > 1 instead would let rounding flip the branch where Re theta_h = 0 exactly, as for rbm_type "cos"),
-//   if |q'_h| < 1e-290 (|Re theta'_h| > ~333): q'_h from theta'_h by exp (+ sincos): the product would sink into the subnormals,
+//   if |q'_h| < 1e-290 (|Re theta'_h| > ~333): q'_h from theta'_h by exp (+ sincos), flushed to 0 below 1e-290: the product would sink
+//   into the subnormals and lose its digits; and if |q'_h| > 1 (the product of a flushed q_h = 0 after a sign change is 1 / 0 = inf;
+//   otherwise only rounding at Re theta'_h ~ 0, or exp(+-4 W) overflowed in the table),
 // and ln|psi'| - ln|psi| = Re a.(x' - x) + sum_h (|Re theta'_h| - |Re theta_h|) + ln prod_h |1 + q'_h| / |1 + q_h| -- per lane a product of
 // at most 8 ratios in [1/2, 2] (real) and one logarithm, then a butterfly over the G lanes.  No quantity leaves the range of a double for
 // any |Re theta_h| (the state is never exp(+-theta)).  The state is recomputed from the parameters at the start of every launch
 // (theta = b + W x, sorb fma per hidden unit), so that the rounding of the updates cannot drift over a run.
+// tanh keeps the hidden part sum_h ln|2cosh theta_h| (always finite) apart from ln|tanh a.x| (-inf where a.x = 0) and forms ln|psi| of an
+// accepted state from the two, so that leaving a state of amplitude zero gives the new state's own ln|psi| (not -inf + inf).
 // The parameter table is copied into LDS when it fits 64 KB (Fe2S2 with 40 real hidden units: 39 KB), else read from the L2.
 // The proposal is computed by every lane of the group (the same hash, the same excite_by_rank), so the group needs no exchange for it;
 // the butterfly leaves the same sum in every lane (each stage adds the same two numbers), so the lanes take the same decision.
@@ -53,10 +57,11 @@ __device__ __forceinline__ double lncosh_of(double ar, double qr, double qi) {
   else return ar + log1p(qr);
 }
 
-// q = exp(-2 s theta) from theta directly, s = sign(Re theta)
+// q = exp(-2 s theta) from theta directly, s = sign(Re theta); 0 where |q| < kMcmcTiny (no digits are lost to the subnormals)
 template <bool CPLX>
 __device__ __forceinline__ void q_of(double tr, double ti, double &qr, double &qi) {
-  const double m = exp(-2.0 * fabs(tr));
+  double m = exp(-2.0 * fabs(tr));
+  m = m >= kMcmcTiny ? m : 0.0;
   if constexpr (CPLX) {
     double sn, cs;
     sincos_mod(-2.0 * (tr < 0.0 ? -ti : ti), sn, cs);
@@ -101,7 +106,7 @@ __global__ __launch_bounds__(kBlock) void mcmc_rbm_kernel(uint64_t *__restrict__
 
   // ---- the chain's state from scratch
   double thr[J], thi[J], qr[J], qi[J];
-  double ax = 0.0, lnpsi = 0.0;
+  double ax = 0.0, lnh = 0.0, lnpsi = 0.0;  // lnh: the hidden part of ln|psi| (tanh only)
   if constexpr (HIDDEN) {
     double part = 0.0;
 #pragma unroll
@@ -122,8 +127,8 @@ __global__ __launch_bounds__(kBlock) void mcmc_rbm_kernel(uint64_t *__restrict__
       }
     }
     for (int o = 0; o < sorb; ++o) ax = fma(pm1_of<LEN>(x, o), tab[(T.offVb + o) * C], ax);
-    lnpsi = group_sum(part, G);
-    lnpsi += FLAVOUR == PYNQS_RBM_TANH ? log(fabs(tanh(ax))) : ax;
+    lnh = group_sum(part, G);
+    lnpsi = lnh + (FLAVOUR == PYNQS_RBM_TANH ? log(fabs(tanh(ax))) : ax);
   }
 
   int64_t accepted = 0;
@@ -193,9 +198,12 @@ __global__ __launch_bounds__(kBlock) void mcmc_rbm_kernel(uint64_t *__restrict__
           } else {
             ui = 0.0;
             ur = qr[j] * fr;
+            // (after a sign change |q fr| >= 1, so without this inverse the |q'| <= 1 test below would recompute q' by exp: dropping
+            //  it changes only the speed, and only the complex inverse above is load-bearing)
             if ((tr < 0.0) != (thr[j] < 0.0)) ur = 1.0 / ur;
           }
-          if (!(fmax(fabs(ur), fabs(ui)) >= kMcmcTiny)) q_of<CPLX>(tr, ti, ur, ui);
+          const double mq = fmax(fabs(ur), fabs(ui));
+          if (!(mq >= kMcmcTiny && mq <= 1.0)) q_of<CPLX>(tr, ti, ur, ui);
           lsum += fabs(tr) - fabs(thr[j]);
           if constexpr (CPLX) {
             pn *= fma(ui, ui, (1.0 + ur) * (1.0 + ur));
@@ -207,20 +215,26 @@ __global__ __launch_bounds__(kBlock) void mcmc_rbm_kernel(uint64_t *__restrict__
           nthr[j] = tr; nthi[j] = ti; nqr[j] = ur; nqi[j] = ui;
         }
       }
-      double dl = group_sum(fma(CPLX ? 0.5 : 1.0, log(pn / po), lsum), G);
+      const double dh = group_sum(fma(CPLX ? 0.5 : 1.0, log(pn / po), lsum), G);
       double dax = 0.0;
 #pragma unroll
       for (int f = 0; f < 4; ++f)
         if (f < nf) dax = fma(2.0 * fs[f], tab[(T.offVb + fo[f]) * C], dax);
       const double axn = ax + dax;
-      dl += FLAVOUR == PYNQS_RBM_TANH ? log(fabs(tanh(axn))) - log(fabs(tanh(ax))) : dax;
-      // u <= |psi'|^2 / |psi|^2, and every proposal from a state of amplitude zero
+      const double lvn = FLAVOUR == PYNQS_RBM_TANH ? log(fabs(tanh(axn))) : 0.0;  // (-inf: x' has amplitude zero)
+      const double dl = dh + (FLAVOUR == PYNQS_RBM_TANH ? lvn - log(fabs(tanh(ax))) : dax);
+      // u <= |psi'|^2 / |psi|^2, and every proposal from a state of amplitude zero (then dl is +inf or nan)
       accept = !(lnpsi > -INFINITY) || mcmc_uniform(seed, t, c) <= exp(2.0 * dl);
       if (accept) {
 #pragma unroll
         for (int j = 0; j < J; ++j) { thr[j] = nthr[j]; thi[j] = nthi[j]; qr[j] = nqr[j]; qi[j] = nqi[j]; }
         ax = axn;
-        lnpsi += dl;
+        if constexpr (FLAVOUR == PYNQS_RBM_TANH) {
+          lnh += dh;
+          lnpsi = lnh + lvn;
+        } else {
+          lnpsi += dl;
+        }
       }
     }
     if (accept) {
@@ -251,18 +265,31 @@ __global__ __launch_bounds__(kBlock) void mcmc_accept_kernel(uint64_t *__restric
   const int64_t i = (int64_t)blockIdx.x * kBlock + threadIdx.x;
   if (i >= n) return;
   constexpr int C = CPLX ? 2 : 1;
-  const double pr = psi_prop[i * C], pi = CPLX ? psi_prop[i * C + 1] : 0.0;
-  const double cr = psi[i * C], ci = CPLX ? psi[i * C + 1] : 0.0;
-  const double a = CPLX ? pr * pr + pi * pi : pr * pr, b = CPLX ? cr * cr + ci * ci : cr * cr;
-  const bool accept = b == 0.0 || mcmc_uniform(seed, t, chain_base + (uint64_t)i) <= a / b;
+  double pr = psi_prop[i * C], pi = CPLX ? psi_prop[i * C + 1] : 0.0;
+  double cr = psi[i * C], ci = CPLX ? psi[i * C + 1] : 0.0;
+  // |psi'|^2 / |psi|^2 with both amplitudes scaled by the same power of two (exact; the larger part of psi to [1/2, 1)), so that no square
+  // under- or overflows where it could decide (the squares of the unscaled values give 0 / 0 below ~1e-162, inf / inf above ~1e154);
+  // non-finite amplitudes as include/pynqs_amd.h says
+  bool accept;
+  if (!(isfinite(pr) && isfinite(pi))) {
+    accept = false;
+  } else if (!(isfinite(cr) && isfinite(ci)) || (cr == 0.0 && ci == 0.0)) {
+    accept = true;
+  } else {
+    int e;
+    frexp(fmax(fabs(cr), fabs(ci)), &e);
+    pr = ldexp(pr, -e); pi = ldexp(pi, -e); cr = ldexp(cr, -e); ci = ldexp(ci, -e);
+    const double a = CPLX ? pr * pr + pi * pi : pr * pr, b = CPLX ? cr * cr + ci * ci : cr * cr;
+    accept = mcmc_uniform(seed, t, chain_base + (uint64_t)i) <= a / b;
+  }
   uint64_t x[LEN];
 #pragma unroll
   for (int w = 0; w < LEN; ++w) x[w] = accept ? prop[i * LEN + w] : states[i * LEN + w];
   if (accept) {
 #pragma unroll
     for (int w = 0; w < LEN; ++w) states[i * LEN + w] = x[w];
-    psi[i * C] = pr;
-    if (CPLX) psi[i * C + 1] = pi;
+    psi[i * C] = psi_prop[i * C];
+    if (CPLX) psi[i * C + 1] = psi_prop[i * C + 1];
     if (nacc) nacc[i] += 1;
   }
   if (rec) {

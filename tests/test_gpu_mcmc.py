@@ -13,10 +13,10 @@ import torch
 from torch import nn
 
 from conftest import synth_integrals
+from mcmc_replay import host_r0, host_u
 
 pytestmark = pytest.mark.gpu
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-M64 = np.uint64(0xFFFFFFFFFFFFFFFF)
 
 
 @pytest.fixture(scope="module")
@@ -36,31 +36,6 @@ class Opaque(nn.Module):
 
     def forward(self, x):
         return self.inner(x)
-
-
-def mix64(z):
-    with np.errstate(over="ignore"):
-        z = (z + np.uint64(0x9E3779B97F4A7C15)) & M64
-        z = (z ^ (z >> np.uint64(30))) * np.uint64(0xBF58476D1CE4E5B9)
-        z = (z ^ (z >> np.uint64(27))) * np.uint64(0x94D049BB133111EB)
-        return z ^ (z >> np.uint64(31))
-
-
-def umulhi32(h, m):
-    """(h * m) >> 64 for m < 2^32."""
-    m = np.uint64(m)
-    with np.errstate(over="ignore"):
-        hi, lo = h >> np.uint64(32), h & np.uint64(0xFFFFFFFF)
-        return (hi * m + ((lo * m) >> np.uint64(32))) >> np.uint64(32)
-
-
-def host_r0(seed, t, c, nsd):
-    return umulhi32(mix64(mix64(np.uint64(seed)) ^ mix64((np.uint64(t) << np.uint64(32)) + c)), nsd + 1).astype(np.int64)
-
-
-def host_u(seed, t, c):
-    h = mix64(mix64(np.uint64(seed) ^ np.uint64(0x243F6A8885A308D3)) ^ mix64((np.uint64(t) << np.uint64(32)) + c))
-    return ((h >> np.uint64(11)).astype(np.float64) + 0.5) * 2.0 ** -53
 
 
 def rand_rbm(rbm, sorb, H, kind, seed, scale=0.2):
@@ -173,13 +148,25 @@ def _exact_law(cx, rbm, kind):
     return sorb, noA, noB, x_all, model, psi, (p / p.sum()).cpu().numpy()
 
 
-@pytest.mark.parametrize("kind", ["real", "complex"])
+@pytest.mark.parametrize("kind", ["real", "complex", "tanh", "cos"])
 def test_stationary_law(mods, kind):
-    from scipy.stats import chi2
-
     cx, mcmc, rbm = mods
     sorb, noA, noB, x_all, model, _, p = _exact_law(cx, rbm, kind)
     assert p.max() / p.min() > 20  # a spread of |psi|^2
+    _chi_square(mcmc, sorb, noA, noB, x_all, model, p)
+
+
+def test_stationary_law_prbm(mods):
+    """pRBM: |psi| = 1, so the chains' law is uniform over the space."""
+    cx, mcmc, rbm = mods
+    sorb, noA, noB, x_all, model, _, p = _exact_law(cx, rbm, "pRBM")
+    assert np.allclose(p, 1.0 / p.size, rtol=1e-12, atol=0)
+    _chi_square(mcmc, sorb, noA, noB, x_all, model, p)
+
+
+def _chi_square(mcmc, sorb, noA, noB, x_all, model, p):
+    from scipy.stats import chi2
+
     nch = 65536
     s = mcmc.MCMCSampler(sorb, noA + noB, noA, noB, nch, 2718, x_all[:1].contiguous())
     s.run(model, 300, 0)
