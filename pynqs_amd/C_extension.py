@@ -127,29 +127,51 @@ _PLAN_BUILDS: "dict[tuple, int]" = {}  # (sorb, numel of h2e, device) -> number 
 _PLAN_REBUILD_WARN = 16
 
 
+_FINGERPRINT_CHUNK = 1 << 24   # elements per pass of _fingerprint: a few 128 MiB int64 temporaries, whatever the size of h2e
+
+
 def _fingerprint(h1e: Tensor, h2e: Tensor):
-    """Content key of a pair of integral tensors: shapes, dtypes, devices and two 64-bit sums over the elements' bit patterns (the plain sum
-    and the sum after a multiply-xorshift mix, both modulo 2^64) per tensor.  The plan is a pure function of the integrals' content, so a
-    cached plan may serve any tensors with the same key: a caller that re-creates equal integrals on every call (a fresh `.to(device)`, a
-    reloaded file) pays two reductions and one read-back instead of a rebuild (ms, up to 1.2 GB written at sorb 184).  None when it cannot
+    """Content key of a pair of integral tensors: shapes, dtypes, devices and two 64-bit sums per tensor (modulo 2^64): the plain sum of the
+    elements' bit patterns, and the sum of a splitmix64-style mix of (bit pattern + flat index x 0x9E3779B97F4A7C15).  The index makes the
+    second sum depend on where each value sits: a permutation of the same values (h1e.t(), a relabelling of the orbitals) is another key.
+    The plan is a pure function of the integrals' content, so a cached plan may serve any tensors with the same key: a caller that re-creates
+    equal integrals on every call (a fresh `.to(device)`, a reloaded file) pays a few reductions and one read-back instead of a rebuild (ms,
+    up to 1.2 GB written at sorb 184).  Taken in chunks of _FINGERPRINT_CHUNK elements, so the temporaries stay bounded.  None when it cannot
     be taken (stream capture: the read-back synchronises)."""
     if any(t.is_cuda for t in (h1e, h2e)) and torch.cuda.is_current_stream_capturing():
         return None
+    golden = -7046029254386353131   # (0x9E3779B97F4A7C15 as a signed 64-bit factor; products wrap)
     out = []
     with torch.no_grad():
         for t in (h1e, h2e):
-            c = t.detach().contiguous()
-            v = c.view(torch.int64) if c.element_size() == 8 else c.view(torch.int32).to(torch.int64)
-            m = (v * -7046029254386353131) ^ (v >> 29)   # (0x9E3779B97F4A7C15 as a signed 64-bit factor; wraps)
-            out.append((tuple(t.shape), str(t.dtype), str(t.device), int(v.sum().item()), int(m.sum().item())))
+            c = t.detach().contiguous().reshape(-1)
+            c = c.view(torch.int64) if c.element_size() == 8 else c.view(torch.int32)
+            plain = torch.zeros((), dtype=torch.int64, device=c.device)
+            mixed = torch.zeros((), dtype=torch.int64, device=c.device)
+            for s in range(0, c.numel(), _FINGERPRINT_CHUNK):
+                v = c[s:s + _FINGERPRINT_CHUNK].to(torch.int64)
+                plain += v.sum()
+                m = torch.arange(s, s + v.numel(), dtype=torch.int64, device=c.device).mul_(golden).add_(v)
+                del v
+                m.bitwise_xor_(m >> 30).mul_(-4658895280553007687)   # (0xBF58476D1CE4E5B9)
+                m.bitwise_xor_(m >> 27).mul_(-7723592293110705685)   # (0x94D049BB133111EB)
+                m.bitwise_xor_(m >> 31)
+                mixed += m.sum()
+                del m
+            out.append((tuple(t.shape), str(t.dtype), str(t.device), int(plain.item()), int(mixed.item())))
     return tuple(out)
 
 
 def plan_for(h1e: Tensor, h2e: Tensor, sorb: int, device: "torch.device | None" = None) -> "IntegralPlan | None":
     """Cached IntegralPlan for these tensors (None when sorb is odd -> direct kernels).  The cache is keyed on the tensor objects
     (identity, or any alias of a cached object that is still alive; version counter, storage address) and, when those miss, on the
-    integrals' CONTENT (_fingerprint: two reductions and one read-back): a fresh copy of equal integrals re-uses the plan instead of
-    rebuilding it.  `device`: where host-resident integrals are staged (the walkers' device)."""
+    integrals' CONTENT (_fingerprint: a few reductions and one read-back): a fresh copy of equal integrals re-uses the plan instead of
+    rebuilding it.  `device`: where host-resident integrals are staged (the walkers' device).
+    Noticed: another tensor object (identity), a view or alias of a cached one, any in-place write torch tracks (copy_, an edit through a
+    view, mul_ on a slice: they bump the version counter the views share), and other content, element order included (a permutation of the
+    same values is another key).  NOT noticed: writes that bypass the version counter -- through `.data` (`t.data.copy_(...)`), through a
+    numpy array sharing a CPU tensor's memory, or by a kernel outside torch -- since seeing them would take a full reduction on every call.
+    After such a write, pass new tensor objects."""
     import weakref
 
     if sorb % 2 or sorb < 2:

@@ -49,7 +49,13 @@ _SIDE_STREAMS: dict = {}
 # popped by the call that uses it and put back when that call has its counters, so two threads never share one; decisions are written once
 # per key.  reset_caches() drops everything (e.g. between two systems in one process).  The C ABI underneath has no global state at all.
 _LOCK = __import__("threading").RLock()
-_CALL_TOKEN: list = [None]  # the total_energy call in progress (an object per call): what per-parameter-state caches of local_energy are valid for
+# .value: the total_energy call in progress in THIS thread (an object per call, restored when the call ends or raises): what per-parameter-state
+# caches of local_energy are valid for
+_CALL_TOKEN = __import__("threading").local()
+
+
+def _call_token():
+    return getattr(_CALL_TOKEN, "value", None)
 
 
 def _side_stream(device):
@@ -290,11 +296,16 @@ def _keys_index_for(WF_LUT, n: int, sorb: int):
     force = SS_INDEX if SS_INDEX is not None else {"1": True, "0": False}.get(os.environ.get("PYNQS_SS_INDEX", ""), None)
     if force is False or sorb % 2:
         return None
+    import weakref
+
     keys = WF_LUT.bra_key
     nk, words = keys.size(0), (sorb - 1) // 64 + 1
     cached = getattr(WF_LUT, "_keys_index", None)
-    if cached is not None and (cached.nkeys != nk or cached.index.device != keys.device or getattr(WF_LUT, "_keys_index_of", None) != keys.data_ptr()):
-        cached = None  # (the table was moved or rebuilt)
+    of = getattr(WF_LUT, "_keys_index_of", None)   # (weakref(keys), version counter of keys) the index was built for
+    ver = CX._ver(keys)
+    if cached is not None and (cached.nkeys != nk or cached.index.device != keys.device or not isinstance(of, tuple) or of[0]() is not keys
+                               or of[1] != ver or ver < 0):
+        cached = None  # (the table was moved, rebuilt or written in place; untracked keys -- inference mode -- are indexed on every call)
     if cached is None:
         if torch.cuda.is_current_stream_capturing():
             return None  # (the build synchronises)
@@ -307,7 +318,7 @@ def _keys_index_for(WF_LUT, n: int, sorb: int):
             return None
         cached = CX.keys_index_build(keys, sorb)
         try:
-            WF_LUT._keys_index, WF_LUT._keys_index_of = cached, keys.data_ptr()
+            WF_LUT._keys_index, WF_LUT._keys_index_of = cached, (weakref.ref(keys), ver)
         except AttributeError:
             pass
     if force is None and cached.per_walker * SS_INDEX_CANDIDATE_COST > nk * SS_INDEX_PAIR_COST[words]:
@@ -581,8 +592,10 @@ def reduce_front_launch(x: Tensor, h1e: Tensor, h2e: Tensor, sorb: int, nele: in
                 _FRONT_NODEDUP.pop(nk)
                 _FRONT_NODEDUP_CALLS[nk] = 0
         caps = _FRONT_NODEDUP.get(nk)
-    if fe is not None and caps is not None and fe.dedup:
-        fe = None   # (a workspace from before the decision to drop the table, e.g. the second slot of total_energy's look-ahead)
+    if fe is not None and fe.dedup == (caps is not None):
+        # (a workspace from before the decision to drop the table, e.g. the second slot of total_energy's look-ahead; or a table-less one
+        # when the decision is measured again: that call must run WITH the table, else reduce_front_finish has nothing to count)
+        fe = None
     if fe is None:
         fe = _new_front(n, x, h1e, sorb, nele, noa, nob, eps_sample, pm1_dtype, want_pm1) if caps is None else \
             _new_front(n, x, h1e, sorb, nele, noa, nob, eps_sample, pm1_dtype, want_pm1, caps[0], caps[1], dedup=False)
@@ -740,7 +753,7 @@ def local_energy(
                 extra = ansatz.module.extra
                 # valid within ONE total_energy call (its token): parameters updated through `p.data.add_` -- the reference's own GD step,
                 # vmc/optim/_base.py:619 -- keep their version counters, so nothing across calls proves that f is still current
-                stamp = (id(extra), WF_LUT.bra_key.data_ptr(), WF_LUT.bra_key.size(0), str(WF_LUT.dtype), _CALL_TOKEN[0])
+                stamp = (id(extra), WF_LUT.bra_key.data_ptr(), WF_LUT.bra_key.size(0), str(WF_LUT.dtype), _call_token())
                 cached = getattr(WF_LUT, "_pynqs_f_keys", None)
                 if cached is not None and cached[0] == stamp and stamp[4] is not None:
                     f_keys = cached[1]
@@ -1084,76 +1097,79 @@ def total_energy(
     device = x.device
     eloc = torch.zeros(dim, device=device).to(dtype)
     sloc = torch.zeros_like(eloc)
-    _CALL_TOKEN[0] = object()
-    assert fp_batch > 0 or fp_batch == -1
-    assert nbatch > 0 or nbatch in (-1, 0)
-    if nbatch == 0:
-        nbatch = auto_nbatch(x, h1e, sorb, nele, noa, nob, ansatz, WF_LUT, dtype, reduce_psi, eps_sample, use_sample_space, use_multi_psi,
-                             use_spin_flip, use_spin_raising)
-    if nbatch == -1:
-        nbatch = dim
-    ends = split_batch_idx(dim, min_batch=nbatch) if dim else []
+    prev_token = _call_token()
+    _CALL_TOKEN.value = object()
+    try:
+        assert fp_batch > 0 or fp_batch == -1
+        assert nbatch > 0 or nbatch in (-1, 0)
+        if nbatch == 0:
+            nbatch = auto_nbatch(x, h1e, sorb, nele, noa, nob, ansatz, WF_LUT, dtype, reduce_psi, eps_sample, use_sample_space, use_multi_psi,
+                                 use_spin_flip, use_spin_raising)
+        if nbatch == -1:
+            nbatch = dim
+        ends = split_batch_idx(dim, min_batch=nbatch) if dim else []
 
-    def _ansatz_batch(x: Tensor, func: Callable[[Tensor], Tensor]) -> Tensor:
-        return ansatz_batch(func, x, fp_batch, sorb, device, dtype)
+        def _ansatz_batch(x: Tensor, func: Callable[[Tensor], Tensor]) -> Tensor:
+            return ansatz_batch(func, x, fp_batch, sorb, device, dtype)
 
-    _ansatz_batch.accepts_pm1_rows = True  # (public_function.ansatz_batch takes uint8 determinants or ready +-1 rows)
+        _ansatz_batch.accepts_pm1_rows = True  # (public_function.ansatz_batch takes uint8 determinants or ready +-1 rows)
 
-    # REDUCE with several chunks of walkers: the front end of chunk k + 1 runs on a second stream while the ansatz works on the distinct x'
-    # of chunk k ("overlap kernel(i+1) with forward(i) on two HIP streams"); two workspaces take turns.  OVERLAP = False or
-    # PYNQS_OVERLAP=0: everything on the current stream.
-    starts = [0] + list(ends[:-1])
-    look_ahead = (OVERLAP and reduce_psi and not use_sample_space and len(ends) >= 2 and x.is_cuda
-                  and all(_front_ok(x[b:e], h1e, sorb, nele, noa, nob, eps_sample) for b, e in ((starts[0], ends[0]), (starts[-1], ends[-1]))))
-    tickets, done = {}, {}
-    if look_ahead:
-        main = torch.cuda.current_stream(device)
-        side = _side_stream(device)
-        ht_, rbm_fwd_ = _reduce_front_options(ansatz, WF_LUT, dtype, use_multi_psi, use_spin_flip)
-
-        xc = x.contiguous()  # (once, on the main stream: the chunks are views of it, no copy kernel runs between the streams)
-
-        def launch(k: int) -> None:
-            xs = xc[starts[k]:ends[k]]
-            if k == 0:
-                side.wait_stream(main)  # (xc and whatever else the caller wrote on the main stream; later launches read nothing newer than that --
-                #                          waiting every time would hold chunk k + 1's front end back until chunk k - 1 has been contracted)
-            if k >= 2:
-                side.wait_event(done[k - 2])  # the workspace of slot k % 2 is free once chunk k - 2 has been contracted
-            with torch.cuda.stream(side):
-                # (consumer: the workspace is allocated in the side stream's pool and read on the main stream -- the allocator must not hand
-                # its memory out again while main-stream work on it is pending)
-                tickets[k] = reduce_front_launch(xs, h1e, h2e, sorb, nele, noa, nob, eps, int(eps_sample), ht_, want_pm1=not rbm_fwd_, slot=k % 2, route=True,
-                                                 consumer=main)
-
-        launch(0)
-    begin = 0
-    for k, end in enumerate(ends):
-        ticket = None
+        # REDUCE with several chunks of walkers: the front end of chunk k + 1 runs on a second stream while the ansatz works on the distinct x'
+        # of chunk k ("overlap kernel(i+1) with forward(i) on two HIP streams"); two workspaces take turns.  OVERLAP = False or
+        # PYNQS_OVERLAP=0: everything on the current stream.
+        starts = [0] + list(ends[:-1])
+        look_ahead = (OVERLAP and reduce_psi and not use_sample_space and len(ends) >= 2 and x.is_cuda
+                      and all(_front_ok(x[b:e], h1e, sorb, nele, noa, nob, eps_sample) for b, e in ((starts[0], ends[0]), (starts[-1], ends[-1]))))
+        tickets, done = {}, {}
         if look_ahead:
-            ticket = tickets.pop(k, None)
-            if ticket is not None:
-                ticket["ev"].synchronize()       # (host: the counters of chunk k are there)
-                main.wait_event(ticket["ev"])     # (device: chunk k's records are there before the ansatz / contraction read them)
-            # (a chunk whose rows outgrew the front end's LDS list sends the rest of the call to the multi-pass path: no more tickets)
-            if k + 1 < len(ends) and _front_ok(x[starts[k + 1]:ends[k + 1]], h1e, sorb, nele, noa, nob, eps_sample):
-                launch(k + 1)                     # runs while the ansatz works on chunk k
-        _eloc, _sloc, _psi, _ = local_energy(
-            ticket["x"] if ticket is not None else x[begin:end], h1e, h2e, ansatz, _ansatz_batch, sorb, nele, noa, nob, dtype=dtype, WF_LUT=WF_LUT,
-            use_spin_raising=False if reduce_psi else use_spin_raising, h1e_spin=h1e_spin, h2e_spin=h2e_spin, use_unique=use_unique,
-            reduce_psi=reduce_psi, eps=eps, eps_sample=eps_sample, use_sample_space=use_sample_space, index=(begin, end), alpha=alpha,
-            use_multi_psi=use_multi_psi, extra_norm=extra_norm, use_spin_flip=use_spin_flip, _front_ticket=ticket)
-        if look_ahead:
-            done[k] = torch.cuda.Event()
-            done[k].record(main)
-        if reduce_psi and use_spin_raising:
-            # <S-S+> is recomputed in the sample space (etot.py:119-142)
-            _sloc, _, _, _ = local_energy(x[begin:end], h1e_spin, h2e_spin, ansatz, _ansatz_batch, sorb, nele, noa, nob, dtype=dtype,
-                                          WF_LUT=WF_LUT, use_spin_raising=False, use_sample_space=True, index=(begin, end), alpha=alpha)
-        eloc[begin:end] = _eloc
-        sloc[begin:end] = _sloc
-        begin = end
-    _CALL_TOKEN[0] = None
+            main = torch.cuda.current_stream(device)
+            side = _side_stream(device)
+            ht_, rbm_fwd_ = _reduce_front_options(ansatz, WF_LUT, dtype, use_multi_psi, use_spin_flip)
+
+            xc = x.contiguous()  # (once, on the main stream: the chunks are views of it, no copy kernel runs between the streams)
+
+            def launch(k: int) -> None:
+                xs = xc[starts[k]:ends[k]]
+                if k == 0:
+                    side.wait_stream(main)  # (xc and whatever else the caller wrote on the main stream; later launches read nothing newer than that --
+                    #                          waiting every time would hold chunk k + 1's front end back until chunk k - 1 has been contracted)
+                if k >= 2:
+                    side.wait_event(done[k - 2])  # the workspace of slot k % 2 is free once chunk k - 2 has been contracted
+                with torch.cuda.stream(side):
+                    # (consumer: the workspace is allocated in the side stream's pool and read on the main stream -- the allocator must not hand
+                    # its memory out again while main-stream work on it is pending)
+                    tickets[k] = reduce_front_launch(xs, h1e, h2e, sorb, nele, noa, nob, eps, int(eps_sample), ht_, want_pm1=not rbm_fwd_, slot=k % 2, route=True,
+                                                     consumer=main)
+
+            launch(0)
+        begin = 0
+        for k, end in enumerate(ends):
+            ticket = None
+            if look_ahead:
+                ticket = tickets.pop(k, None)
+                if ticket is not None:
+                    ticket["ev"].synchronize()       # (host: the counters of chunk k are there)
+                    main.wait_event(ticket["ev"])     # (device: chunk k's records are there before the ansatz / contraction read them)
+                # (a chunk whose rows outgrew the front end's LDS list sends the rest of the call to the multi-pass path: no more tickets)
+                if k + 1 < len(ends) and _front_ok(x[starts[k + 1]:ends[k + 1]], h1e, sorb, nele, noa, nob, eps_sample):
+                    launch(k + 1)                     # runs while the ansatz works on chunk k
+            _eloc, _sloc, _psi, _ = local_energy(
+                ticket["x"] if ticket is not None else x[begin:end], h1e, h2e, ansatz, _ansatz_batch, sorb, nele, noa, nob, dtype=dtype, WF_LUT=WF_LUT,
+                use_spin_raising=False if reduce_psi else use_spin_raising, h1e_spin=h1e_spin, h2e_spin=h2e_spin, use_unique=use_unique,
+                reduce_psi=reduce_psi, eps=eps, eps_sample=eps_sample, use_sample_space=use_sample_space, index=(begin, end), alpha=alpha,
+                use_multi_psi=use_multi_psi, extra_norm=extra_norm, use_spin_flip=use_spin_flip, _front_ticket=ticket)
+            if look_ahead:
+                done[k] = torch.cuda.Event()
+                done[k].record(main)
+            if reduce_psi and use_spin_raising:
+                # <S-S+> is recomputed in the sample space (etot.py:119-142)
+                _sloc, _, _, _ = local_energy(x[begin:end], h1e_spin, h2e_spin, ansatz, _ansatz_batch, sorb, nele, noa, nob, dtype=dtype,
+                                              WF_LUT=WF_LUT, use_spin_raising=False, use_sample_space=True, index=(begin, end), alpha=alpha)
+            eloc[begin:end] = _eloc
+            sloc[begin:end] = _sloc
+            begin = end
+    finally:
+        _CALL_TOKEN.value = prev_token   # (also when a chunk raises: a later direct local_energy call must not match this call's token)
     if torch.any(torch.isnan(eloc)):
         raise ValueError("The Local energy exists nan")
     return eloc, sloc, torch.zeros(1, device=device, dtype=dtype)

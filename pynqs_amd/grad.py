@@ -72,7 +72,8 @@ class GraphedGrad:
     submission.  The cross-rank reduction DistributedDataParallel would do in its last backward is ONE all-reduce of the
     flat gradient buffer after the replay (RCCL over xGMI; mean over the ranks, DDP's convention).  Parameters keep their
     identity: after the call every p.grad is a view into that buffer, so any torch optimizer works unchanged.
-    Restrictions (otherwise use grad()): fixed number of walkers per call, float +-1 states, parameters not re-allocated.
+    Restrictions (otherwise use grad()): fixed number of walkers per call, float +-1 states, parameters not re-allocated (checked on
+    every call: a replaced Parameter or `p.data = ...` raises RuntimeError).
     With a REAL dtype the logarithm of a negative amplitude is nan (grad() raises "negative numbers in the log-psi" there): the replay's
     loss is checked after every call (one scalar read-back; check_nan=False leaves it to the caller) and the gradients are not
     installed when it is nan.  Complex dtypes need no check (ln of a non-zero complex number is finite).
@@ -84,6 +85,7 @@ class GraphedGrad:
         self.module, self.dtype = m, dtype
         self.check_nan = (not dtype.is_complex) if check_nan is None else check_nan
         self.params = [p for p in m.parameters() if p.requires_grad]
+        self.ptrs = [p.data_ptr() for p in self.params]   # (what the graph reads: checked on every call)
         dev = device if device is not None else self.params[0].device
         rdt = dtype.to_real() if dtype.is_complex else dtype
         self.states = torch.zeros((n, sorb), dtype=rdt, device=dev)
@@ -120,7 +122,14 @@ class GraphedGrad:
             v.copy_(g)
         self.loss.copy_(loss.detach().reshape(1))
 
+    def _check_params(self) -> None:
+        cur = [p for p in self.module.parameters() if p.requires_grad]
+        if len(cur) != len(self.params) or any(a is not b or a.data_ptr() != ptr for a, b, ptr in zip(cur, self.params, self.ptrs)):
+            raise RuntimeError("GraphedGrad: the module's parameters were replaced or re-allocated since the graph was captured (the replay "
+                               "would read the old storage and fill the old tensors' .grad); build a new GraphedGrad")
+
     def __call__(self, states: Tensor, state_prob: Tensor, eloc: Tensor, e_total, extra_psi_pow=1.0) -> Tensor:
+        self._check_params()
         self.states.copy_(states)
         self.prob.copy_(state_prob.real if state_prob.is_complex() else state_prob)
         self.eloc.copy_(eloc)
@@ -171,20 +180,31 @@ class FusedRbmGrad:
         else:
             raise ValueError("FusedRbmGrad: the module is not a real (rbm_type 'real') or complex-parameter RBM")
         self.N, self.module, self.sorb = N, m, sorb
-        self.params = [getattr(m, nm) for nm in self.names]
-        if any(p.dtype != torch.float64 or not p.is_cuda for p in self.params):
+        params = [getattr(m, nm) for nm in self.names]
+        if any(p.dtype != torch.float64 or not p.is_cuda for p in params):
             raise ValueError("FusedRbmGrad: float64 parameters on the GPU")
-        dev = self.params[0].device
-        self.H = self.params[0].size(0)
+        dev = params[0].device
+        self.H = params[0].size(0)
+        self.shapes = [p.shape for p in params]
         # one buffer for the gradients AND the loss (its last element): one all-reduce per step over the ranks, not two
-        self.flat = torch.zeros(sum(p.numel() for p in self.params) + 1, dtype=torch.float64, device=dev)
+        self.flat = torch.zeros(sum(p.numel() for p in params) + 1, dtype=torch.float64, device=dev)
         self.views, o = [], 0
-        for p in self.params:
+        for p in params:
             self.views.append(self.flat[o:o + p.numel()].view_as(p))
             o += p.numel()
         self.loss = self.flat[o:o + 1]
         self.work = None
         self.events = None
+
+    @property
+    def params(self):
+        """the module's parameters as they are NOW (load_state_dict(..., assign=True) or `module.weights = nn.Parameter(...)` replace them)"""
+        ps = [getattr(self.module, nm) for nm in self.names]
+        if any(p.dtype != torch.float64 or p.device != self.flat.device for p in ps):
+            raise ValueError("FusedRbmGrad: float64 parameters on the GPU")
+        if [p.shape for p in ps] != self.shapes:
+            raise ValueError(f"FusedRbmGrad: parameter shapes changed since construction ({self.shapes} -> {[p.shape for p in ps]})")
+        return ps
 
     def __call__(self, onv: Tensor, state_prob: Tensor, eloc: Tensor, e_total, extra_psi_pow=1.0) -> Tensor:
         N, dev = self.N, self.flat.device
@@ -205,7 +225,8 @@ class FusedRbmGrad:
         need = N.lib().pynqs_rbm_grad_workspace(n, self.sorb, self.H, self.flavour)
         if self.work is None or self.work.numel() * 8 < need:
             self.work = torch.empty(max(need // 8, 1), dtype=torch.float64, device=dev)
-        W, hb, vb = (p.detach().contiguous() for p in self.params)
+        params = self.params
+        W, hb, vb = (p.detach().contiguous() for p in params)
         gw, ghb, gvb = self.views
         N.check(N.lib().pynqs_rbm_grad(onv.contiguous().data_ptr(), n, self.sorb, W.data_ptr(), hb.data_ptr(), vb.data_ptr(), self.H, self.flavour,
                                        prob.data_ptr(), el.data_ptr(), int(cplx), et.data_ptr(), pw.data_ptr() if pw is not None else None,
@@ -224,6 +245,6 @@ class FusedRbmGrad:
         if ev is not None:
             ev[1].record()
             self.events.append(ev)
-        for p, v in zip(self.params, self.views):
+        for p, v in zip(params, self.views):
             p.grad = v
         return self.loss * ws if ws > 1 else self.loss.clone()
