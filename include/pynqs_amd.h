@@ -444,8 +444,13 @@ int pynqs_rbm_forward(const uint64_t *onv, int64_t n, int sorb, const double *we
  *                                    ~64 x 64) is read from the L2 by one wave per row, the lanes over the hidden units
  * Flavours and parameter layouts as pynqs_rbm_forward.  exp(-2 theta_h) is formed for the parents: if some Re theta_h < -340 the prepare
  * step raises a flag in the table and pynqs_rbm_forward_children computes every row from scratch instead (pynqs_rbm_forward's
- * algorithm inside the same kernel).  Values agree with pynqs_rbm_forward to rounding (typically
- * 1e-14 relative; a factor 2cosh(theta_h) near zero amplifies it).                                                                      */
+ * algorithm inside the same kernel).  Below that, negative theta_h still make the factors 1 + q_h large (e^100 at theta_h = -50): a row
+ * whose product of them, or whose q_h after the flips, leaves the range of a double is detected (the product is inf or nan) and computed
+ * from scratch inside the same launch, as is a row that flips an orbital with |4 Re W_ho| > 80 (its table entry is stored as nan); the
+ * other rows keep the parents' route.  Such rows cost a from-scratch evaluation on top: a model with many hidden units at theta_h << -40
+ * is served no faster than by pynqs_rbm_forward.  For every row whose psi is a finite double the value obeys the rounding bound of
+ * pynqs_rbm_forward, |psi / psi_exact - 1| <= 2^-53 (sorb + nhidden + 16) cond(x), cond(x) = 1 + sum_h |tanh theta_h| (|b_h| + sum_o
+ * |W_ho|) + sum_o |a_o| (tests/rbm_exact.py; typically 1e-14 relative, a factor 2cosh(theta_h) near zero amplifies it through cond).      */
 int64_t pynqs_rbm_children_table_bytes(int64_t nwalkers, int sorb, int nhidden, int flavour);
 int pynqs_rbm_children_prepare(const uint64_t *walkers, int64_t nwalkers, int sorb, const double *weights, const double *hidden_bias,
                                const double *visible_bias, int nhidden, int flavour, void *table, void *stream);

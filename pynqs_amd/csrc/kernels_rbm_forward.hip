@@ -35,6 +35,8 @@ struct Prod {
     re = ldexp(re, -k); im = ldexp(im, -k);
     e2 += k;
   }
+  // false once a factor or the product left the range of a double (inf, or the nan of inf - inf / inf * 0): it stays that way
+  __device__ __forceinline__ bool finite() const { return fabs(re) < __builtin_inf() && fabs(im) < __builtin_inf(); }
   // *= 2cosh(x + iy) = e^{s(x + iy)} (1 + e^{-2s(x + iy)}),  s = sign(x)
   template <bool CPLX>
   __device__ __forceinline__ void times_2cosh(double x, double y) {
@@ -145,6 +147,13 @@ __global__ __launch_bounds__(kBlock) void rbm_forward_kernel(const uint64_t *__r
 //   flag    one double after the factors: non-zero if some parent has Re theta_h < -340, where q_h = exp(-2 theta_h) leaves the range of a
 //           double: the children kernel then computes every row from scratch (rbm_forward_row, the plain kernel's body)
 // all entries real or (re, im) by the flavour.
+// The factors 1 + q_h are NOT bounded for negative theta_h (the plain forward's are: it uses |theta_h|): q_h = e^100 for theta_h = -50, and
+// eight such factors between two renorm() calls, or one q_h beyond e^709 after four flips, overflow although psi itself is an ordinary
+// number.  An overflow cannot pass unseen -- inf and nan survive every later multiplication -- so both kernels look at the finished
+// product once (Prod::finite) and compute a row whose product is not finite from scratch, as they do for strangers; the inner loops are
+// as they were.  What could lose digits without overflowing is an UNDERFLOW on the way from q_h(parent) to q_h(child) followed by a large
+// factor; with |4 W_ho| <= 80 (factors within e^+-80) every intermediate of a q_h(child) >= 1e-17 is a normal number, and an entry with
+// |4 Re W_ho| > 80 is stored as nan: a child that flips such an orbital gets a nan product and goes the same way.
 __host__ __device__ inline int children_hp(int H) { return (H + 2) | 1; }
 
 template <bool CPLX>
@@ -162,7 +171,7 @@ __global__ __launch_bounds__(kBlock) void rbm_children_factors_kernel(int sorb, 
     re = h < H ? 1.0 : 0.0;
   } else if (h < H) {
     const double wr = W[((size_t)h * sorb + o) * C], wi = CPLX ? W[((size_t)h * sorb + o) * C + 1] : 0.0;
-    const double m = exp(-4.0 * sign * wr);
+    const double m = fabs(4.0 * wr) <= 80.0 ? exp(-4.0 * sign * wr) : __builtin_nan("");  // (nan: see above; also for a nan weight)
     if constexpr (CPLX) {
       double sn, cs;
       sincos(-4.0 * sign * wi, &sn, &cs);
@@ -364,7 +373,7 @@ __global__ __launch_bounds__(kChildBlock) void rbm_forward_children_kernel(const
         axi += wl[(size_t)(at[q] + H + 1) * C + 1];
       }
     }
-    stranger = stranger || nflip > 4;
+    stranger = stranger || nflip > 4 || !P.finite();  // (a product that overflowed: see the table's description)
     if (__ballot(stranger)) {  // (rare: the whole wave walks the parameters, the strangers keep the result)
       uint64_t ket[LEN];
 #pragma unroll
@@ -444,7 +453,7 @@ __global__ __launch_bounds__(kBlock) void rbm_forward_children_wave_kernel(const
         }
       }
     }
-    if (stranger || nflip > 4) {  // (wave-uniform, rare: from scratch, every lane the same row)
+    const auto from_scratch = [&]() {  // (every lane the same row)
       uint64_t ket[LEN];
 #pragma unroll
       for (int w = 0; w < LEN; ++w) ket[w] = onv[i * LEN + w];
@@ -452,6 +461,9 @@ __global__ __launch_bounds__(kBlock) void rbm_forward_children_wave_kernel(const
       double a2r, a2i;
       rbm_forward_row<LEN, FLAVOUR>(ket, sorb, H, W, hb, vb, P2, a2r, a2i);
       if (lane == 0) write_psi<FLAVOUR>(psi, i, P2, a2r, a2i);
+    };
+    if (stranger || nflip > 4) {  // (wave-uniform, rare)
+      from_scratch();
       continue;
     }
     const double *__restrict__ tp = table + (size_t)p * (size_t)(H + 2) * C;
@@ -495,6 +507,10 @@ __global__ __launch_bounds__(kBlock) void rbm_forward_children_wave_kernel(const
       P.e2 += oe;   // (mantissas in [0.5, 1): 64 of them multiply to >= 2^-64, no renormalisation on the way)
     }
     P.renorm();
+    if (__ballot(!P.finite())) {  // (a product that overflowed: see the table's description; the ballot keeps the branch wave-uniform)
+      from_scratch();
+      continue;
+    }
     if (lane == 0) {
       double axr = tp[(size_t)(H + 1) * C], axi = CPLX ? tp[(size_t)(H + 1) * C + 1] : 0.0;
       P.lin = tp[(size_t)H * C];

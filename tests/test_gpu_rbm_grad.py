@@ -1,6 +1,6 @@
 """pynqs_rbm_grad / grad.FusedRbmGrad: the analytic energy-gradient estimator of the RBM amplitudes (vmc/grad/energy_grad.py:118-184 on
 vmc/ansatz/rbm/rbm.py:186-211) against the same estimator through autograd (pynqs_amd.grad.grad, itself pinned on vectors captured from
-the reference: tests/test_gpu_grad.py).  Tolerance: 1e-11 relative to the largest gradient entry; the loss to 1e-10."""
+the reference: tests/test_grad_golden.py).  Tolerance: 1e-11 relative to the largest gradient entry; the loss to 1e-10."""
 import numpy as np
 import pytest
 import torch
