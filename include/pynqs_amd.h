@@ -466,6 +466,62 @@ int pynqs_rbm_grad(const uint64_t *onv, int64_t n, int sorb, const double *weigh
                    int eloc_is_complex, const double *e_total, const double *pow, double *grad_weights,
                    double *grad_hidden_bias, double *grad_visible_bias, double *loss, void *workspace, void *stream);
 
+/* ---- stochastic reconfiguration for RBM amplitudes, matrix-free (kernels_rbm_sr.hip; vmc/grad/sr.py with vmc/grad/_jacobian.py, the
+ * reference's `sr=True`, which builds a dense P x P matrix and inverts it) ---------------------------------------------------------------
+ * Modules and parameter layouts as pynqs_rbm_grad: PYNQS_RBM_REAL (weights double[nhidden][sorb], hidden_bias [nhidden], visible_bias
+ * [sorb]) or PYNQS_RBM_COMPLEX (the same with a trailing [2] = (re, im)).
+ *  - Real parameter vector: the stored numbers in the order weights, hidden_bias, visible_bias, P_real = P or 2 P doubles with
+ *    P = nhidden sorb + nhidden + sorb.  Every vector below (obar, v, y, rhs, d, r, p) is ONE flat buffer of this layout.
+ *  - O_nk = d ln psi(x_n) / d theta_k = (tanh theta_h x_o, tanh theta_h, x_o), theta = b + W x (no dependence on the visible bias); the two
+ *    real derivatives of a complex parameter stored as (re, im) are (O_nk, i O_nk).
+ *  - Obar_k = sum_n p_n O_nk, p = prob (real; sums to 1 over all ranks; per rank pre-scaled by the world size, so every cross-rank sum is
+ *    an all-reduce SUM divided by the world size).  obar holds (Re, Im) for pairs.
+ *  - S = Re(<O* O> - <O*><O>) on the real parameters: the reference's S_kk (sr.py:87-117) for real parameters; for (re, im) pairs the
+ *    real form [[A, -B], [B, A]] of the Hermitian matrix <O* O>_c = A + i B of the holomorphic parameters (the reference's
+ *    inv(S).real @ F.real is not defined for its own complex layout, its "TODO: S-1 is complex or real").  S is symmetric, >= 0.
+ *  - Product, z_k = v_k or v_k,re + i v_k,im:
+ *      c_n = sum_k (O_nk - Obar_k) z_k = x_n . z_a + sum_h tanh theta_nh (z_b,h + sum_o z_W,ho x_no) - Obar . z,
+ *      y_k = sum_n p_n conj(O_nk) c_n,      (S v)_k = y_k  or  (Re y_k, Im y_k).
+ *  - The SR direction d solves (S + diag_shift I) d = F, F = the gradient exactly as pynqs_rbm_grad returns it (2 Re G, -2 Im G), the
+ *    reference's F_i = 2 Re(<E_loc O_i*> - <E_loc><O_i*>); diag_shift 0.02 is the reference's default.
+ *   pynqs_rbm_sr_workspace : [host] bytes of the workspace for n walkers (-1 on bad arguments): the tanh table, double[nhidden][n] (x2:
+ *        (re, im)), walkers fastest; then the workgroups' partial sums (ceil(n / 32) x P_real doubles, the largest temporary besides the
+ *        table); then Obar . z.  Nothing of size n x P or P x P.
+ *   pynqs_rbm_sr_prepare   : once per solve: tanh theta -> the table (e = exp(-2 |Re theta|): no overflow), obar <- THIS rank's
+ *        sum_n p_n O_nk.  n = 0 gives obar = 0.
+ *   pynqs_rbm_sr_matvec    : y <- THIS rank's y as defined above for the vector v, from the packed bits and the table; obar: the
+ *        ALL-REDUCED Obar, so Obar . z needs no communication.  v and y must not overlap.  n = 0 gives y = 0.
+ *   pynqs_rbm_sr_cg_step   : the vector part of conjugate gradients on (S + diag_shift) d = rhs, np = P_real, one workgroup, scalars
+ *        double[PYNQS_SR_NSCALARS] in device memory (no host synchronisation):
+ *          PYNQS_SR_CG_INIT      d = 0, r = p = rhs, rho = |rhs|^2, iterations = 0; done and converged at once when rhs = 0
+ *          PYNQS_SR_CG_STEP      after y <- matvec(p) (all-reduced SUM over the ranks): Ap = y inv_world + diag_shift p (left in y),
+ *                                alpha = rho / p.Ap, d += alpha p, r -= alpha Ap, rho' = r.r, p = r + (rho' / rho) p, iterations += 1;
+ *                                done when rho' <= tol^2 |rhs|^2 (or p.Ap <= 0: breakdown).  A no-op once done is set, so that the
+ *                                host may enqueue several iterations between read-backs of the scalars.
+ *          PYNQS_SR_CG_RESIDUAL  after y <- matvec(d): r = rhs - (y inv_world + diag_shift d), the TRUE residual, |r|^2 -> PYNQS_SR_TRUE2;
+ *                                converged and done when |r|^2 <= tol^2 |rhs|^2, else p = r, rho = |r|^2 and done is cleared: the
+ *                                iteration goes on from d (the recurrence's residual drifts by rounding over hundreds of steps).
+ * Every sum runs in a fixed order (two stages over the walkers, a tree over the parameters): all results are bit-reproducible.        */
+#define PYNQS_SR_RHO 0       /* r.r of the recurrence */
+#define PYNQS_SR_RHS2 1      /* |rhs|^2 */
+#define PYNQS_SR_DONE 2      /* 0.0 / 1.0 */
+#define PYNQS_SR_ITER 3      /* iterations performed (a whole number) */
+#define PYNQS_SR_TRUE2 4     /* the last true |r|^2 (PYNQS_SR_CG_RESIDUAL) */
+#define PYNQS_SR_PAP 5       /* the last p.Ap */
+#define PYNQS_SR_CONVERGED 6 /* 0.0 / 1.0: the TRUE residual met the tolerance */
+#define PYNQS_SR_BREAKDOWN 7 /* 1.0: p.Ap <= 0 or not a number */
+#define PYNQS_SR_NSCALARS 8
+#define PYNQS_SR_CG_INIT 0
+#define PYNQS_SR_CG_STEP 1
+#define PYNQS_SR_CG_RESIDUAL 2
+int64_t pynqs_rbm_sr_workspace(int64_t n, int sorb, int nhidden, int flavour);
+int pynqs_rbm_sr_prepare(const uint64_t *onv, int64_t n, int sorb, const double *weights, const double *hidden_bias, int nhidden,
+                         int flavour, const double *prob, void *workspace, double *obar, void *stream);
+int pynqs_rbm_sr_matvec(const uint64_t *onv, int64_t n, int sorb, int nhidden, int flavour, const double *prob, const void *workspace,
+                        const double *obar, const double *v, double *y, void *stream);
+int pynqs_rbm_sr_cg_step(int mode, int64_t np, double *y, const double *rhs, double *d, double *r, double *p, double *scalars,
+                         double inv_world, double diag_shift, double tol, void *stream);
+
 /* ---- many-chain Metropolis sampling (vmc/sample.py:480-569, Sampler.MCMC; the reference runs one chain in a Python loop) -------------
  * Semantics shared by both entry points (and by pynqs_amd/mcmc.py, which drives them):
  *  - nchains independent chains; chain i of a call has the global index c = chain_base + i (c < 2^32).  Steps are numbered t = 0, 1, ...
