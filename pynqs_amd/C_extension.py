@@ -15,6 +15,9 @@ like bind.cpp:290-299.
 """
 from __future__ import annotations
 
+import os
+import warnings
+import weakref
 from typing import Tuple
 
 import numpy as np
@@ -172,8 +175,6 @@ def plan_for(h1e: Tensor, h2e: Tensor, sorb: int, device: "torch.device | None" 
     same values is another key).  NOT noticed: writes that bypass the version counter -- through `.data` (`t.data.copy_(...)`), through a
     numpy array sharing a CPU tensor's memory, or by a kernel outside torch -- since seeing them would take a full reduction on every call.
     After such a write, pass new tensor objects."""
-    import weakref
-
     if sorb % 2 or sorb < 2:
         return None
     ver = (_ver(h1e), _ver(h2e), h1e.data_ptr(), h2e.data_ptr())
@@ -211,8 +212,6 @@ def plan_for(h1e: Tensor, h2e: Tensor, sorb: int, device: "torch.device | None" 
     key = (sorb, h2e.numel(), str(pl.device))
     _PLAN_BUILDS[key] = _PLAN_BUILDS.get(key, 0) + 1
     if _PLAN_BUILDS[key] == _PLAN_REBUILD_WARN:
-        import warnings
-
         warnings.warn(f"pynqs_amd: the integral plan for sorb = {sorb} ({pl.buf.numel() * pl.buf.element_size() / 2**20:.0f} MiB) has been rebuilt "
                       f"{_PLAN_REBUILD_WARN} times: the caller passes new h1e / h2e tensor objects (or modifies them in place) on every call. "
                       "Keep the same tensors alive between calls to reuse the plan.", RuntimeWarning, stacklevel=3)
@@ -226,8 +225,6 @@ def integrals_f64(h1e: Tensor, h2e: Tensor) -> Tuple[Tensor, Tensor]:
     """float64 copies of float32 integrals (cached per tensor pair like the plans), for the fused local-energy kernels, which
     exist in float64 only: every float32 value is a float64 value, so the kernels see exactly the caller's numbers and only the
     accumulation is done in (more than) the precision the reference's float32 path has (cpu_tensor.cpp:249,298 dispatch)."""
-    import weakref
-
     if h1e.dtype == torch.float64:
         return h1e, h2e
     ver = (_ver(h1e), _ver(h2e), h1e.data_ptr(), h2e.data_ptr())
@@ -294,13 +291,11 @@ def onv_to_tensor(bra: Tensor, sorb: int) -> Tensor:
 # fused plan kernel in its Hmat-only form -- bit-identical values at a fifth of the generic pair kernel's time.
 _last_comb = None  # (weakref(comb), comb ptr, comb version, weakref(bra), bra ptr, bra version, sorb, nele, noA, noB)
 REUSE_COMB = True
-CHECK_COMB_REUSE = __import__("os").environ.get("PYNQS_CHECK_COMB_REUSE", "0") == "1"
+CHECK_COMB_REUSE = os.environ.get("PYNQS_CHECK_COMB_REUSE", "0") == "1"
 
 
 def _remember_comb(comb: Tensor, bra: Tensor, sorb: int, nele: int, noA: int, noB: int) -> None:
     global _last_comb
-    import weakref
-
     _last_comb = (weakref.ref(comb), comb.data_ptr(), _ver(comb), weakref.ref(bra), bra.data_ptr(), _ver(bra), sorb, nele, noA, noB) \
         if comb.is_cuda and bra.is_cuda and _ver(comb) >= 0 and _ver(bra) >= 0 else None
 

@@ -3,9 +3,11 @@ its sources (pynqs_amd/csrc/libpynqs_amd.so) so that it travels with the reposit
 from __future__ import annotations
 
 import glob
+import hashlib
 import os
 import shutil
 import subprocess
+from concurrent.futures import ThreadPoolExecutor
 
 _HERE = os.path.dirname(os.path.abspath(__file__))
 CSRC = os.path.join(_HERE, "csrc")
@@ -26,8 +28,6 @@ def sources():
 def source_hash() -> str:
     """sha256 over the native sources (csrc/*.hip, csrc/*.h, include/pynqs_amd.h; names and contents): what a stored profile of a kernel
     (profiles/pmc_*.json, written by tools/pmc_roofline.py) was measured on -- bench.py refuses to quote a profile of another tree."""
-    import hashlib
-
     h = hashlib.sha256()
     files = sources() + sorted(glob.glob(os.path.join(CSRC, "*.h"))) + [os.path.join(_HERE, "..", "include", "pynqs_amd.h")]
     for f in files:
@@ -57,8 +57,6 @@ def build_native(force: bool = False, verbose: bool = False) -> str:
     """One object per .hip file (recompiled only when it or a header is newer), compiled in parallel, then linked."""
     if not force and not needs_build():
         return LIB
-    from concurrent.futures import ThreadPoolExecutor
-
     objdir = os.path.join(CSRC, "build")
     os.makedirs(objdir, exist_ok=True)
     hdr_t = max(os.path.getmtime(d) for d in glob.glob(os.path.join(CSRC, "*.h")) + [os.path.join(_HERE, "..", "include", "pynqs_amd.h")])

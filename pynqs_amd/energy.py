@@ -20,38 +20,60 @@ What differs is where the work happens (all on the MI355X, through pynqs_amd.C_e
     writing the whole (batch, ncomb) comb / Hmat and filtering afterwards; the projected / multi-psi / <S-S+> factors are evaluated on
     the kept records.
 `FUSED = False` (and FUSED_RBM / FUSED_SAMPLED) force the generic tensor path (used by the tests to cross-check the fast paths).
+
+local_energy is a dispatcher over one function per path, asked in this order (each returns (eloc, sloc, psi, times); None: it declines):
+  1. _eloc_sample_space_fused        SAMPLE_SPACE in one kernel per sum
+  2. _eloc_simple_rbm                SIMPLE with an RBM evaluated in the kernel (declines: not such an RBM, or it does not fit the LDS)
+  3. _eloc_reduce_front              REDUCE through the one-launch front end (declines: a long row outgrew its LDS list)
+  4. _eloc_reduce_multipass          REDUCE, eps_sample = 0, compaction in several passes
+  5. _eloc_reduce_multipass_sampled  REDUCE, eps_sample > 0, plain form, selection and draws in several passes
+  6. _eloc_generic                   the reference's tensor algebra on the (batch, ncomb) matrices
 """
 from __future__ import annotations
 
+import logging
+import math
 import os
+import threading
 import time
+import weakref
+from dataclasses import dataclass
 from functools import partial
+from types import SimpleNamespace
 from typing import Callable, Optional, Tuple
 
-import numpy as np
 import torch
-from torch import Tensor, nn
+from torch import Tensor
 
 from . import C_extension as CX
 from . import _native as N
 from . import reduce_front as RF
 from .C_extension import get_comb_hij_fused, get_hij_torch
-from .distributed import get_rank
+from .distributed import get_rank, get_world_size
 from .public_function import (SpinProjection, WavefunctionLUT, ansatz_batch, check_para, get_nbatch, get_Num_SinglesDoubles,
                               spin_flip_onv, spin_flip_sign, split_batch_idx, unique_onv)
+from .rbm import ComplexRBM, RealRBM
+
+_LOG = logging.getLogger("pynqs_amd")
+
+
+def _env_flag(name: str, default: Optional[bool]) -> Optional[bool]:
+    """The "1" / "0" switches of the environment: True / False, and `default` for anything else (or nothing) there."""
+    return {"1": True, "0": False}.get(os.environ.get(name, ""), default)
+
 
 FUSED = True  # use the fused sample-space / reduce kernels when the configuration allows it
 FUSED_SAMPLED = True  # REDUCE with eps_sample > 0: select and draw on chip (reduce_compact_sampled) instead of torch.multinomial on the matrix
 FUSED_RBM = True  # SIMPLE method: evaluate a real RBM ansatz inside the kernel (pynqs_eloc_rbm) instead of calling the module
-OVERLAP = __import__("os").environ.get("PYNQS_OVERLAP", "1") != "0"  # total_energy: front end of the next walker chunk on a second stream
+OVERLAP = _env_flag("PYNQS_OVERLAP", True)  # total_energy: front end of the next walker chunk on a second stream
 _SIDE_STREAMS: dict = {}
 # The caches below (front-end workspaces, routing decisions, timed kernel choices) are process-wide and guarded by ONE lock: a workspace is
 # popped by the call that uses it and put back when that call has its counters, so two threads never share one; decisions are written once
 # per key.  reset_caches() drops everything (e.g. between two systems in one process).  The C ABI underneath has no global state at all.
-_LOCK = __import__("threading").RLock()
+_LOCK = threading.RLock()
 # .value: the total_energy call in progress in THIS thread (an object per call, restored when the call ends or raises): what per-parameter-state
 # caches of local_energy are valid for
-_CALL_TOKEN = __import__("threading").local()
+_CALL_TOKEN = threading.local()
 
 
 def _call_token():
@@ -79,10 +101,13 @@ _FRONT_DENSE: "set[tuple]" = set()   # long-row systems whose kept records outgr
 # 21.5 M of 21.5 M records are distinct and the probes cost 16x the enumeration (46.6 against 2.8 ms per launch, tools/onepass_flush_stamps.py).
 # local_energy therefore looks at the first call of a (system, batch size): when more than FRONT_NODEDUP_RATIO of the records were distinct
 # the following calls run without the table (every record its own row; E_loc is the same, the ansatz sees <= 1 / ratio as many rows).
-FRONT_NODEDUP = __import__("os").environ.get("PYNQS_FRONT_NODEDUP", "1") != "0"
+FRONT_NODEDUP = _env_flag("PYNQS_FRONT_NODEDUP", True)
 FRONT_NODEDUP_RATIO = 0.9
 _FRONT_NODEDUP: "dict[tuple, Optional[tuple]]" = {}   # key -> (cap_doubles, cap_unique) of the table-less front end, or None: keep the table
+FRONT_NODEDUP_RECHECK = 64   # routed calls after which the decision (table or no table) for a (system, batch size, eps) is measured again:
+_FRONT_NODEDUP_CALLS: dict = {}  # the first VMC iterations see the most diverse walkers; a run must not stay table-less once they concentrate
 FUSED_ONEPASS = True  # REDUCE: the one-launch front end (reduce_front.ReduceFrontEnd); False: the multi-pass compaction of round 2
+SPECULATE_RBM = _env_flag("PYNQS_SPECULATE_RBM", True)  # REDUCE with an RBM: amplitudes and contraction enqueued before the counters are read (_rbm_ahead)
 
 
 def Func(func: Callable[..., Tensor], x: Tensor, WF_LUT: Optional[WavefunctionLUT] = None, use_unique: bool = False) -> Tensor:
@@ -116,6 +141,17 @@ def _contract(f_psi: Tensor, psi_x1: Tensor, hij: Tensor) -> Tensor:
     return ((f_psi.T / psi_x1[..., 0]).T * hij).sum(-1)
 
 
+def _f_psi(psi_x1: Tensor, f: Optional[Tensor], eta_m: Optional[Tensor], psi_flip: Optional[Tensor], f_flip: Optional[Tensor], extra_norm):
+    """The numerator of the projected / multi-psi forms on (batch, n_comb) matrices, column 0 = the walker itself (flip.py:254-303):
+    (f psi + eta eta_m f(flip) psi(flip)) conj(f(x)) / N^2;  f None: no multi-psi (f = 1), eta_m None: no projection (no second term)."""
+    if eta_m is None:
+        return psi_x1 if f is None else psi_x1 * f * f[..., 0].reshape(-1, 1).conj() / extra_norm**2
+    eta = SpinProjection.eta
+    if f is None:
+        return (psi_x1 + eta * eta_m * psi_flip) / extra_norm**2
+    return (f * psi_x1 + eta * eta_m * f_flip * psi_flip) * f[..., 0].reshape(-1, 1).conj() / extra_norm**2
+
+
 def _amplitudes(comb_flat: Tensor, sel: Optional[Tensor], batch: int, n_comb: int, ansatz, ansatz_extra, WF_LUT, use_unique,
                 use_multi_psi, use_spin_flip, extra_norm, dtype, sorb, device):
     """psi (and, for the projected / multi-psi forms, f*psi) on the selected columns, scattered into
@@ -129,25 +165,44 @@ def _amplitudes(comb_flat: Tensor, sel: Optional[Tensor], batch: int, n_comb: in
         out[sel] = v.to(out.dtype)
         return out.reshape(batch, n_comb)
 
-    psi_x1 = scatter(Func(ansatz, x, WF_LUT, use_unique).to(dtype), dtype)
-    if not use_spin_flip:
-        if use_multi_psi:
-            f = scatter(Func(ansatz_extra, x, None, use_unique).to(dtype), dtype)
-            f_psi = psi_x1 * f * f[..., 0].reshape(-1, 1).conj() / extra_norm**2
-        else:
-            f_psi = psi_x1
-        return psi_x1, f_psi
-    eta = SpinProjection.eta
-    x_flip = spin_flip_onv(x, sorb)
-    eta_m = scatter(spin_flip_sign(x, sorb))
-    psi_flip = scatter(Func(ansatz, x_flip, WF_LUT, use_unique).to(dtype), dtype)
+    def on(fn, xx, lut) -> Tensor:
+        return scatter(Func(fn, xx, lut, use_unique).to(dtype), dtype)
+
+    psi_x1 = on(ansatz, x, WF_LUT)
+    eta_m = psi_flip = f = f_flip = None
+    if use_spin_flip:
+        x_flip = spin_flip_onv(x, sorb)
+        eta_m = scatter(spin_flip_sign(x, sorb))
+        psi_flip = on(ansatz, x_flip, WF_LUT)
     if use_multi_psi:
-        f = scatter(Func(ansatz_extra, x, None, use_unique).to(dtype), dtype)
-        f_flip = scatter(Func(ansatz_extra, x_flip, None, use_unique).to(dtype), dtype)
-        f_psi = (f * psi_x1 + eta * eta_m * f_flip * psi_flip) * f[..., 0].reshape(-1, 1).conj() / extra_norm**2
-    else:
-        f_psi = (psi_x1 + eta * eta_m * psi_flip) / extra_norm**2
-    return psi_x1, f_psi
+        f = on(ansatz_extra, x, None)
+        f_flip = on(ansatz_extra, x_flip, None) if use_spin_flip else None
+    return psi_x1, _f_psi(psi_x1, f, eta_m, psi_flip, f_flip, extra_norm)
+
+
+def _amplitudes_sample_space(flat: Tensor, batch: int, n_comb: int, ansatz_extra, WF_LUT, use_multi_psi, use_spin_flip, extra_norm, sorb):
+    """_amplitudes for SAMPLE_SPACE: psi only from the table (eloc.py:381-385, flip.py:375-383), f only on its hits; misses stay 0."""
+    def in_table(xx: Tensor):
+        out = torch.zeros(xx.size(0), device=xx.device, dtype=WF_LUT.dtype)
+        idx, _, value = WF_LUT.lookup(xx)
+        out[idx] = value
+        return out.reshape(batch, n_comb), idx
+
+    def f_on(xx: Tensor, hit: Tensor) -> Tensor:
+        out = torch.zeros(xx.size(0), device=xx.device, dtype=WF_LUT.dtype)
+        out[hit] = Func(ansatz_extra, xx[hit], None, True).to(out.dtype)
+        return out.reshape(batch, n_comb)
+
+    psi_x1, hit = in_table(flat)
+    eta_m = psi_flip = f = f_flip = None
+    if use_spin_flip:
+        flip = spin_flip_onv(flat, sorb)
+        eta_m = spin_flip_sign(flat, sorb).reshape(batch, n_comb)
+        psi_flip, hit_f = in_table(flip)
+    if use_multi_psi:
+        f = f_on(flat, hit)
+        f_flip = f_on(flip, hit_f) if use_spin_flip else None
+    return psi_x1, _f_psi(psi_x1, f, eta_m, psi_flip, f_flip, extra_norm)
 
 
 def _reduce_select(comb_hij: Tensor, eps: float, eps_sample: int) -> Tensor:
@@ -178,8 +233,6 @@ def _real_rbm_params(ansatz):
     """(weights [H, sorb], hidden_bias [H], visible_bias [sorb], rbm_type) if `ansatz` (possibly DDP-wrapped) is an RBM with real
     parameters and one of the fused formulas (pynqs_amd.rbm.RealRBM, or PyNQS' RBMWavefunction, rbm_type "real" / "tanh" / "pRBM",
     rbm.py:199-211), else None."""
-    from .rbm import RealRBM
-
     m = getattr(ansatz, "module", ansatz)
     kind = getattr(m, "rbm_type", None)
     if kind not in CX.RBM_FLAVOURS or not (isinstance(m, RealRBM) or hasattr(m, "effective_theta")):
@@ -196,10 +249,6 @@ def _complex_rbm_params(ansatz):
     with complex running products (pynqs_eloc_crbm): an RBM with complex parameters (pynqs_amd.rbm.ComplexRBM, or PyNQS'
     RBMWavefunction(rbm_type="complex") -- the reference's params_* layout), or rbm_type "cos" with real parameters, which is the same
     function of i W, i b up to 2^H (cos t = cosh(i t)); else None."""
-    import math
-
-    from .rbm import ComplexRBM, RealRBM
-
     m = getattr(ansatz, "module", ansatz)
     kind = getattr(m, "rbm_type", None)
     if isinstance(m, ComplexRBM) or (kind == "complex" and hasattr(m, "params_weights")):
@@ -222,7 +271,7 @@ def _rbm_lds_ok(sorb: int, nele: int, noa: int, nob: int, nhidden: int) -> bool:
     return bool(N.lib().pynqs_eloc_rbm_supported(sorb, nele, noa, nob, nhidden))
 
 
-def _fast_sample_space_ok(x, h1e, h2e, sorb, WF_LUT, use_spin_raising, use_multi_psi, use_spin_flip, noa=0, nob=0) -> bool:
+def _fast_sample_space_ok(x, h1e, sorb, WF_LUT) -> bool:
     return (FUSED and WF_LUT is not None and WF_LUT.sort
             and sorb % 2 == 0 and h1e.dtype in (torch.float64, torch.float32)
             and WF_LUT.dtype in (torch.float64, torch.complex128, torch.float32, torch.complex64)
@@ -242,16 +291,14 @@ SS_KEYS_ZONE = {1: (0.75, 64.0, 1.5), 2: (16.0, 256.0, 16.0), 3: (16.0, 256.0, 1
 # Timing both kernels costs a host synchronisation inside a VMC step and makes the choice (key-major accumulates with float atomics) depend
 # on the machine's state: OFF by default -- the fixed ratios above decide, the same on every rank and in every run.  PYNQS_SS_AUTOTUNE=1
 # (or SS_AUTOTUNE = True) turns the probe on; with several ranks rank 0 probes and everybody takes its answer.
-SS_AUTOTUNE = __import__("os").environ.get("PYNQS_SS_AUTOTUNE", "0") == "1"
+SS_AUTOTUNE = _env_flag("PYNQS_SS_AUTOTUNE", False)
 _SS_CHOICE: dict = {}
 
 
 def _key_major(nkeys: int, sorb: int, noa: int, nob: int, probe: Optional[Callable[[], bool]] = None, tag=()) -> bool:
-    import os
-
     if nkeys >= 1 << 27:
         return False
-    force = SS_KEYS if SS_KEYS is not None else {"1": True, "0": False}.get(os.environ.get("PYNQS_SS_KEYS", ""), None)
+    force = SS_KEYS if SS_KEYS is not None else _env_flag("PYNQS_SS_KEYS", None)   # (read at call time)
     if force is not None:
         return force
     ncomb = get_Num_SinglesDoubles(sorb, noa, nob) + 1
@@ -260,9 +307,7 @@ def _key_major(nkeys: int, sorb: int, noa: int, nob: int, probe: Optional[Callab
         return True
     if nkeys >= hi * ncomb:
         return False
-    from .distributed import get_world_size as _ws
-
-    if probe is None or not SS_AUTOTUNE or _ws() > 1 or (torch.cuda.is_available() and torch.cuda.is_current_stream_capturing()):
+    if probe is None or not SS_AUTOTUNE or get_world_size() > 1 or (torch.cuda.is_available() and torch.cuda.is_current_stream_capturing()):
         # (a probe synchronises: never inside a graph capture; and never with several ranks -- the ranks do not reach this point in the same
         # calls (an empty shard never calls local_energy, the per-process cache answers some ranks and not others): the fixed ratio decides,
         # the same on every rank)
@@ -271,9 +316,7 @@ def _key_major(nkeys: int, sorb: int, noa: int, nob: int, probe: Optional[Callab
     if key not in _SS_CHOICE:
         choice = bool(probe())
         _SS_CHOICE[key] = choice
-        import logging
-
-        logging.getLogger("pynqs_amd").info("SAMPLE_SPACE kernel for sorb %d, %d keys: %s (timed)", sorb, nkeys, "key-major" if choice else "column-major")
+        _LOG.info("SAMPLE_SPACE kernel for sorb %d, %d keys: %s (timed)", sorb, nkeys, "key-major" if choice else "column-major")
     return _SS_CHOICE[key]
 
 
@@ -291,13 +334,9 @@ SS_INDEX_CANDIDATE_COST = 6.0e-12  # seconds per (walker, key met through the in
 
 def _keys_index_for(WF_LUT, n: int, sorb: int):
     """The table's KeysIndex if the INDEXED form should run this call, else None (the streamed form runs and the call is counted)."""
-    import os
-
-    force = SS_INDEX if SS_INDEX is not None else {"1": True, "0": False}.get(os.environ.get("PYNQS_SS_INDEX", ""), None)
+    force = SS_INDEX if SS_INDEX is not None else _env_flag("PYNQS_SS_INDEX", None)   # (read at call time)
     if force is False or sorb % 2:
         return None
-    import weakref
-
     keys = WF_LUT.bra_key
     nk, words = keys.size(0), (sorb - 1) // 64 + 1
     cached = getattr(WF_LUT, "_keys_index", None)
@@ -328,37 +367,26 @@ def _keys_index_for(WF_LUT, n: int, sorb: int):
 
 def _launch_sample_space(key_major: bool, x, n, sorb, nele, noa, nob, plan, WF_LUT, wf, cplx, flip, eloc, psi0, part, st) -> None:
     lib = N.lib()
-    ht = getattr(WF_LUT, "hashtable", None)
-    if key_major:
-        keys = WF_LUT.bra_key
+    keys, ht = WF_LUT.bra_key, getattr(WF_LUT, "hashtable", None)
+    head = (x.data_ptr(), n, sorb, nele, noa, nob, plan.data_ptr())
+    if key_major:   # one entry point for both sums: its flag says which
         ki = _keys_index_for(WF_LUT, n, sorb)
         if ki is not None:
-            rc = lib.pynqs_eloc_sample_space_indexed(x.data_ptr(), n, sorb, nele, noa, nob, plan.data_ptr(), keys.data_ptr(), keys.size(0),
-                                                     ki.index.data_ptr(), wf.data_ptr(), int(cplx), 0, eloc.data_ptr(), psi0.data_ptr(), st)
-            if rc == 0 and flip:
-                rc = lib.pynqs_eloc_sample_space_indexed(x.data_ptr(), n, sorb, nele, noa, nob, plan.data_ptr(), keys.data_ptr(), keys.size(0),
-                                                         ki.index.data_ptr(), wf.data_ptr(), int(cplx), 1, part.data_ptr(), psi0.data_ptr(), st)
-            N.check(rc, "pynqs_eloc_sample_space_indexed")
-            return
-        rc = lib.pynqs_eloc_sample_space_keys(x.data_ptr(), n, sorb, nele, noa, nob, plan.data_ptr(), keys.data_ptr(), keys.size(0), wf.data_ptr(),
-                                              int(cplx), 0, eloc.data_ptr(), psi0.data_ptr(), st)
+            fn, name, table = lib.pynqs_eloc_sample_space_indexed, "pynqs_eloc_sample_space_indexed", (keys.data_ptr(), keys.size(0), ki.index.data_ptr())
+        else:
+            fn, name, table = lib.pynqs_eloc_sample_space_keys, "pynqs_eloc_sample_space_keys", (keys.data_ptr(), keys.size(0))
+        rc = fn(*head, *table, wf.data_ptr(), int(cplx), 0, eloc.data_ptr(), psi0.data_ptr(), st)
         if rc == 0 and flip:
-            rc = lib.pynqs_eloc_sample_space_keys(x.data_ptr(), n, sorb, nele, noa, nob, plan.data_ptr(), keys.data_ptr(), keys.size(0),
-                                                  wf.data_ptr(), int(cplx), 1, part.data_ptr(), psi0.data_ptr(), st)
-        N.check(rc, "pynqs_eloc_sample_space_keys")
+            rc = fn(*head, *table, wf.data_ptr(), int(cplx), 1, part.data_ptr(), psi0.data_ptr(), st)
+        N.check(rc, name)
         return
     if ht is not None:  # 1-2 probes per x' instead of log2(nkeys) dependent ones
-        rc = lib.pynqs_eloc_sample_space_hash(x.data_ptr(), n, sorb, nele, noa, nob, plan.data_ptr(), ht.table.data_ptr(),
-                                              ht.nkeys, wf.data_ptr(), int(cplx), eloc.data_ptr(), psi0.data_ptr(), st)
-        if rc == 0 and flip:
-            rc = lib.pynqs_eloc_sample_space_hash_flip(x.data_ptr(), n, sorb, nele, noa, nob, plan.data_ptr(), ht.table.data_ptr(),
-                                                       ht.nkeys, wf.data_ptr(), int(cplx), psi0.data_ptr(), part.data_ptr(), st)
+        fn, fn_flip, table = lib.pynqs_eloc_sample_space_hash, lib.pynqs_eloc_sample_space_hash_flip, (ht.table.data_ptr(), ht.nkeys)
     else:
-        rc = lib.pynqs_eloc_sample_space(x.data_ptr(), n, sorb, nele, noa, nob, plan.data_ptr(), WF_LUT.bra_key.data_ptr(),
-                                         WF_LUT.bra_key.size(0), wf.data_ptr(), int(cplx), eloc.data_ptr(), psi0.data_ptr(), st)
-        if rc == 0 and flip:
-            rc = lib.pynqs_eloc_sample_space_flip(x.data_ptr(), n, sorb, nele, noa, nob, plan.data_ptr(), WF_LUT.bra_key.data_ptr(),
-                                                  WF_LUT.bra_key.size(0), wf.data_ptr(), int(cplx), psi0.data_ptr(), part.data_ptr(), st)
+        fn, fn_flip, table = lib.pynqs_eloc_sample_space, lib.pynqs_eloc_sample_space_flip, (keys.data_ptr(), keys.size(0))
+    rc = fn(*head, *table, wf.data_ptr(), int(cplx), eloc.data_ptr(), psi0.data_ptr(), st)
+    if rc == 0 and flip:
+        rc = fn_flip(*head, *table, wf.data_ptr(), int(cplx), psi0.data_ptr(), part.data_ptr(), st)
     N.check(rc, "pynqs_eloc_sample_space")
 
 
@@ -385,8 +413,6 @@ def choose_sample_space_kernel(x, sorb, nele, noa, nob, plan, WF_LUT, wf, cplx) 
             t[mode] = a.elapsed_time(b)
         return t[True] <= t[False]
 
-    from .distributed import get_world_size
-
     # (the cache key must be the same on every rank: shard sizes are not)
     return _key_major(WF_LUT.bra_key.size(0), sorb, noa, nob, probe, (bool(cplx), x.size(0) >= 1024 if get_world_size() == 1 else None))
 
@@ -410,36 +436,45 @@ def _sample_space_fused(x, h1e, h2e, sorb, nele, noa, nob, WF_LUT, wf: Optional[
     return eloc, psi0, part
 
 
-def reduce_compact(x: Tensor, h1e: Tensor, h2e: Tensor, sorb: int, nele: int, noa: int, nob: int, eps: float, sort: bool = False):
-    """Kept columns of the REDUCE method, compacted on the GPU: (row int64[m], col int32[m], onv uint8[m, 8*len],
-    h[m], counts int64[n]) with |h| >= eps.  Rows ascend; inside a row the records come in the kernels' reproducible
-    tile order (sort=True: ascending columns like the reference's boolean mask, at the price of a sort)."""
-    plan = CX.plan_for(h1e, h2e, sorb, x.device)
-    dev = x.device
-    n = x.size(0)
-    L = (sorb - 1) // 64 + 1
-    code = N.PYNQS_F64 if h1e.dtype == torch.float64 else N.PYNQS_F32
-    st = torch.cuda.current_stream(dev).cuda_stream
-    T = N.lib().pynqs_reduce_tiles(n, sorb, nele, noa, nob)
-    if T < 0:
-        raise RuntimeError("pynqs_reduce_tiles: bad arguments")
-    tile_counts = torch.empty((n, T), dtype=torch.int32, device=dev)
-    N.check(N.lib().pynqs_reduce_count(x.data_ptr(), n, sorb, nele, noa, nob, plan.data_ptr(), code, float(eps), tile_counts.data_ptr(), st),
-            "pynqs_reduce_count")
+def _emit_kept(x, sorb, nele, noa, nob, plan, code, eps, tile_counts, h_dtype, st):
+    """(row, col, onv, h, counts) of the kept records from their counts per (walker, tile) -- by pynqs_reduce_count or _count_sums: prefix
+    sums, ONE read-back (the total), the emit."""
+    dev, n = x.device, x.size(0)
     ends = torch.cumsum(tile_counts.view(-1), 0, dtype=torch.int64)
     tile_off = (ends - tile_counts.view(-1)).contiguous()
     counts = tile_counts.sum(1, dtype=torch.int64)
     m = int(ends[-1].item()) if n else 0
     col = torch.empty(m, dtype=torch.int32, device=dev)
-    onv = torch.empty((m, 8 * L), dtype=torch.uint8, device=dev)
-    h = torch.empty(m, dtype=h1e.dtype, device=dev)
+    onv = torch.empty((m, 8 * ((sorb - 1) // 64 + 1)), dtype=torch.uint8, device=dev)
+    h = torch.empty(m, dtype=h_dtype, device=dev)
     row = torch.repeat_interleave(torch.arange(n, device=dev), counts)
     if m:
-        N.check(N.lib().pynqs_reduce_emit(x.data_ptr(), n, sorb, nele, noa, nob, plan.data_ptr(), code, float(eps), tile_off.data_ptr(),
+        N.check(N.lib().pynqs_reduce_emit(x.data_ptr(), n, sorb, nele, noa, nob, plan.data_ptr(), code, eps, tile_off.data_ptr(),
                                           col.data_ptr(), onv.data_ptr(), h.data_ptr(), st), "pynqs_reduce_emit")
-        if sort:
-            order = torch.argsort((row << 32) | col.long())
-            col, onv, h = col[order], onv[order], h[order]
+    return row, col, onv, h, counts
+
+
+def _compact_setup(x, h1e, h2e, sorb, nele, noa, nob):
+    """What both multi-pass compactions start from: (plan, code of the integrals' type, stream, counts per (walker, tile) to be filled)."""
+    plan = CX.plan_for(h1e, h2e, sorb, x.device)
+    T = N.lib().pynqs_reduce_tiles(x.size(0), sorb, nele, noa, nob)
+    if T < 0:
+        raise RuntimeError("pynqs_reduce_tiles: bad arguments")
+    code = N.PYNQS_F64 if h1e.dtype == torch.float64 else N.PYNQS_F32
+    return plan, code, torch.cuda.current_stream(x.device).cuda_stream, torch.empty((x.size(0), T), dtype=torch.int32, device=x.device)
+
+
+def reduce_compact(x: Tensor, h1e: Tensor, h2e: Tensor, sorb: int, nele: int, noa: int, nob: int, eps: float, sort: bool = False):
+    """Kept columns of the REDUCE method, compacted on the GPU: (row int64[m], col int32[m], onv uint8[m, 8*len],
+    h[m], counts int64[n]) with |h| >= eps.  Rows ascend; inside a row the records come in the kernels' reproducible
+    tile order (sort=True: ascending columns like the reference's boolean mask, at the price of a sort)."""
+    plan, code, st, tile_counts = _compact_setup(x, h1e, h2e, sorb, nele, noa, nob)
+    N.check(N.lib().pynqs_reduce_count(x.data_ptr(), x.size(0), sorb, nele, noa, nob, plan.data_ptr(), code, float(eps), tile_counts.data_ptr(), st),
+            "pynqs_reduce_count")
+    row, col, onv, h, counts = _emit_kept(x, sorb, nele, noa, nob, plan, code, float(eps), tile_counts, h1e.dtype, st)
+    if sort and col.numel():
+        order = torch.argsort((row << 32) | col.long())
+        col, onv, h = col[order], onv[order], h[order]
     return row, col, onv, h, counts
 
 
@@ -451,33 +486,13 @@ def reduce_compact_sampled(x: Tensor, h1e: Tensor, h2e: Tensor, sorb: int, nele:
     drawn column and w = (hits / eps_sample) * sign(h) * S_row, S_row = sum of the sub-eps |h| of the row.
     The draws over the tiles of a row come from torch.multinomial, the ones inside a tile from a counter-based
     generator in the kernel seeded with `seed` (default: drawn from torch's generator)."""
-    plan = CX.plan_for(h1e, h2e, sorb, x.device)
-    dev = x.device
-    n = x.size(0)
-    L = (sorb - 1) // 64 + 1
-    code = N.PYNQS_F64 if h1e.dtype == torch.float64 else N.PYNQS_F32
-    st = torch.cuda.current_stream(dev).cuda_stream
-    lib = N.lib()
-    T = lib.pynqs_reduce_tiles(n, sorb, nele, noa, nob)
-    if T < 0:
-        raise RuntimeError("pynqs_reduce_tiles: bad arguments")
+    plan, code, st, tile_counts = _compact_setup(x, h1e, h2e, sorb, nele, noa, nob)
+    dev, lib, (n, T), L = x.device, N.lib(), tile_counts.shape, (sorb - 1) // 64 + 1
     eps_eff = float(eps) if eps > 0.0 else float("inf")
-    tile_counts = torch.empty((n, T), dtype=torch.int32, device=dev)
     tile_sums = torch.empty((n, T), dtype=torch.float64, device=dev)
     N.check(lib.pynqs_reduce_count_sums(x.data_ptr(), n, sorb, nele, noa, nob, plan.data_ptr(), code, eps_eff, tile_counts.data_ptr(),
                                         tile_sums.data_ptr(), st), "pynqs_reduce_count_sums")
-    # kept part (same records as reduce_compact)
-    ends = torch.cumsum(tile_counts.view(-1), 0, dtype=torch.int64)
-    counts = tile_counts.sum(1, dtype=torch.int64)
-    m = int(ends[-1].item()) if n else 0
-    col = torch.empty(m, dtype=torch.int32, device=dev)
-    onv = torch.empty((m, 8 * L), dtype=torch.uint8, device=dev)
-    h = torch.empty(m, dtype=h1e.dtype, device=dev)
-    row = torch.repeat_interleave(torch.arange(n, device=dev), counts)
-    if m:
-        tile_off = (ends - tile_counts.view(-1)).contiguous()
-        N.check(lib.pynqs_reduce_emit(x.data_ptr(), n, sorb, nele, noa, nob, plan.data_ptr(), code, eps_eff, tile_off.data_ptr(),
-                                      col.data_ptr(), onv.data_ptr(), h.data_ptr(), st), "pynqs_reduce_emit")
+    kept = _emit_kept(x, sorb, nele, noa, nob, plan, code, eps_eff, tile_counts, h1e.dtype, st)   # (same records as reduce_compact)
     # draws over the tiles, then inside the tiles
     S = tile_sums.sum(1)
     live = S > 0
@@ -494,8 +509,6 @@ def reduce_compact_sampled(x: Tensor, h1e: Tensor, h2e: Tensor, sorb: int, nele:
     s_h = torch.empty(total, dtype=h1e.dtype, device=dev)
     scale = (S / eps_sample).contiguous()
     if seed is None:
-        # from torch's host generator (reproducible after torch.manual_seed), decorrelated between the ranks: after the usual
-        # manual_seed(seed) every rank's generator is in the same state, and the kernel's stream is keyed by (seed, local walker, tile, k)
         seed = _draw_seed()
     N.check(lib.pynqs_reduce_sample(x.data_ptr(), n, sorb, nele, noa, nob, plan.data_ptr(), code, eps_eff, tile_draws.data_ptr(),
                                     sample_off.data_ptr(), scale.data_ptr(), seed, s_col.data_ptr(), s_onv.data_ptr(), s_h.data_ptr(), st),
@@ -508,9 +521,9 @@ def reduce_compact_sampled(x: Tensor, h1e: Tensor, h2e: Tensor, sorb: int, nele:
     keep = torch.nonzero(valid).squeeze(1)  # one compaction for the four arrays
     s_row = slot_row[keep]
     # records per walker: a segmented sum over its slot range (scatter_add_ here: 0.6 ms of atomics on 5 M rows)
-    s_counts = torch.segment_reduce(valid.to(torch.float64), "sum", lengths=draws_per_row, unsafe=True).to(torch.int64) if used else \
+    s_counts = _segment_sum(valid.to(torch.float64), draws_per_row).to(torch.int64) if used else \
         torch.zeros(n, dtype=torch.int64, device=dev)
-    return (row, col, onv, h, counts), (s_row, s_col[keep], s_onv[keep], s_h[keep], s_counts)
+    return kept, (s_row, s_col[keep], s_onv[keep], s_h[keep], s_counts)
 
 # ---- REDUCE through the one-launch front end ---------------------------------------------------------------------------------
 _FRONTS: "dict[tuple, RF.ReduceFrontEnd]" = {}
@@ -548,10 +561,6 @@ def _nodedup_key(device, n, sorb, nele, noa, nob, eps_sample, eps=None) -> tuple
     return (str(device), int(n), sorb, nele, noa, nob, int(eps_sample), None if eps is None else float(eps))
 
 
-FRONT_NODEDUP_RECHECK = 64   # routed calls after which the decision (table or no table) for a (system, batch size, eps) is measured again:
-_FRONT_NODEDUP_CALLS: dict = {}  # the first VMC iterations see the most diverse walkers; a run must not stay table-less once they concentrate
-
-
 def _new_front(n, x, h1e, sorb, nele, noa, nob, eps_sample, pm1_dtype, want_pm1, cap_d=None, cap_u=None, dedup=True):
     if not dedup and cap_d is not None and cap_d > RF.list_capacity(n, sorb, nele, noa, nob, int(eps_sample), h1e.dtype, without_table=True):
         dedup = True   # (only the LIST forms of the kernel run without the table)
@@ -564,6 +573,27 @@ def _new_front(n, x, h1e, sorb, nele, noa, nob, eps_sample, pm1_dtype, want_pm1,
         if limit is not None and limit >= 0:
             cap_d = min(cap_d, limit)   # (long rows: start in the LIST form; reduce_front_finish leaves the path if that overflows)
     return RF.ReduceFrontEnd(n, sorb, nele, noa, nob, eps_sample, h1e.dtype, x.device, cap_d, cap_u, pm1_dtype, want_pm1=want_pm1, dedup=dedup)
+
+
+@dataclass(slots=True)
+class _FrontTicket:
+    """one enqueued front-end launch (reduce_front_launch), for reduce_front_finish: the workspace and its cache key, the counters' pinned
+    host copy and the event behind it, and the call's arguments (an overflow repeats the call)"""
+    fe: RF.ReduceFrontEnd
+    key: tuple
+    host: Tensor
+    ev: torch.cuda.Event
+    x: Tensor
+    plan: object
+    h1e: Tensor
+    system: tuple   # (sorb, nele, noa, nob)
+    eps: float
+    eps_sample: int
+    seed: int
+    lut: object
+    pm1_dtype: torch.dtype
+    want_pm1: bool
+    route: bool
 
 
 def reduce_front_launch(x: Tensor, h1e: Tensor, h2e: Tensor, sorb: int, nele: int, noa: int, nob: int, eps: float, eps_sample: int = 0,
@@ -597,8 +627,7 @@ def reduce_front_launch(x: Tensor, h1e: Tensor, h2e: Tensor, sorb: int, nele: in
         # when the decision is measured again: that call must run WITH the table, else reduce_front_finish has nothing to count)
         fe = None
     if fe is None:
-        fe = _new_front(n, x, h1e, sorb, nele, noa, nob, eps_sample, pm1_dtype, want_pm1) if caps is None else \
-            _new_front(n, x, h1e, sorb, nele, noa, nob, eps_sample, pm1_dtype, want_pm1, caps[0], caps[1], dedup=False)
+        fe = _new_front(n, x, h1e, sorb, nele, noa, nob, eps_sample, pm1_dtype, want_pm1, *(caps or (None, None)), dedup=caps is None)
     if seed is None:
         seed = _draw_seed() if eps_sample > 0 else 0
     if consumer is not None:
@@ -608,47 +637,45 @@ def reduce_front_launch(x: Tensor, h1e: Tensor, h2e: Tensor, sorb: int, nele: in
     host.copy_(fe.counters, non_blocking=True)
     ev = torch.cuda.Event()
     ev.record(torch.cuda.current_stream(x.device))
-    return dict(fe=fe, key=key, host=host, ev=ev, x=x, plan=plan, eps=eps, seed=seed, lut=lut, route=route, args=(h1e, sorb, nele, noa, nob, eps_sample, pm1_dtype, want_pm1))
+    return _FrontTicket(fe=fe, key=key, host=host, ev=ev, x=x, plan=plan, h1e=h1e, system=(sorb, nele, noa, nob), eps=eps, eps_sample=eps_sample,
+                        seed=seed, lut=lut, pm1_dtype=pm1_dtype, want_pm1=want_pm1, route=route)
 
 
-def reduce_front_finish(t):
+def reduce_front_finish(t: _FrontTicket):
     """(front end, number of distinct x') of a ticket: waits for THAT launch only (its event), grows the buffers and repeats the call on
     the current stream if it reported an overflow."""
-    t["ev"].synchronize()
-    fe, x = t["fe"], t["x"]
-    cnt = tuple(int(v) for v in t["host"].tolist()[:3])
-    h1e, sorb, nele, noa, nob, eps_sample, pm1_dtype, want_pm1 = t["args"]
+    t.ev.synchronize()
+    fe, x, n, system = t.fe, t.x, t.x.size(0), t.system
+    cnt = tuple(int(v) for v in t.host.tolist()[:3])
     while fe.overflowed(cnt):
         nu, flags, mx = cnt
         cap_d = max(fe.cap_doubles, int(mx * 1.25) + 16) if mx > fe.cap_doubles else fe.cap_doubles
         cap_u = fe.cap_unique
-        limit = _long_row_cap(x.size(0), h1e, sorb, nele, noa, nob, eps_sample) if t["route"] else None
+        limit = _long_row_cap(n, t.h1e, *system, t.eps_sample) if t.route else None
         if limit is not None and cap_d > limit:
-            _FRONT_DENSE.add(_dense_key(x.device, sorb, nele, noa, nob, eps_sample))
+            _FRONT_DENSE.add(_dense_key(x.device, *system, t.eps_sample))
             raise _FrontDense()
         if flags & RF.OVERFLOW_TABLE:
             cap_u = max(4 * cap_u, int(nu * 1.5))   # (the kernel stops inserting once the table is full: nu is a lower bound then)
         elif nu > cap_u:
             cap_u = int(nu * 1.25) + 1024
-        fe = _new_front(x.size(0), x, h1e, sorb, nele, noa, nob, eps_sample, pm1_dtype, want_pm1, cap_d, cap_u, dedup=fe.dedup)
-        fe.run(x, t["plan"].buf, t["eps"], t["seed"], t["lut"])
+        fe = _new_front(n, x, t.h1e, *system, t.eps_sample, t.pm1_dtype, t.want_pm1, cap_d, cap_u, dedup=fe.dedup)
+        fe.run(x, t.plan.buf, t.eps, t.seed, t.lut)
         cnt = fe.counters_host()
-    nk = _nodedup_key(x.device, x.size(0), sorb, nele, noa, nob, eps_sample, t["eps"])
-    if t["route"] and FRONT_NODEDUP and fe.dedup and nk not in _FRONT_NODEDUP:
+    nk = _nodedup_key(x.device, n, *system, t.eps_sample, t.eps)
+    if t.route and FRONT_NODEDUP and fe.dedup and nk not in _FRONT_NODEDUP:
         # the first call for this system and batch size: how many of the records were distinct?  (one more read-back, once)
         records = fe.count_records()
-        list_ok = fe.cap_doubles <= RF.list_capacity(x.size(0), sorb, nele, noa, nob, int(eps_sample), h1e.dtype, without_table=True)
-        import logging
-
-        drop = bool(list_ok and t["lut"] is None and cnt[0] > FRONT_NODEDUP_RATIO * records)
-        logging.getLogger("pynqs_amd").info("REDUCE front end, sorb %d, %d walkers, eps %g: %d of %d records distinct -> %s", sorb, x.size(0), t["eps"], cnt[0],
-                                            records, "no de-duplication table from now on" if drop else "de-duplication table kept")
+        list_ok = fe.cap_doubles <= RF.list_capacity(n, *system, int(t.eps_sample), t.h1e.dtype, without_table=True)
+        drop = bool(list_ok and t.lut is None and cnt[0] > FRONT_NODEDUP_RATIO * records)
+        _LOG.info("REDUCE front end, sorb %d, %d walkers, eps %g: %d of %d records distinct -> %s", system[0], n, t.eps, cnt[0], records,
+                  "no de-duplication table from now on" if drop else "de-duplication table kept")
         if drop:
             _FRONT_NODEDUP[nk] = (fe.cap_doubles, int(records * 1.05) + 4096)
             return fe, cnt[0]   # (not kept: the next call builds the table-less front end)
         _FRONT_NODEDUP[nk] = None
     with _LOCK:
-        _FRONTS[t["key"]] = fe  # (most recently used last)
+        _FRONTS[t.key] = fe  # (most recently used last)
         while len(_FRONTS) > _MAX_FRONTS:
             _FRONTS.pop(next(iter(_FRONTS)))
     return fe, cnt[0]
@@ -669,41 +696,40 @@ def reduce_front(x: Tensor, h1e: Tensor, h2e: Tensor, sorb: int, nele: int, noa:
     return reduce_front_finish(reduce_front_launch(x, h1e, h2e, sorb, nele, noa, nob, eps, eps_sample, lut, seed, pm1_dtype, want_pm1, route=route))
 
 
+def _rbm_forward_params(ansatz, dtype):
+    """(weights, hidden bias, visible bias, kind) if the forward kernels (pynqs_rbm_forward[_children]) give this ansatz' amplitudes in
+    `dtype`: a real RBM whose flavour matches dtype (pRBM is complex-valued, the others real), else an RBM with complex parameters -- not
+    "cos" -- with a complex dtype; else None.  THE place that decides it: once per local_energy call / per look-ahead of total_energy."""
+    rp = _real_rbm_params(ansatz)
+    if rp is not None and dtype.is_complex == (rp[3] == "pRBM"):
+        return rp
+    cp = _complex_rbm_params(ansatz) if rp is None and dtype.is_complex else None
+    return None if cp is None or cp[4] else (cp[0], cp[1], cp[2], "complex")
+
+
 def _reduce_front_options(ansatz, WF_LUT, dtype, use_multi_psi, use_spin_flip):
-    """(wave-function hash table asked inside the kernel or None, amplitudes of the distinct x' by pynqs_rbm_forward?) for local_energy's
-    REDUCE path -- one definition for local_energy and for total_energy's look-ahead."""
+    """(wave-function hash table asked inside the kernel or None, _rbm_forward_params if the amplitudes of the distinct x' come from
+    pynqs_rbm_forward, else None) for local_energy's REDUCE path -- one definition for local_energy and for total_energy's look-ahead."""
     plain = not (use_multi_psi or use_spin_flip)
     # the table is asked inside the kernel when it has a GPU hash table and psi is all that is needed on x' (f of the multi-psi
     # form has no table; the projected forms look flip(x') up as well): otherwise on the distinct rows
     ht = getattr(WF_LUT, "hashtable", None) if (WF_LUT is not None and plain) else None
     # an RBM of the reference's family gets its amplitudes on the distinct x' from the packed bits (pynqs_rbm_forward): no +-1 rows
-    rp, cp = _real_rbm_params(ansatz), None
-    if rp is None:
-        cp = _complex_rbm_params(ansatz)
-    rbm_fwd = bool(FUSED_RBM and not use_multi_psi and not (WF_LUT is not None and ht is None) and (
-        (rp is not None and dtype.is_complex == (rp[3] == "pRBM")) or (cp is not None and not cp[4] and dtype.is_complex)))
-    return ht, rbm_fwd
+    if not FUSED_RBM or use_multi_psi or (WF_LUT is not None and ht is None):
+        return ht, None
+    return ht, _rbm_forward_params(ansatz, dtype)
 
 
-SPECULATE_RBM = os.environ.get("PYNQS_SPECULATE_RBM", "1") != "0"
-
-
-def _rbm_ahead(ticket, x, ansatz, lut, dtype, sorb, other_stream: bool):
+def _rbm_ahead(ticket, x, rbm, lut, dtype, sorb, other_stream: bool):
     """(front end, eloc, psi(x)) with the RBM amplitudes of the distinct x' (from their parent walkers, device-side row count) and the
-    contraction enqueued behind the front end of `ticket` without waiting for its counters; None when the ansatz / the sizes do not allow it."""
-    fe = ticket["fe"]
-    prm = _real_rbm_params(ansatz)
-    if prm is not None and (dtype.is_complex == (prm[3] == "pRBM")):
-        W, hb, vb, kind = prm[0], prm[1], prm[2], prm[3]
-    else:
-        cprm = _complex_rbm_params(ansatz)
-        if cprm is None or cprm[4] or not dtype.is_complex:
-            return None
-        W, hb, vb, kind = cprm[0], cprm[1], cprm[2], "complex"
+    contraction enqueued behind the front end of `ticket` without waiting for its counters; None when the sizes do not allow it.
+    rbm: _rbm_forward_params of the ansatz."""
+    fe = ticket.fe
+    W, hb, vb, kind = rbm
     if not (RBM_FROM_PARENTS and CX.rbm_forward_children_supported(sorb, W.size(0), kind)):
         return None
     if other_stream:   # (total_energy's look-ahead enqueued the front end on its second stream)
-        torch.cuda.current_stream(x.device).wait_event(ticket["ev"])
+        torch.cuda.current_stream(x.device).wait_event(ticket.ev)
     psi_u = CX.rbm_forward_children(fe.uniq_onv, fe.uniq_parent, x, W, hb, vb, sorb, kind, count=fe.counters).to(dtype)
     eloc, psi_x = fe.contract(psi_u, lut.wf_value if lut is not None else None)
     return fe, eloc, psi_x
@@ -721,6 +747,255 @@ def _front_ok(x, h1e, sorb, nele, noa, nob, eps_sample) -> bool:
     return limit >= 0 and _dense_key(x.device, sorb, nele, noa, nob, eps_sample) not in _FRONT_DENSE
 
 
+def _segment_sum(values: Tensor, lengths: Tensor) -> Tensor:
+    """sums over consecutive segments of `values` (a walker's records are contiguous): a segmented sum instead of index_add_ (atomics: 2.7 of
+    5.0 ms on Fe2S2); complex values through their (re, im) view"""
+    if values.is_complex():
+        return torch.view_as_complex(torch.segment_reduce(torch.view_as_real(values).contiguous(), "sum", lengths=lengths, unsafe=True))
+    return torch.segment_reduce(values, "sum", lengths=lengths, unsafe=True)
+
+
+def _projected_t(c, onv: Tensor, psi: Tensor, f: Optional[Tensor]) -> Tensor:
+    """The projected / multi-psi factor on records or distinct rows `onv` (flip.py:153-319):
+        T = f psi + eta eta_m(x') f(flip x') psi(flip x')        (f = 1 without multi-psi, no second term without the projection)
+    from psi (and f, multi-psi) on them.  The callers apply conj(f(x)) / N^2: per walker after the front end's contraction, per record on
+    the multi-pass path -- two orders of the same product, which this function leaves to them."""
+    t = f * psi if c.use_multi_psi else psi
+    if c.use_spin_flip:
+        onv_flip = spin_flip_onv(onv, c.sorb)
+        psi_flip = Func(c.ansatz_f, onv_flip, c.WF_LUT, c.use_unique).to(c.dtype)
+        if c.use_multi_psi:
+            psi_flip = Func(c.ansatz_extra, onv_flip, None, c.use_unique).to(c.dtype) * psi_flip
+        t = t + SpinProjection.eta * spin_flip_sign(onv, c.sorb) * psi_flip
+    return t
+
+
+def _f_on_keys(c) -> Tensor:
+    """f on the sample-space keys (the reference stores f in the table's dtype, flip.py:392): once per parameter state, not once
+    per chunk of walkers -- total_energy calls local_energy for every chunk, and the table has up to 1e5-1e6 keys"""
+    WF_LUT, extra = c.WF_LUT, c.ansatz.module.extra
+    # valid within ONE total_energy call (its token): parameters updated through `p.data.add_` -- the reference's own GD step,
+    # vmc/optim/_base.py:619 -- keep their version counters, so nothing across calls proves that f is still current
+    stamp = (id(extra), WF_LUT.bra_key.data_ptr(), WF_LUT.bra_key.size(0), str(WF_LUT.dtype), _call_token())
+    cached = getattr(WF_LUT, "_pynqs_f_keys", None)
+    if cached is not None and cached[0] == stamp and stamp[4] is not None:
+        return cached[1]
+    f_keys = Func(partial(c.ansatz_batch, func=extra), WF_LUT.bra_key, None, True).to(WF_LUT.dtype)
+    try:
+        WF_LUT._pynqs_f_keys = (stamp, f_keys)
+    except AttributeError:  # (a table object that takes no attributes)
+        pass
+    return f_keys
+
+
+def _in_sample_space(c, h1, h2, f_keys):
+    """(sum over the sample space with the integrals (h1, h2), psi(x)): the energy, and with the S-S+ integrals <S-S+> (eloc.py:377-400)"""
+    x, WF_LUT = c.x, c.WF_LUT
+    if not (c.use_multi_psi or c.use_spin_flip):
+        e1, p0, _ = _sample_space_fused(x, h1, h2, *c.system, WF_LUT)
+        return e1, p0
+    # projected / multi-psi forms (flip.py:322-418, eloc.py:381-392) on the same kernel:
+    #   E_loc = conj(f(x)) [ sum_k H_k (f psi)(x'_k) + eta sum_k H_k eta_m(x'_k) (f psi)(flip x'_k) ] / (N^2 psi(x))
+    # (f psi) is a table over the sample space
+    wf = WF_LUT.wf_value * f_keys if c.use_multi_psi else WF_LUT.wf_value
+    e1, p0, part = _sample_space_fused(x, h1, h2, *c.system, WF_LUT, wf, c.use_spin_flip)
+    if c.use_spin_flip:
+        e1 = e1 + SpinProjection.eta * part
+    if c.use_multi_psi:
+        # t(x) = f(x) psi(x): back to sum / psi(x) and the reference's factor conj(f(x)); psi(x), f(x) from the table
+        # (pynqs_amd's table answers through its hash table; the reference's own WavefunctionLUT class has no `find`)
+        pos, found = WF_LUT.find(x) if hasattr(WF_LUT, "find") else CX.wavefunction_lut(WF_LUT.bra_key, x, c.sorb)
+        pos = pos.clamp_min(0)
+        p0 = torch.where(found, WF_LUT.wf_value[pos], torch.zeros((), dtype=WF_LUT.dtype, device=x.device))
+        f_x = torch.where(found, f_keys[pos], torch.zeros((), dtype=f_keys.dtype, device=x.device))
+        e1 = e1 * f_x * f_x.conj()
+    return e1 / c.extra_norm**2, p0
+
+
+def _eloc_sample_space_fused(c):
+    """SAMPLE_SPACE in one kernel per sum (every form)."""
+    f_keys = _f_on_keys(c) if c.use_multi_psi else None
+    eloc, psi0 = _in_sample_space(c, c.h1e, c.h2e, f_keys)
+    sloc = _in_sample_space(c, c.h1e_spin, c.h2e_spin, f_keys)[0] if c.use_spin_raising else torch.zeros_like(eloc)
+    t1 = time.time_ns()
+    return eloc.to(c.dtype), sloc.to(c.dtype), psi0.to(c.dtype), ((t1 - c.t0) / 1e6, 0.0, 0.0)
+
+
+def _eloc_simple_rbm(c):
+    """SIMPLE with an RBM: amplitude ratios on chip.  None: not such an RBM / `dtype` is not its own / its parameters do not fit the LDS."""
+    x, dtype, system = c.x, c.dtype, c.system
+    prm = _real_rbm_params(c.ansatz)
+    cprm = _complex_rbm_params(c.ansatz) if prm is None else None
+    # the phase flavour (pRBM) is complex-valued; the others need a real `dtype` like the module itself
+    if (prm is not None and dtype in ((torch.complex128, torch.complex64) if prm[3] == "pRBM" else (torch.double, torch.float32))
+            and _rbm_lds_ok(*system, prm[0].size(0))):
+        table, run, psi_kw = CX.RBMTable(*prm[:3]), partial(CX.eloc_rbm, rbm_type=prm[3]), {}
+    # complex parameters (complex running products in the kernel); "cos" is real-valued and rides on the same kernel
+    elif (cprm is not None and dtype in ((torch.double, torch.float32) if cprm[4] else (torch.complex128, torch.complex64))
+            and N.lib().pynqs_eloc_crbm_supported(*system, cprm[0].size(0))):
+        table, run, psi_kw = CX.CRBMTable(*cprm[:3]), CX.eloc_crbm, dict(log_scale=cprm[3])
+    else:
+        return None
+    eloc, psi0 = run(x, *CX.integrals_f64(c.h1e, c.h2e), table, *system, **psi_kw)
+    # <S-S+> (eloc.py:173-188): the same kernel with the S-S+ integrals
+    sloc = run(x, *CX.integrals_f64(c.h1e_spin, c.h2e_spin), table, *system, want_psi=False)[0] if c.use_spin_raising else torch.zeros_like(eloc)
+    if cprm is not None and cprm[4]:
+        eloc, sloc, psi0 = eloc.real, sloc.real, psi0.real
+    t1 = time.time_ns()
+    return eloc.to(dtype), sloc.to(dtype), psi0.to(dtype), ((t1 - c.t0) / 1e6, 0.0, 0.0)
+
+
+def _on_distinct(c, fe, nu, fn, lut) -> Tensor:
+    """a function of the determinant on the distinct x' (the +-1 rows the kernel wrote are the module's input already)"""
+    if lut is not None:
+        return Func(fn, fe.uniq_onv[:nu], lut, False).to(c.dtype)
+    takes_rows = fe.uniq_pm1 is not None and getattr(c.ansatz_batch, "accepts_pm1_rows", False) and fe.pm1_dtype == torch.get_default_dtype()
+    return fn(fe.uniq_pm1[:nu] if takes_rows else fe.uniq_onv[:nu]).to(c.dtype)
+
+
+def _rbm_on_distinct(c, fe, nu, rbm) -> Tensor:
+    """psi on the distinct x' by one kernel (rbm: _rbm_forward_params).  Every distinct x' is its parent walker with <= 4 orbitals flipped
+    (the front end notes the parent): theta(x') from theta(x) by 4 updates per hidden unit when the parameters fit the LDS, else from scratch"""
+    W, hb, vb, kind = rbm
+    if RBM_FROM_PARENTS and CX.rbm_forward_children_supported(c.sorb, W.size(0), kind):
+        return CX.rbm_forward_children(fe.uniq_onv[:nu], fe.uniq_parent, c.x, W, hb, vb, c.sorb, kind).to(c.dtype)
+    return CX.rbm_forward(fe.uniq_onv[:nu], W, hb, vb, c.sorb, kind).to(c.dtype)
+
+
+def _front_spin_raising(c, fe, amp_u, tab, num_over_psi) -> Tensor:
+    """<S-S+> over the front end's records (eloc.py:250-310: the raw S-S+ matrix elements, also on the drawn columns); amp_u: psi (plain
+    form, num_over_psi None) or T on the distinct x'"""
+    x = c.x
+    xs = x if fe.nchunks == 1 else x.repeat_interleave(fe.nchunks, 0)
+    hs = get_hij_torch(xs, fe.rec_onv.view(fe.nseg, fe.stride, -1), c.h1e_spin, c.h2e_spin, c.sorb, c.nele).reshape(-1).to(fe.h_dtype)
+    hs_s = get_hij_torch(x, fe.srec_onv.view(x.size(0), fe.eps_sample, -1), c.h1e_spin, c.h2e_spin, c.sorb, c.nele).reshape(-1).to(fe.h_dtype) \
+        if fe.eps_sample else None
+    if num_over_psi is None:
+        return fe.contract(amp_u, tab, rec_w=hs, srec_w=hs_s)[0]
+    return fe.contract(amp_u, None, divide=False, rec_w=hs, srec_w=hs_s)[0] * num_over_psi
+
+
+def _eloc_reduce_front(c):
+    """REDUCE through the one-launch front end (deterministic and semi-stochastic, every form).  None: a long row kept more records than
+    the front end's LDS list holds (_FrontDense) -- the multi-pass paths serve the system, from now on."""
+    dtype = c.dtype
+    ht, rbm = _reduce_front_options(c.ansatz, c.WF_LUT, dtype, c.use_multi_psi, c.use_spin_flip)
+    plain = not (c.use_multi_psi or c.use_spin_flip)
+    ahead = None
+    try:
+        ticket = c.front_ticket
+        if ticket is None:
+            ticket = reduce_front_launch(c.x, c.h1e, c.h2e, *c.system, c.eps, int(c.eps_sample), ht, want_pm1=rbm is None, route=True)
+        if rbm is not None and SPECULATE_RBM and plain and not c.use_spin_raising:
+            # An RBM of the reference's family needs nothing from the host between the front end and the contraction: the amplitude
+            # kernel takes the number of distinct x' from the device, so both are enqueued BEFORE the counters are waited for (the wait
+            # + two launches used to leave the GPU idle for ~0.2 ms of a 1 ms call).  Used if the counters then report no overflow.
+            ahead = _rbm_ahead(ticket, c.x, rbm, c.WF_LUT if ht is not None else None, dtype, c.sorb, c.front_ticket is not None)
+        fe, nu = reduce_front_finish(ticket)
+    except _FrontDense:
+        return None
+    t2 = time.time_ns()
+    if ahead is not None and ahead[0] is fe:
+        eloc, psi_x = ahead[1], ahead[2]
+        return eloc.to(dtype), torch.zeros_like(eloc).to(dtype), psi_x.to(dtype), ((t2 - c.t0) / 1e6, 0.0, 0.0)
+    psi_u = _rbm_on_distinct(c, fe, nu, rbm) if rbm is not None else _on_distinct(c, fe, nu, c.ansatz_f, c.WF_LUT if ht is None else None)
+    tab = c.WF_LUT.wf_value if ht is not None else None
+    if plain:
+        amp_u, num_over_psi = psi_u, None
+        eloc, psi_x = fe.contract(psi_u, tab)
+    else:
+        # projected / multi-psi forms: E_loc = conj(f(x)) sum_k w_k T(x'_k) / (N^2 psi(x)), T per distinct x'
+        f_u = _on_distinct(c, fe, nu, c.ansatz_extra, None) if c.use_multi_psi else None
+        amp_u = _projected_t(c, fe.uniq_onv[:nu], psi_u, f_u)
+        num, _ = fe.contract(amp_u, None, divide=False)
+        _, psi_x = fe.contract(psi_u, None, divide=False)
+        scale = 1.0 / c.extra_norm**2
+        if c.use_multi_psi:
+            scale = scale * fe.contract(f_u, None, divide=False)[1].conj()
+        num_over_psi = scale / psi_x
+        eloc = num * num_over_psi
+    sloc = _front_spin_raising(c, fe, amp_u, tab, num_over_psi) if c.use_spin_raising else torch.zeros_like(eloc)
+    t3 = time.time_ns()
+    return eloc.to(dtype), sloc.to(dtype), psi_x.to(dtype), ((t2 - c.t0) / 1e6, 0.0, (t3 - t2) / 1e6)
+
+
+def _eloc_reduce_multipass(c):
+    """REDUCE (deterministic) with on-chip compaction in several passes: rows too long for the one-launch front end.  Also the spin-flip
+    projected and multi-psi forms (flip.py:200-319): their extra factors are evaluated on the kept records only."""
+    x, dtype = c.x, c.dtype
+    row, col, onv, h, counts = reduce_compact(x, c.h1e, c.h2e, *c.system, c.eps)
+    t2 = time.time_ns()
+    first = col == 0
+
+    def at_x(v: Tensor) -> Tensor:
+        """value on the kept column 0 of each row; 0 if it was filtered out (as in the reference)"""
+        out = torch.zeros(x.size(0), dtype=dtype, device=x.device)
+        out[row[first]] = v[first]
+        return out
+
+    psi = Func(c.ansatz_f, onv, c.WF_LUT, c.use_unique).to(dtype)
+    psi_x = at_x(psi)
+    f = Func(c.ansatz_extra, onv, None, c.use_unique).to(dtype) if c.use_multi_psi else None
+    t = _projected_t(c, onv, psi, f)
+    if c.use_multi_psi:
+        t = t * at_x(f).conj()[row]
+    if c.use_multi_psi or c.use_spin_flip:
+        t = t / c.extra_norm**2
+    ratio = t / psi_x[row]
+    eloc = _segment_sum(ratio * h.to(_real_dtype(dtype)), counts)
+    if c.use_spin_raising:
+        # <S-S+> over the same kept columns (eloc.py:250-310): its matrix elements for the (x, x') pairs of the records
+        h_spin = get_hij_torch(x[row].contiguous(), onv.unsqueeze(1), c.h1e_spin, c.h2e_spin, c.sorb, c.nele).reshape(-1)
+        sloc = _segment_sum(ratio * h_spin.to(_real_dtype(dtype)), counts)
+    else:
+        sloc = torch.zeros_like(eloc)
+    t3 = time.time_ns()
+    return eloc.to(dtype), sloc.to(dtype), psi_x, ((t2 - c.t0) / 1e6, 0.0, (t3 - t2) / 1e6)
+
+
+def _eloc_reduce_multipass_sampled(c):
+    """Semi-stochastic REDUCE (eps_sample > 0) with the selection done on chip, in several passes (plain form only)."""
+    x, dtype = c.x, c.dtype
+    (row, col, onv, h, counts), (s_row, s_col, s_onv, s_w, s_counts) = reduce_compact_sampled(x, c.h1e, c.h2e, *c.system, c.eps, int(c.eps_sample))
+    t2 = time.time_ns()
+    psi_all = Func(c.ansatz_f, torch.cat([onv, s_onv]), c.WF_LUT, c.use_unique).to(dtype)
+    psi, psi_s = psi_all[: onv.size(0)], psi_all[onv.size(0):]
+    # psi(x): column 0 among the kept records (every row keeps it unless |H_00| < eps, where the reference divides by 0 too),
+    # else among the drawn ones
+    psi_x = torch.zeros(x.size(0), dtype=dtype, device=x.device)
+    first_s = s_col == 0
+    psi_x[s_row[first_s]] = psi_s[first_s]
+    first = col == 0
+    psi_x[row[first]] = psi[first]
+    rdt = _real_dtype(dtype)
+    eloc = _segment_sum((psi / psi_x[row]) * h.to(rdt), counts) + _segment_sum((psi_s / psi_x[s_row]) * s_w.to(rdt), s_counts)
+    t3 = time.time_ns()
+    return eloc.to(dtype), torch.zeros_like(eloc).to(dtype), psi_x, ((t2 - c.t0) / 1e6, 0.0, (t3 - t2) / 1e6)
+
+
+def _eloc_generic(c):
+    """The generic path: the same tensor algebra as the reference, on the materialised (batch, ncomb) matrices."""
+    x, dtype = c.x, c.dtype
+    comb_x, comb_hij = get_comb_hij_fused(x, c.h1e, c.h2e, *c.system)
+    t1 = time.time_ns()
+    hij_spin = get_hij_torch(x, comb_x, c.h1e_spin, c.h2e_spin, c.sorb, c.nele) if c.use_spin_raising else None
+    t2 = time.time_ns()
+    batch, n_comb, bra_len = comb_x.shape
+    flat = comb_x.reshape(-1, bra_len)
+    if c.use_sample_space:
+        psi_x1, f_psi = _amplitudes_sample_space(flat, batch, n_comb, c.ansatz_extra, c.WF_LUT, c.use_multi_psi, c.use_spin_flip,
+                                                 c.extra_norm, c.sorb)
+    else:
+        sel = _reduce_select(comb_hij, c.eps, c.eps_sample) if c.reduce_psi else None
+        psi_x1, f_psi = _amplitudes(flat, sel, batch, n_comb, c.ansatz_f, c.ansatz_extra, c.WF_LUT, c.use_unique, c.use_multi_psi,
+                                    c.use_spin_flip, c.extra_norm, dtype, c.sorb, x.device)
+    rdt = _real_dtype(dtype)
+    eloc = _contract(f_psi, psi_x1, comb_hij.to(rdt))
+    sloc = _contract(f_psi, psi_x1, hij_spin.to(rdt)) if c.use_spin_raising else torch.zeros_like(eloc)
+    t3 = time.time_ns()
+    return eloc.to(dtype), sloc.to(dtype), psi_x1[..., 0].to(dtype), ((t1 - c.t0) / 1e6, (t2 - t1) / 1e6, (t3 - t2) / 1e6)
+
+
 def local_energy(
     x: Tensor, h1e: Tensor, h2e: Tensor, ansatz, ansatz_batch: Callable[..., Tensor], sorb: int, nele: int, noa: int, nob: int,
     dtype=torch.double, use_spin_raising: bool = False, h1e_spin: Optional[Tensor] = None, h2e_spin: Optional[Tensor] = None,
@@ -730,7 +1005,8 @@ def local_energy(
 ) -> Tuple[Tensor, Tensor, Tensor, Tuple[float, float, float]]:
     """vmc/energy/eloc.py:23-132.  Returns (eloc[n], sloc[n], psi(x)[n], (t_enumerate, t_hij, t_psi) in ms).
     _front_ticket (not in the reference): a reduce_front_launch ticket for exactly these walkers and arguments, enqueued earlier
-    (total_energy's look-ahead on a second stream)."""
+    (total_energy's look-ahead on a second stream).
+    A dispatcher: the paths of the module docstring in their order; a path that returns None has declined and the next one is asked."""
     with torch.no_grad():
         check_para(x)
         assert x.dim() == 2
@@ -740,309 +1016,31 @@ def local_energy(
             assert eps >= 0.0 and eps_sample >= 0
         if extra_norm is None:
             extra_norm = 1.0
-        device = h1e.device
-        batch = x.size(0)
-        t0 = time.time_ns()
-
-        # ---- fast path: SAMPLE_SPACE in one kernel ----------------------------------------------------
-        if use_sample_space and _fast_sample_space_ok(x, h1e, h2e, sorb, WF_LUT, use_spin_raising, use_multi_psi, use_spin_flip, noa, nob):
-            f_keys = None
-            if use_multi_psi:
-                # f on the sample-space keys (the reference stores f in the table's dtype, flip.py:392): once per parameter state, not once
-                # per chunk of walkers -- total_energy calls this function for every chunk, and the table has up to 1e5-1e6 keys
-                extra = ansatz.module.extra
-                # valid within ONE total_energy call (its token): parameters updated through `p.data.add_` -- the reference's own GD step,
-                # vmc/optim/_base.py:619 -- keep their version counters, so nothing across calls proves that f is still current
-                stamp = (id(extra), WF_LUT.bra_key.data_ptr(), WF_LUT.bra_key.size(0), str(WF_LUT.dtype), _call_token())
-                cached = getattr(WF_LUT, "_pynqs_f_keys", None)
-                if cached is not None and cached[0] == stamp and stamp[4] is not None:
-                    f_keys = cached[1]
-                else:
-                    f_keys = Func(partial(ansatz_batch, func=extra), WF_LUT.bra_key, None, True).to(WF_LUT.dtype)
-                    try:
-                        WF_LUT._pynqs_f_keys = (stamp, f_keys)
-                    except AttributeError:  # (a table object that takes no attributes)
-                        pass
-
-            def in_sample_space(h1, h2):
-                """sum over the sample space with the integrals (h1, h2): the energy, and with the S-S+ integrals <S-S+> (eloc.py:377-400)"""
-                if not (use_multi_psi or use_spin_flip):
-                    e1, p0, _ = _sample_space_fused(x, h1, h2, sorb, nele, noa, nob, WF_LUT)
-                    return e1, p0
-                # projected / multi-psi forms (flip.py:322-418, eloc.py:381-392) on the same kernel:
-                #   E_loc = conj(f(x)) [ sum_k H_k (f psi)(x'_k) + eta sum_k H_k eta_m(x'_k) (f psi)(flip x'_k) ] / (N^2 psi(x))
-                # (f psi) is a table over the sample space
-                wf = WF_LUT.wf_value * f_keys if use_multi_psi else WF_LUT.wf_value
-                e1, t0x, part = _sample_space_fused(x, h1, h2, sorb, nele, noa, nob, WF_LUT, wf, use_spin_flip)
-                if use_spin_flip:
-                    e1 = e1 + SpinProjection.eta * part
-                if use_multi_psi:
-                    # t(x) = f(x) psi(x): back to sum / psi(x) and the reference's factor conj(f(x)); psi(x), f(x) from the table
-                    # (pynqs_amd's table answers through its hash table; the reference's own WavefunctionLUT class has no `find`)
-                    pos, found = WF_LUT.find(x) if hasattr(WF_LUT, "find") else CX.wavefunction_lut(WF_LUT.bra_key, x, sorb)
-                    pos = pos.clamp_min(0)
-                    p0 = torch.where(found, WF_LUT.wf_value[pos], torch.zeros((), dtype=WF_LUT.dtype, device=x.device))
-                    f_x = torch.where(found, f_keys[pos], torch.zeros((), dtype=f_keys.dtype, device=x.device))
-                    e1 = e1 * f_x * f_x.conj()
-                else:
-                    p0 = t0x
-                return e1 / extra_norm**2, p0
-
-            eloc, psi0 = in_sample_space(h1e, h2e)
-            sloc = in_sample_space(h1e_spin, h2e_spin)[0] if use_spin_raising else torch.zeros_like(eloc)
-            t1 = time.time_ns()
-            return eloc.to(dtype), sloc.to(dtype), psi0.to(dtype), ((t1 - t0) / 1e6, 0.0, 0.0)
-
-        # ---- fast path: SIMPLE with an RBM (real parameters), amplitude ratios on chip ----------------------------
-        if (FUSED and FUSED_RBM and not reduce_psi and not use_sample_space and WF_LUT is None and x.is_cuda
-                and not (use_multi_psi or use_spin_flip) and sorb % 2 == 0
-                and h1e.dtype in (torch.float64, torch.float32)):
-            prm = _real_rbm_params(ansatz)
-            # the phase flavour (pRBM) is complex-valued; the others need a real `dtype` like the module itself
-            if (prm is not None and dtype in ((torch.complex128, torch.complex64) if prm[3] == "pRBM" else (torch.double, torch.float32))
-                    and _rbm_lds_ok(sorb, nele, noa, nob, prm[0].size(0))):
-                table = CX.RBMTable(*prm[:3])
-                eloc, psi0 = CX.eloc_rbm(x, *CX.integrals_f64(h1e, h2e), table, sorb, nele, noa, nob, rbm_type=prm[3])
-                # <S-S+> (eloc.py:173-188): the same kernel with the S-S+ integrals
-                sloc = CX.eloc_rbm(x, *CX.integrals_f64(h1e_spin, h2e_spin), table, sorb, nele, noa, nob, want_psi=False, rbm_type=prm[3])[0] \
-                    if use_spin_raising else torch.zeros_like(eloc)
-                t1 = time.time_ns()
-                return eloc.to(dtype), sloc.to(dtype), psi0.to(dtype), ((t1 - t0) / 1e6, 0.0, 0.0)
-            cprm = _complex_rbm_params(ansatz) if prm is None else None
-            # complex parameters (complex running products in the kernel); "cos" is real-valued and rides on the same kernel
-            if (cprm is not None and dtype in ((torch.double, torch.float32) if cprm[4] else (torch.complex128, torch.complex64))
-                    and N.lib().pynqs_eloc_crbm_supported(sorb, nele, noa, nob, cprm[0].size(0))):
-                ctable = CX.CRBMTable(*cprm[:3])
-                eloc, psi0 = CX.eloc_crbm(x, *CX.integrals_f64(h1e, h2e), ctable, sorb, nele, noa, nob, log_scale=cprm[3])
-                sloc = CX.eloc_crbm(x, *CX.integrals_f64(h1e_spin, h2e_spin), ctable, sorb, nele, noa, nob, want_psi=False)[0] \
-                    if use_spin_raising else torch.zeros_like(eloc)
-                if cprm[4]:
-                    eloc, sloc, psi0 = eloc.real, sloc.real, psi0.real
-                t1 = time.time_ns()
-                return eloc.to(dtype), sloc.to(dtype), psi0.to(dtype), ((t1 - t0) / 1e6, 0.0, 0.0)
-
-        if use_multi_psi:
-            ansatz_extra = partial(ansatz_batch, func=ansatz.module.extra)
-            ansatz_f = partial(ansatz_batch, func=ansatz.module.sample)
-        else:
-            ansatz_extra = None
-            ansatz_f = partial(ansatz_batch, func=ansatz)
-
-        # ---- fast path: REDUCE through the one-launch front end (deterministic and semi-stochastic, every form) ---------------
-        front = None
-        ahead = None
-        if reduce_psi and not use_sample_space and batch > 0 and _front_ok(x, h1e, sorb, nele, noa, nob, eps_sample):
-            ht, rbm_fwd = _reduce_front_options(ansatz, WF_LUT, dtype, use_multi_psi, use_spin_flip)
-            try:
-                ticket = _front_ticket if _front_ticket is not None else \
-                    reduce_front_launch(x, h1e, h2e, sorb, nele, noa, nob, eps, int(eps_sample), ht, want_pm1=not rbm_fwd, route=True)
-                if rbm_fwd and SPECULATE_RBM and not (use_multi_psi or use_spin_flip or use_spin_raising):
-                    # An RBM of the reference's family needs nothing from the host between the front end and the contraction: the amplitude
-                    # kernel takes the number of distinct x' from the device, so both are enqueued BEFORE the counters are waited for (the wait
-                    # + two launches used to leave the GPU idle for ~0.2 ms of a 1 ms call).  Used if the counters then report no overflow.
-                    ahead = _rbm_ahead(ticket, x, ansatz, WF_LUT if ht is not None else None, dtype, sorb, _front_ticket is not None)
-                front = reduce_front_finish(ticket)
-            except _FrontDense:
-                front = None   # (long rows, more kept records than the LDS list holds: the multi-pass path below, from now on)
-        if front is not None and ahead is not None and ahead[0] is front[0]:
-            t2 = t3 = time.time_ns()
-            eloc, psi_x = ahead[1], ahead[2]
-            return eloc.to(dtype), torch.zeros_like(eloc).to(dtype), psi_x.to(dtype), ((t2 - t0) / 1e6, 0.0, (t3 - t2) / 1e6)
-        if front is not None:
-            fe, nu = front
-            plain = not (use_multi_psi or use_spin_flip)
-            t2 = time.time_ns()
-            uniq = fe.uniq_onv[:nu]
-            takes_rows = fe.uniq_pm1 is not None and getattr(ansatz_batch, "accepts_pm1_rows", False) and fe.pm1_dtype == torch.get_default_dtype()
-
-            def on_distinct(fn, lut) -> Tensor:
-                """a function of the determinant on the distinct x' (the rows the kernel wrote are the module's input already)"""
-                if lut is None:
-                    return fn(fe.uniq_pm1[:nu] if takes_rows else uniq).to(dtype)
-                return Func(fn, uniq, lut, False).to(dtype)
-
-            def rbm_on_distinct():
-                """psi on the distinct x' by one kernel when the ansatz is an RBM of the reference's family (pynqs_rbm_forward), else None"""
-                if not rbm_fwd:
-                    return None
-                def fwd(W, hb, vb, kind):
-                    # every distinct x' is its parent walker with <= 4 orbitals flipped (the front end notes the parent): theta(x') from
-                    # theta(x) by 4 updates per hidden unit when the parameters fit the LDS, else from scratch
-                    if RBM_FROM_PARENTS and CX.rbm_forward_children_supported(sorb, W.size(0), kind):
-                        return CX.rbm_forward_children(uniq, fe.uniq_parent, x, W, hb, vb, sorb, kind)
-                    return CX.rbm_forward(uniq, W, hb, vb, sorb, kind)
-
-                prm = _real_rbm_params(ansatz)
-                if prm is not None and (dtype.is_complex == (prm[3] == "pRBM")):
-                    return fwd(prm[0], prm[1], prm[2], prm[3]).to(dtype)
-                cprm = _complex_rbm_params(ansatz)
-                if cprm is not None and not cprm[4] and dtype.is_complex:
-                    return fwd(cprm[0], cprm[1], cprm[2], "complex").to(dtype)
-                return None
-
-            psi_u = rbm_on_distinct()
-            if psi_u is None:
-                psi_u = on_distinct(ansatz_f, WF_LUT if ht is None else None)
-            tab = WF_LUT.wf_value if ht is not None else None
-            if plain:
-                eloc, psi_x = fe.contract(psi_u, tab)
-                num_over_psi = None
-            else:
-                # projected / multi-psi forms (flip.py:153-319): per distinct x'
-                #   T = f psi + eta eta_m(x') f(flip x') psi(flip x');  E_loc = conj(f(x)) sum_k w_k T(x'_k) / (N^2 psi(x))
-                t_u = psi_u
-                f_u = None
-                if use_multi_psi:
-                    f_u = on_distinct(ansatz_extra, None)
-                    t_u = f_u * psi_u
-                if use_spin_flip:
-                    uniq_flip = spin_flip_onv(uniq, sorb)
-                    psi_flip = Func(ansatz_f, uniq_flip, WF_LUT, use_unique).to(dtype)
-                    if use_multi_psi:
-                        psi_flip = Func(ansatz_extra, uniq_flip, None, use_unique).to(dtype) * psi_flip
-                    t_u = t_u + SpinProjection.eta * spin_flip_sign(uniq, sorb) * psi_flip
-                num, _ = fe.contract(t_u, None, divide=False)
-                _, psi_x = fe.contract(psi_u, None, divide=False)
-                scale = 1.0 / extra_norm**2
-                if use_multi_psi:
-                    scale = scale * fe.contract(f_u, None, divide=False)[1].conj()
-                num_over_psi = scale / psi_x
-                eloc = num * num_over_psi
-            if use_spin_raising:
-                # <S-S+> over the same records (eloc.py:250-310: the raw S-S+ matrix elements, also on the drawn columns)
-                xs = x if fe.nchunks == 1 else x.repeat_interleave(fe.nchunks, 0)
-                hs = get_hij_torch(xs, fe.rec_onv.view(fe.nseg, fe.stride, -1), h1e_spin, h2e_spin, sorb, nele).reshape(-1).to(fe.h_dtype)
-                hs_s = get_hij_torch(x, fe.srec_onv.view(batch, fe.eps_sample, -1), h1e_spin, h2e_spin, sorb, nele).reshape(-1).to(fe.h_dtype) \
-                    if fe.eps_sample else None
-                if plain:
-                    sloc = fe.contract(psi_u, tab, rec_w=hs, srec_w=hs_s)[0]
-                else:
-                    sloc = fe.contract(t_u, None, divide=False, rec_w=hs, srec_w=hs_s)[0] * num_over_psi
-            else:
-                sloc = torch.zeros_like(eloc)
-            t3 = time.time_ns()
-            return eloc.to(dtype), sloc.to(dtype), psi_x.to(dtype), ((t2 - t0) / 1e6, 0.0, (t3 - t2) / 1e6)
-
-        # ---- fast path: REDUCE (deterministic) with on-chip compaction, multi-pass (rows too long for the fused front end) -----
-        # (also the spin-flip projected and multi-psi forms, flip.py:200-319: their extra factors are evaluated on the kept records only)
-        if (FUSED and reduce_psi and not use_sample_space and eps_sample == 0 and sorb % 2 == 0 and x.is_cuda):
-            row, col, onv, h, counts = reduce_compact(x, h1e, h2e, sorb, nele, noa, nob, eps)
-            t2 = time.time_ns()
-            first = col == 0
-
-            def at_x(v: Tensor) -> Tensor:
-                """value on the kept column 0 of each row; 0 if it was filtered out (as in the reference)"""
-                out = torch.zeros(batch, dtype=dtype, device=x.device)
-                out[row[first]] = v[first]
-                return out
-
-            psi = Func(ansatz_f, onv, WF_LUT, use_unique).to(dtype)
-            psi_x = at_x(psi)
-            t = psi
-            if use_multi_psi:
-                f = Func(ansatz_extra, onv, None, use_unique).to(dtype)
-                t = f * psi
-            if use_spin_flip:
-                onv_flip = spin_flip_onv(onv, sorb)
-                psi_flip = Func(ansatz_f, onv_flip, WF_LUT, use_unique).to(dtype)
-                if use_multi_psi:
-                    psi_flip = Func(ansatz_extra, onv_flip, None, use_unique).to(dtype) * psi_flip
-                t = t + SpinProjection.eta * spin_flip_sign(onv, sorb) * psi_flip
-            if use_multi_psi:
-                t = t * at_x(f).conj()[row]
-            if use_multi_psi or use_spin_flip:
-                t = t / extra_norm**2
-            ratio = t / psi_x[row]
-
-            def row_sums(wv: Tensor) -> Tensor:
-                # rows are contiguous segments: a segmented sum instead of index_add_ (atomics: 2.7 of 5.0 ms on Fe2S2)
-                if wv.is_complex():
-                    return torch.view_as_complex(torch.segment_reduce(torch.view_as_real(wv).contiguous(), "sum", lengths=counts, unsafe=True))
-                return torch.segment_reduce(wv, "sum", lengths=counts, unsafe=True)
-
-            eloc = row_sums(ratio * h.to(_real_dtype(dtype)))
-            if use_spin_raising:
-                # <S-S+> over the same kept columns (eloc.py:250-310): its matrix elements for the (x, x') pairs of the records
-                h_spin = get_hij_torch(x[row].contiguous(), onv.unsqueeze(1), h1e_spin, h2e_spin, sorb, nele).reshape(-1)
-                sloc = row_sums(ratio * h_spin.to(_real_dtype(dtype)))
-            else:
-                sloc = torch.zeros_like(eloc)
-            t3 = time.time_ns()
-            return eloc.to(dtype), sloc.to(dtype), psi_x, ((t2 - t0) / 1e6, 0.0, (t3 - t2) / 1e6)
-
-        # ---- fast path: semi-stochastic REDUCE (eps_sample > 0) with the selection done on chip ------------------------
-        if (FUSED and FUSED_SAMPLED and reduce_psi and not use_sample_space and eps_sample > 0
-                and not (use_spin_raising or use_multi_psi or use_spin_flip) and sorb % 2 == 0 and x.is_cuda):
-            (row, col, onv, h, counts), (s_row, s_col, s_onv, s_w, s_counts) = reduce_compact_sampled(
-                x, h1e, h2e, sorb, nele, noa, nob, eps, int(eps_sample))
-            t2 = time.time_ns()
-            psi_all = Func(ansatz_f, torch.cat([onv, s_onv]), WF_LUT, use_unique).to(dtype)
-            psi, psi_s = psi_all[: onv.size(0)], psi_all[onv.size(0):]
-            # psi(x): column 0 among the kept records (every row keeps it unless |H_00| < eps, where the reference divides by 0 too),
-            # else among the drawn ones
-            psi_x = torch.zeros(batch, dtype=dtype, device=x.device)
-            first_s = s_col == 0
-            psi_x[s_row[first_s]] = psi_s[first_s]
-            first = col == 0
-            psi_x[row[first]] = psi[first]
-            rdt = _real_dtype(dtype)
-
-            def seg(wv, cnt):
-                if wv.is_complex():
-                    return torch.view_as_complex(torch.segment_reduce(torch.view_as_real(wv).contiguous(), "sum", lengths=cnt, unsafe=True))
-                return torch.segment_reduce(wv, "sum", lengths=cnt, unsafe=True)
-
-            eloc = seg((psi / psi_x[row]) * h.to(rdt), counts) + seg((psi_s / psi_x[s_row]) * s_w.to(rdt), s_counts)
-            t3 = time.time_ns()
-            return eloc.to(dtype), torch.zeros_like(eloc).to(dtype), psi_x, ((t2 - t0) / 1e6, 0.0, (t3 - t2) / 1e6)
-
-        # ---- generic path: same tensor algebra as the reference ---------------------------------------------
-        comb_x, comb_hij = get_comb_hij_fused(x, h1e, h2e, sorb, nele, noa, nob)
-        t1 = time.time_ns()
-        hij_spin = get_hij_torch(x, comb_x, h1e_spin, h2e_spin, sorb, nele) if use_spin_raising else None
-        t2 = time.time_ns()
-        n_comb, bra_len = comb_x.size(1), comb_x.size(2)
-        flat = comb_x.reshape(-1, bra_len)
-
-        if use_sample_space:
-            # psi only from the table (eloc.py:381-385, flip.py:375-383); misses stay 0
-            def lut_psi(xx: Tensor) -> Tensor:
-                out = torch.zeros(xx.size(0), device=xx.device, dtype=WF_LUT.dtype)
-                idx, _, value = WF_LUT.lookup(xx)
-                out[idx] = value
-                return out, idx
-
-            psi_flat, hit = lut_psi(flat)
-            psi_x1 = psi_flat.reshape(batch, n_comb)
-            if use_spin_flip:
-                eta = SpinProjection.eta
-                flip = spin_flip_onv(flat, sorb)
-                eta_m = spin_flip_sign(flat, sorb).reshape(batch, n_comb)
-                psi_flip_flat, hit_f = lut_psi(flip)
-                psi_flip = psi_flip_flat.reshape(batch, n_comb)
-                if use_multi_psi:
-                    fz = torch.zeros_like(psi_flat); fz[hit] = Func(ansatz_extra, flat[hit], None, True).to(fz.dtype)
-                    ff = torch.zeros_like(psi_flat); ff[hit_f] = Func(ansatz_extra, flip[hit_f], None, True).to(ff.dtype)
-                    f, f_flip = fz.reshape(batch, n_comb), ff.reshape(batch, n_comb)
-                    f_psi = (f * psi_x1 + eta * eta_m * f_flip * psi_flip) * f[..., 0].reshape(-1, 1).conj() / extra_norm**2
-                else:
-                    f_psi = (psi_x1 + eta * eta_m * psi_flip) / extra_norm**2
-            elif use_multi_psi:
-                fz = torch.zeros_like(psi_flat); fz[hit] = Func(ansatz_extra, flat[hit], None, True).to(fz.dtype)
-                f = fz.reshape(batch, n_comb)
-                f_psi = psi_x1 * f * f[..., 0].reshape(-1, 1).conj() / extra_norm**2
-            else:
-                f_psi = psi_x1
-        else:
-            sel = _reduce_select(comb_hij, eps, eps_sample) if reduce_psi else None
-            psi_x1, f_psi = _amplitudes(flat, sel, batch, n_comb, ansatz_f, ansatz_extra, WF_LUT, use_unique, use_multi_psi,
-                                        use_spin_flip, extra_norm, dtype, sorb, x.device)
-
-        rdt = _real_dtype(dtype)
-        eloc = _contract(f_psi, psi_x1, comb_hij.to(rdt))
-        sloc = _contract(f_psi, psi_x1, hij_spin.to(rdt)) if use_spin_raising else torch.zeros_like(eloc)
-        t3 = time.time_ns()
-        return eloc.to(dtype), sloc.to(dtype), psi_x1[..., 0].to(dtype), ((t1 - t0) / 1e6, (t2 - t1) / 1e6, (t3 - t2) / 1e6)
+        c = SimpleNamespace(
+            x=x, h1e=h1e, h2e=h2e, ansatz=ansatz, ansatz_batch=ansatz_batch, system=(sorb, nele, noa, nob), sorb=sorb, nele=nele, dtype=dtype,
+            use_spin_raising=use_spin_raising, h1e_spin=h1e_spin, h2e_spin=h2e_spin, WF_LUT=WF_LUT, use_unique=use_unique, reduce_psi=reduce_psi,
+            eps=eps, eps_sample=eps_sample, use_sample_space=use_sample_space, use_multi_psi=use_multi_psi, use_spin_flip=use_spin_flip,
+            extra_norm=extra_norm, front_ticket=_front_ticket, ansatz_f=None, ansatz_extra=None, t0=time.time_ns())
+        plain = not (use_multi_psi or use_spin_flip)
+        gpu_ok = FUSED and x.is_cuda and sorb % 2 == 0   # (every fused kernel packs an even number of spin orbitals)
+        if use_sample_space and _fast_sample_space_ok(x, h1e, sorb, WF_LUT):
+            return _eloc_sample_space_fused(c)
+        simple_rbm = gpu_ok and FUSED_RBM and not reduce_psi and not use_sample_space and WF_LUT is None and plain and h1e.dtype in (torch.float64, torch.float32)
+        out = _eloc_simple_rbm(c) if simple_rbm else None
+        if out is not None:
+            return out
+        # (ansatz_f: psi; ansatz_extra: f of the multi-psi form -- functions of a batch of determinants)
+        c.ansatz_extra = partial(ansatz_batch, func=ansatz.module.extra) if use_multi_psi else None
+        c.ansatz_f = partial(ansatz_batch, func=ansatz.module.sample if use_multi_psi else ansatz)
+        front = reduce_psi and not use_sample_space and x.size(0) > 0 and _front_ok(x, h1e, sorb, nele, noa, nob, eps_sample)
+        out = _eloc_reduce_front(c) if front else None
+        if out is not None:
+            return out
+        if gpu_ok and reduce_psi and not use_sample_space and eps_sample == 0:
+            return _eloc_reduce_multipass(c)
+        if gpu_ok and FUSED_SAMPLED and reduce_psi and not use_sample_space and eps_sample > 0 and plain and not use_spin_raising:
+            return _eloc_reduce_multipass_sampled(c)
+        return _eloc_generic(c)
 
 
 AUTO_NBATCH_KEEP = 64   # calls of one shape served from the last answer before the device memory is looked at again
@@ -1056,7 +1054,7 @@ def auto_nbatch(x, h1e, sorb, nele, noa, nob, ansatz, WF_LUT, dtype, reduce_psi,
     n_sd = get_Num_SinglesDoubles(sorb, noa, nob)
     fused = None
     if n and x.is_cuda and FUSED and sorb % 2 == 0:
-        if use_sample_space and _fast_sample_space_ok(x, h1e, None, sorb, WF_LUT, use_spin_raising, use_multi_psi, use_spin_flip, noa, nob):
+        if use_sample_space and _fast_sample_space_ok(x, h1e, sorb, WF_LUT):
             fused = "sample_space"
         elif reduce_psi and not use_sample_space and _front_ok(x[: min(n, 4096)], h1e, sorb, nele, noa, nob, eps_sample):
             fused = "reduce"
@@ -1124,7 +1122,7 @@ def total_energy(
         if look_ahead:
             main = torch.cuda.current_stream(device)
             side = _side_stream(device)
-            ht_, rbm_fwd_ = _reduce_front_options(ansatz, WF_LUT, dtype, use_multi_psi, use_spin_flip)
+            ht_, rbm_ = _reduce_front_options(ansatz, WF_LUT, dtype, use_multi_psi, use_spin_flip)
 
             xc = x.contiguous()  # (once, on the main stream: the chunks are views of it, no copy kernel runs between the streams)
 
@@ -1138,7 +1136,7 @@ def total_energy(
                 with torch.cuda.stream(side):
                     # (consumer: the workspace is allocated in the side stream's pool and read on the main stream -- the allocator must not hand
                     # its memory out again while main-stream work on it is pending)
-                    tickets[k] = reduce_front_launch(xs, h1e, h2e, sorb, nele, noa, nob, eps, int(eps_sample), ht_, want_pm1=not rbm_fwd_, slot=k % 2, route=True,
+                    tickets[k] = reduce_front_launch(xs, h1e, h2e, sorb, nele, noa, nob, eps, int(eps_sample), ht_, want_pm1=rbm_ is None, slot=k % 2, route=True,
                                                      consumer=main)
 
             launch(0)
@@ -1148,13 +1146,13 @@ def total_energy(
             if look_ahead:
                 ticket = tickets.pop(k, None)
                 if ticket is not None:
-                    ticket["ev"].synchronize()       # (host: the counters of chunk k are there)
-                    main.wait_event(ticket["ev"])     # (device: chunk k's records are there before the ansatz / contraction read them)
+                    ticket.ev.synchronize()       # (host: the counters of chunk k are there)
+                    main.wait_event(ticket.ev)     # (device: chunk k's records are there before the ansatz / contraction read them)
                 # (a chunk whose rows outgrew the front end's LDS list sends the rest of the call to the multi-pass path: no more tickets)
                 if k + 1 < len(ends) and _front_ok(x[starts[k + 1]:ends[k + 1]], h1e, sorb, nele, noa, nob, eps_sample):
                     launch(k + 1)                     # runs while the ansatz works on chunk k
             _eloc, _sloc, _psi, _ = local_energy(
-                ticket["x"] if ticket is not None else x[begin:end], h1e, h2e, ansatz, _ansatz_batch, sorb, nele, noa, nob, dtype=dtype, WF_LUT=WF_LUT,
+                ticket.x if ticket is not None else x[begin:end], h1e, h2e, ansatz, _ansatz_batch, sorb, nele, noa, nob, dtype=dtype, WF_LUT=WF_LUT,
                 use_spin_raising=False if reduce_psi else use_spin_raising, h1e_spin=h1e_spin, h2e_spin=h2e_spin, use_unique=use_unique,
                 reduce_psi=reduce_psi, eps=eps, eps_sample=eps_sample, use_sample_space=use_sample_space, index=(begin, end), alpha=alpha,
                 use_multi_psi=use_multi_psi, extra_norm=extra_norm, use_spin_flip=use_spin_flip, _front_ticket=ticket)

@@ -4,6 +4,7 @@ sit on the path: SURVEY.md 8a rows a3, a16).  Same names and argument meaning as
 """
 from __future__ import annotations
 
+import sys
 from typing import Callable, List, Optional, Tuple
 
 import numpy as np
@@ -332,8 +333,6 @@ class _SpinProjection:
         if self._eta is None:
             # inside a PyNQS process that imports pynqs_amd.energy (one-line change) the run initialises PyNQS' own
             # instance (utils/public_function.py:1017-1036): follow it instead of asking for a second init
-            import sys
-
             host = getattr(sys.modules.get("utils.public_function"), "SpinProjection", None)
             if host is not None and host is not self:
                 try:

@@ -14,6 +14,7 @@ when it needs the number of distinct rows to slice the ansatz' input; a captured
 from __future__ import annotations
 
 import ctypes as C
+import os
 from typing import Optional, Tuple
 
 import torch
@@ -24,9 +25,9 @@ from . import _native as N
 OVERFLOW_DOUBLES, OVERFLOW_TABLE, OVERFLOW_UNIQUE = 1, 2, 4
 ROW_CACHE = True                  # semi-stochastic kernel: cache the row in global memory for the draws (see ReduceFrontEnd)
 ROW_CACHE_MAX_BYTES = 8 << 30
-ROW_F32 = __import__("os").environ.get("PYNQS_ROW_F32", "1") != "0"  # semi-stochastic calls on short rows: the two-kernel form (see ReduceFrontEnd)
-ROW_F32_MAX_BYTES = int(__import__("os").environ.get("PYNQS_ROW_F32_MAX_BYTES", str(16 << 30)))  # long rows: the float32 copy is 4 bytes per column and walker
-TILE_SCRATCH_MIN_ROW = int(__import__("os").environ.get("PYNQS_TILE_SCRATCH_MIN_ROW", "65536"))  # columns per row from which the tile sums leave the LDS
+ROW_F32 = os.environ.get("PYNQS_ROW_F32", "1") != "0"  # semi-stochastic calls on short rows: the two-kernel form (see ReduceFrontEnd)
+ROW_F32_MAX_BYTES = int(os.environ.get("PYNQS_ROW_F32_MAX_BYTES", str(16 << 30)))  # long rows: the float32 copy is 4 bytes per column and walker
+TILE_SCRATCH_MIN_ROW = int(os.environ.get("PYNQS_TILE_SCRATCH_MIN_ROW", "65536"))  # columns per row from which the tile sums leave the LDS
 
 
 def _pow2_at_least(v: int) -> int:
