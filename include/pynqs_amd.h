@@ -565,6 +565,34 @@ int pynqs_mcmc_accept(uint64_t *states, double *psi, const uint64_t *proposals, 
                       int sorb, int is_complex, uint64_t seed, uint64_t chain_base, uint64_t t, uint64_t *record_row,
                       int64_t *n_accept, void *stream);
 
+/* ---- reduced density matrices ---------------------------------------------------------------------------------------------------------
+ * With E = sum_x w_x sum_k H[x,k] r_{x,k}, r = psi(x'_k) / psi(x), and H[x,k] linear in the packed integrals exactly as the local-energy
+ * kernels read them:   rdm1[q sorb + p] = dE / dh1e[q sorb + p]  (h1e's layout, sorb^2 doubles),
+ *                      rdm2[t]          = dE / dh2e[t]           (h2e's packed layout, pair (pair + 1) / 2 doubles).
+ * Per walker: +w on rdm1[p,p] for every occupied p and on rdm2[tri(pq,pq)] for every occupied pair; a single h -> q with sign s adds
+ * s w Re r to rdm1[q sorb + h] and, for every occupied k != h, s sigma w Re r to rdm2[tri(pair(h,k), pair(q,k))], sigma = -1 iff
+ * (h > k) != (q > k); a double (h0 > h1 -> q0 > q1) adds s w Re r to rdm2[tri(pair(h0,h1), pair(q0,q1))].  A packed slot aliases (ij,kl)
+ * with (kl,ij): it holds the Hermitian sum.  By construction dot(h1e, rdm1) + dot(h2e, rdm2) = sum_x w_x Re E_loc(x) for any integrals,
+ * the diagonal of rdm1 sums to nele sum w and the diagonal pair slots of rdm2 to nele (nele - 1) / 2 sum w.
+ * Walkers whose electron counts are not (noA, noB), or with bits at or above sorb, contribute nothing.
+ *
+ *   pynqs_rdm_scatter : any ansatz.  ratio: double[nbatch][ncomb] (is_complex: [nbatch][ncomb][2], the real part is used) in the column
+ *        order of pynqs_comb (column 0 = x itself, not read).  ADDS into rdm1 / rdm2 (the caller zeroes them; several calls accumulate
+ *        chunks of walkers) with f64 global atomics: NOT bit-reproducible.
+ *   pynqs_rdm_rbm : real RBM (PYNQS_RBM_REAL), table from pynqs_rbm_table_build.  OVERWRITES rdm1 / rdm2.  Nothing of size
+ *        nbatch x ncomb exists, no float atomics, every sum in a fixed order (walker order): two calls give the same bits.  workspace:
+ *        pynqs_rdm_rbm_workspace bytes.  The amplitude ratio is (owner factor) x (lane constant) x prod_h (b_h + a_h g_h)
+ *        (kernels_rdm.hip); the lane constant is exp(+-2 sum_o (sum_h W_ho - a_o)) over the two orbitals of the lane side, which must
+ *        stay a finite double (|sum_h W_ho| below ~170 per orbital).
+ *   pynqs_rdm_rbm_supported : 1 if the fused kernel serves (sorb even, (sorb / 2)^2 <= 2048, nhidden <= 512, its tables within 64 KiB of
+ *        LDS), else 0: callers then use pynqs_rdm_scatter.                                                                              */
+int pynqs_rdm_scatter(const uint64_t *bra, int64_t nbatch, int sorb, int nele, int noA, int noB, const double *w, const double *ratio,
+                      int is_complex, double *rdm1, double *rdm2, void *stream);
+int pynqs_rdm_rbm_supported(int sorb, int nele, int noA, int noB, int nhidden);
+int64_t pynqs_rdm_rbm_workspace(int64_t nbatch, int sorb, int nhidden);
+int pynqs_rdm_rbm(const uint64_t *bra, int64_t nbatch, int sorb, int nele, int noA, int noB, const double *w, const void *rbm_table,
+                  int nhidden, void *workspace, double *rdm1, double *rdm2, void *stream);
+
 #ifdef __cplusplus
 }
 #endif

@@ -13,6 +13,7 @@ Modules (reference counterpart):
   distributed      utils/distributed/comm.py: packed all-reduce, all-gather of uneven shards, shard bounds
   sample_comm      Sampler.gather_scatter_sample (vmc/sample.py:627-772)
   gfmc             gfmc/walker.py: Green's-function row, move (one kernel), branching
+  rdm              (no counterpart) one- and two-body reduced density matrices in the integrals' packed layouts
   rbm              the real RBM amplitude of vmc/ansatz/rbm/rbm.py (used by tests, bench and the example)
 """
 __version__ = "0.1.0"
