@@ -205,6 +205,10 @@ int pynqs_unique_first(const uint64_t *onv, int64_t n, int sorb, void *workspace
  *                           2 or 4 flipped orbitals (no overflow for any theta); results agree with the
  *                           materialised path to rounding (tests: 1e-8 Ha). */
 int pynqs_eloc_rbm_supported(int sorb, int nele, int noA, int noB, int nhidden);
+/* [host] the form a launch of pynqs_eloc_rbm / _flavour (green = 0) or pynqs_green_rbm (green = 1) on nbatch walkers takes, from the
+ * very rule the launch uses: -1 if unsupported, else bit 0 = the windowed kernel (sorb x nhidden beyond the LDS), bit 1 = a walker's
+ * tiles are cut over several workgroups that add their parts with atomics (fewer than 1024 walkers). */
+int pynqs_eloc_rbm_form(int64_t nbatch, int sorb, int nele, int noA, int noB, int nhidden, int green);
 int64_t pynqs_rbm_table_bytes(int sorb, int nhidden);
 int pynqs_rbm_table_build(const double *weights, const double *hidden_bias, const double *visible_bias, int sorb,
                           int nhidden, void *table, void *stream);
@@ -231,6 +235,8 @@ int pynqs_eloc_rbm_flavour(const uint64_t *bra, int64_t nbatch, int sorb, int ne
  *   pynqs_eloc_crbm : eloc double[nbatch][2] = sum_x' <x|H|x'> psi(x')/psi(x);  psi double[nbatch][2] (may be NULL) =
  *                     psi(x) exp(-log_scale). */
 int pynqs_eloc_crbm_supported(int sorb, int nele, int noA, int noB, int nhidden);
+/* [host] as pynqs_eloc_rbm_form, for pynqs_eloc_crbm */
+int pynqs_eloc_crbm_form(int64_t nbatch, int sorb, int nele, int noA, int noB, int nhidden);
 int64_t pynqs_crbm_table_bytes(int sorb, int nhidden);
 int pynqs_crbm_table_build(const double *weights, const double *hidden_bias, const double *visible_bias, int sorb, int nhidden,
                            void *table, void *stream);

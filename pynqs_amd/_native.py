@@ -51,11 +51,13 @@ SIGNATURES = {
     "pynqs_keys_index_density": (_int, [_vp, _i64, _int, _vp, _vp]),
     "pynqs_eloc_sample_space_indexed": (_int, [_vp, _i64, _int, _int, _int, _int, _vp, _vp, _i64, _vp, _vp, _int, _int, _vp, _vp, _vp]),
     "pynqs_eloc_rbm_supported": (_int, [_int, _int, _int, _int, _int]),
+    "pynqs_eloc_rbm_form": (_int, [_i64, _int, _int, _int, _int, _int, _int]),
     "pynqs_rbm_table_bytes": (_i64, [_int, _int]),
     "pynqs_rbm_table_build": (_int, [_vp, _vp, _vp, _int, _int, _vp, _vp]),
     "pynqs_eloc_rbm": (_int, [_vp, _i64, _int, _int, _int, _int, _vp, _vp, _int, _vp, _vp, _vp]),
     "pynqs_eloc_rbm_flavour": (_int, [_vp, _i64, _int, _int, _int, _int, _vp, _vp, _int, _int, _vp, _vp, _vp]),
     "pynqs_eloc_crbm_supported": (_int, [_int, _int, _int, _int, _int]),
+    "pynqs_eloc_crbm_form": (_int, [_i64, _int, _int, _int, _int, _int]),
     "pynqs_crbm_table_bytes": (_i64, [_int, _int]),
     "pynqs_crbm_table_build": (_int, [_vp, _vp, _vp, _int, _int, _vp, _vp]),
     "pynqs_eloc_crbm": (_int, [_vp, _i64, _int, _int, _int, _int, _vp, _vp, _int, _dbl, _vp, _vp, _vp]),

@@ -608,6 +608,35 @@ static uint32_t rbm_window(const SDParams &p, const RbmLayout &rl, size_t window
   return 0;
 }
 
+// The form a launch takes: workgroups per walker (few walkers: a walker's tiles are cut over several workgroups, each of which
+// repeats the per-walker set-up and adds its part with an atomic), the windowed kernel's shape, the hidden units resident in LDS.
+struct RbmForm {
+  uint32_t nchunks, hw;
+  RbmShape shape;
+};
+static RbmForm rbm_form(const SDParams &p, const RbmLayout &rl, const RbmBlocks &B, int64_t nbatch, bool green) {
+  RbmForm f;
+  f.nchunks = 1;
+  if (nbatch < 1024 && !green) {  // (the Green's-function row finishes its diagonal in the kernel: one workgroup per walker)
+    f.nchunks = (uint32_t)((1024 + nbatch - 1) / nbatch);
+    const uint32_t maxc = B.ntiles / 4 > 0 ? B.ntiles / 4 : 1;
+    if (f.nchunks > maxc) f.nchunks = maxc;
+  }
+  f.shape = rbm_windowed_shape(B.ntiles / f.nchunks);
+  f.hw = rbm_window(p, rl, f.shape.window_lds);
+  return f;
+}
+
+extern "C" int pynqs_eloc_rbm_form(int64_t nbatch, int sorb, int nele, int noA, int noB, int nhidden, int green) {
+  SDParams p;
+  PlanLayout pl;
+  RbmLayout rl;
+  if (nbatch < 1 || !make_sd_params(sorb, nele, noA, noB, &p) || !make_plan_layout(sorb, &pl) || !make_rbm_layout(sorb, nhidden, &rl)) return -1;
+  const RbmForm f = rbm_form(p, rl, make_rbm_blocks(p), nbatch, green != 0);
+  if (f.hw == 0) return -1;
+  return (f.hw < (uint32_t)rl.Hloop ? 1 : 0) | (f.nchunks > 1 ? 2 : 0);
+}
+
 extern "C" int64_t pynqs_rbm_table_bytes(int sorb, int nhidden) {
   RbmLayout rl;
   if (!make_rbm_layout(sorb, nhidden, &rl)) return -1;
@@ -651,15 +680,9 @@ static int eloc_rbm_impl(const uint64_t *bra, int64_t nbatch, int sorb, int nele
   if (nbatch == 0) return PYNQS_OK;
   if (!bra || !plan || !rbm_table || !eloc) return set_error(PYNQS_EINVAL, "null pointer");
   const RbmBlocks B = make_rbm_blocks(p);
-  // few walkers: cut a walker's tiles over several workgroups (each repeats the per-walker set-up)
-  uint32_t nchunks = 1;
-  if (nbatch < 1024 && !green) {  // (the Green's-function row finishes its diagonal in the kernel: one workgroup per walker)
-    nchunks = (uint32_t)((1024 + nbatch - 1) / nbatch);
-    const uint32_t maxc = B.ntiles / 4 > 0 ? B.ntiles / 4 : 1;
-    if (nchunks > maxc) nchunks = maxc;
-  }
-  const RbmShape shape = rbm_windowed_shape(B.ntiles / nchunks);
-  const uint32_t hw = rbm_window(p, rl, shape.window_lds);
+  const RbmForm form = rbm_form(p, rl, B, nbatch, green != nullptr);
+  const uint32_t nchunks = form.nchunks, hw = form.hw;
+  const RbmShape shape = form.shape;
   if (hw == 0) return set_error(PYNQS_EINVAL, "the walker tables of this system leave no LDS for the RBM rows");
   const bool windowed = hw < (uint32_t)rl.Hloop;
   const size_t lds = lds_bytes_rbm(p, rl, hw);

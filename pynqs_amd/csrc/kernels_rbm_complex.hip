@@ -389,6 +389,27 @@ static uint32_t crbm_window(const SDParams &p, const CrbmLayout &cl) {
   return 0u;
 }
 
+// few walkers: a walker's tiles over several workgroups (each repeats the per-walker set-up and adds its part with an atomic)
+static uint32_t crbm_chunks(const CrbmBlocks &B, int64_t nbatch) {
+  uint32_t nchunks = 1;
+  if (nbatch < 1024) {
+    nchunks = (uint32_t)((1024 + nbatch - 1) / nbatch);
+    const uint32_t maxc = B.ntiles / 4 > 0 ? B.ntiles / 4 : 1;
+    if (nchunks > maxc) nchunks = maxc;
+  }
+  return nchunks;
+}
+
+extern "C" int pynqs_eloc_crbm_form(int64_t nbatch, int sorb, int nele, int noA, int noB, int nhidden) {
+  SDParams p;
+  PlanLayout pl;
+  CrbmLayout cl;
+  if (nbatch < 1 || !make_sd_params(sorb, nele, noA, noB, &p) || !make_plan_layout(sorb, &pl) || !make_crbm_layout(sorb, nhidden, &cl)) return -1;
+  const uint32_t hw = crbm_window(p, cl);
+  if (hw == 0) return -1;
+  return (hw < (uint32_t)cl.Hloop ? 1 : 0) | (crbm_chunks(make_crbm_blocks(p), nbatch) > 1 ? 2 : 0);
+}
+
 extern "C" int64_t pynqs_crbm_table_bytes(int sorb, int nhidden) {
   CrbmLayout cl;
   if (!make_crbm_layout(sorb, nhidden, &cl)) return -1;
@@ -433,12 +454,7 @@ extern "C" int pynqs_eloc_crbm(const uint64_t *bra, int64_t nbatch, int sorb, in
   const bool windowed = hw < (uint32_t)cl.Hloop;
   const size_t lds = lds_bytes_crbm(p, cl, hw);
   const CrbmBlocks B = make_crbm_blocks(p);
-  uint32_t nchunks = 1;  // few walkers: a walker's tiles over several workgroups (each repeats the per-walker set-up)
-  if (nbatch < 1024) {
-    nchunks = (uint32_t)((1024 + nbatch - 1) / nbatch);
-    const uint32_t maxc = B.ntiles / 4 > 0 ? B.ntiles / 4 : 1;
-    if (nchunks > maxc) nchunks = maxc;
-  }
+  const uint32_t nchunks = crbm_chunks(B, nbatch);
   const uint64_t grid = (uint64_t)nbatch * nchunks;
   if (grid > 0x7fffffffull) return set_error(PYNQS_EINVAL, "grid too large");
   hipStream_t st = (hipStream_t)stream;

@@ -113,12 +113,20 @@ def exact_ld(rbm: Rbm, x: np.ndarray) -> Exact:
     """The reference in numpy longdouble for the +-1 rows x [n, sorb]."""
     assert rbm.kind in ("real", "tanh", "pRBM", "complex"), rbm.kind
     xl = x.astype(LD)
-    n = x.shape[0]
-    S = hidden_scale(rbm)
-    one, zero = np.ones(n, dtype=LD), np.zeros(n, dtype=LD)
     if rbm.kind == "complex":
         a = rbm.hb.real.astype(LD) + xl @ rbm.W.real.T.astype(LD)
         b = rbm.hb.imag.astype(LD) + xl @ rbm.W.imag.T.astype(LD)
+        return exact_from_theta(rbm, a, b, xl @ rbm.vb.real.astype(LD), xl @ rbm.vb.imag.astype(LD))
+    return exact_from_theta(rbm, rbm.hb.astype(LD) + xl @ rbm.W.T.astype(LD), None, xl @ rbm.vb.astype(LD), None)
+
+
+def exact_from_theta(rbm: Rbm, a: np.ndarray, b, axr: np.ndarray, axi) -> Exact:
+    """exact_ld from theta = a + i b (longdouble [n, H]; b None for real parameters) and a.x = axr + i axi (longdouble [n]) of the rows:
+    for callers that have theta of many rows which differ from one row in a few orbitals (eloc_exact)."""
+    n = a.shape[0]
+    S = hidden_scale(rbm)
+    one, zero = np.ones(n, dtype=LD), np.zeros(n, dtype=LD)
+    if rbm.kind == "complex":
         s = np.where(a < 0, LD(-1), LD(1))
         e = np.exp(-2 * np.abs(a))
         ome = -np.expm1(-2 * np.abs(a))  # 1 - e
@@ -128,14 +136,12 @@ def exact_ld(rbm: Rbm, x: np.ndarray) -> Exact:
             re = (np.abs(a) + 0.5 * np.log(den)).sum(1)
             im = (s * b + np.arctan2(-2 * s * e * sb * cb, ome + 2 * e * cb * cb)).sum(1)
             y = (s * ome * (1 + e) / den) + 1j * (4 * e * sb * cb / den)
-        axr, axi = xl @ rbm.vb.real.astype(LD), xl @ rbm.vb.imag.astype(LD)
         cond = 1 + (np.abs(y) * S).sum(1) + np.abs(rbm.vb).astype(LD).sum()
         return Exact(rbm.kind, re + axr, im + axi, one, cond.astype(np.float64), y, np.abs(1 - y * y).astype(np.float64))
-    th = rbm.hb.astype(LD) + xl @ rbm.W.T.astype(LD)
+    th, ax = a, axr
     e = np.exp(-2 * np.abs(th))
     lnh = (np.abs(th) + np.log1p(e)).sum(1)
     y = np.where(th < 0, LD(-1), LD(1)) * (-np.expm1(-2 * np.abs(th))) / (1 + e)
-    ax = xl @ rbm.vb.astype(LD)
     cond = (1 + (np.abs(y) * S).sum(1) + np.abs(rbm.vb).astype(LD).sum()).astype(np.float64)
     sech2 = (4 * e / ((1 + e) * (1 + e))).astype(np.float64)
     if rbm.kind == "real":
@@ -352,6 +358,7 @@ def grad_errors(ge: GradExact, gw: np.ndarray, ghb: np.ndarray, gvb, cplx: bool)
 
 # ---- seeded inputs shared by the host tests (tests/test_rbm_exact.py) and the GPU tests (tests/test_gpu_rbm_exact.py) -----------------
 REGIMES_ANY = ("small", "fe2s2", "alt30", "chunk+50", "chunk-50", "two-200", "one-338", "one-338-w", "spread-45", "novb")
+REGIMES_ELOC = ("cross",)  # (tests/eloc_exact.py: excitations that take theta through zero)
 REGIMES_COMPLEX = ("imb50", "imb1000", "exact-theta")
 REGIMES_GRAD = ("tiny", "sat40")
 
@@ -366,8 +373,15 @@ def regime_params(regime: str, kind: str, sorb: int, H: int, seed: int) -> Rbm:
     without a visible bias; imb50 (complex): Im b = 100 (U - 0.5); imb1000 (complex): six units with Im b = 2000 (U - 0.5) and Re b = +-2;
     exact-theta (complex, H even): W = 0, b in conjugate pairs a_j +- i beta_j with |a_j| in [0.2, 0.6] and beta_j in [500, 4000], a real
     and a multiple of 2^-10: theta_h = b_h, a.x and the sum of the phases carry NO rounding (see amp_bound_exact_theta);
-    tiny: every parameter 1e-8 (U - 0.5); sat40: +40 / -40 alternating on the first 16 units.  The numbers of biased units keep
-    |Re ln psi| below LN_MAX."""
+    tiny: every parameter 1e-8 (U - 0.5); sat40: +40 / -40 alternating on the first 16 units; cross (H >= 3, sorb >= 4): fe2s2 with two
+    hidden units, one of each sign of b, coupled by Re W = +-3 to the four orbitals of cross_orbitals(sorb) = (p0, p1, q0, q1), two of each
+    spin: unit 1 has Re b = +1 and Re W = +3 / -3 on the alpha pair (p0, q0), unit 2 Re b = -1 and Re W = -3 / +3 on the beta pair (p1, q1).
+    A row that occupies p0, p1 and leaves q0, q1 empty has theta = +7 / -7 (plus what the other orbitals add, about +-0.5); the excitation
+    p -> q of that spin takes theta through zero to -5 / +5, where n_h prod q carries the factor and m_h does not; p -> elsewhere or
+    elsewhere -> q stops at +-1.  (A unit coupled to all four would reach -+17, but then psi(x') / psi(x) spans e^-12 ... e^24 within one
+    walker and a tenth of its columns lie below ANY rounding bound on E_loc, which is relative to the largest: each unit keeps to one spin,
+    the ratios to [1e-5, 1], and every column stays visible -- tests/test_eloc_exact.py.)
+    The numbers of biased units keep |Re ln psi| below LN_MAX."""
     g = np.random.default_rng([seed, sorb, H, len(regime)])
     cplx = kind == "complex"
     r = (lambda *s: (g.random(s) - 0.5) + 1j * (g.random(s) - 0.5)) if cplx else (lambda *s: g.random(s) - 0.5)
@@ -411,6 +425,13 @@ def regime_params(regime: str, kind: str, sorb: int, H: int, seed: int) -> Rbm:
     elif regime == "sat40":
         u = np.arange(16)
         set_re(u, np.where(u % 2 == 0, 40.0, -40.0) + g.random(16) - 0.5)
+    elif regime == "cross":
+        assert H >= 3 and sorb >= 4
+        p0, p1, q0, q1 = cross_orbitals(sorb)
+        for h, p, q, sg in ((1, p0, q0, 1.0), (2, p1, q1, -1.0)):
+            W[h, p] = 3.0 * sg + (1j * W[h, p].imag if cplx else 0.0)
+            W[h, q] = -3.0 * sg + (1j * W[h, q].imag if cplx else 0.0)
+        set_re([1, 2], [1.0, -1.0])
     elif regime == "imb50":
         assert cplx
         hb = hb.real + 100j * (g.random(H) - 0.5)
@@ -432,6 +453,17 @@ def forced_orbitals(sorb: int):
             f.append(o)
         o += 1
     return sorted(f)
+
+
+def cross_orbitals(sorb: int):
+    """(p0, p1, q0, q1) of the regime "cross": p0, q0 alpha (even) and p1, q1 beta (odd) orbitals, at the word edges that exist (0, 64,
+    128; 63, 127, the last orbital), filled up with the lowest ones"""
+    assert sorb >= 4
+    alpha = [o for o in (0, 64, 128) if o < sorb]
+    beta = [o for o in (63, 127, sorb - 1 if sorb & 1 == 0 else sorb - 2) if 0 < o < sorb]
+    alpha = (alpha + [o for o in range(2, sorb, 2) if o not in alpha])[:2]
+    beta = (beta + [o for o in range(1, sorb, 2) if o not in beta])[:2]
+    return alpha[0], beta[0], alpha[1], beta[1]
 
 
 def rand_words(n: int, sorb: int, seed: int, fill: float = 0.4) -> np.ndarray:

@@ -1,0 +1,174 @@
+"""The E_loc yardstick of tests/eloc_exact.py itself, on the CPU: its matrix elements column by column against the oracle's, its local
+energies against oracle.eloc_simple_rbm, the variational energy of a complete sorb-8 space against <psi|H|psi> from oracle.hij, its
+incremental theta against rbm_exact.exact_ld on the rows; and, for every case tests/test_gpu_eloc_exact.py lists, the conditions that
+keep a comparison from passing vacuously, from the reference alone: finite normal psi for x and every x', finite E and A_x, bound <= 1e-9
+A_x, at least 0.99 of the columns above the walker's bound on the synthetic integrals (one dropped or sign-flipped column would fail),
+|tanh(a.x)| >= 1e-3, walkers and columns of "cross" whose theta changes sign with |theta|, |theta'| > 3, Lambda such that some walkers
+clamp and some do not with a margin of 1e3 bounds, every sign decision of the Green's rows above its bound, and the form every case takes."""
+import os
+import time
+
+import numpy as np
+import pytest
+
+import eloc_exact as X
+import rbm_exact as R
+import test_gpu_eloc_exact as T
+from conftest import golden, rand_occ, synth_integrals
+
+_CLOCK = {}
+ALL_CASES = T.ELOC_CASES + [T.FORCED_WINDOW_CASE] + T.GREEN_CASES + T.ROUTE_CASES
+
+
+@pytest.fixture(scope="module", autouse=True)
+def _clock():
+    _CLOCK["t0"] = time.time()
+    yield
+
+
+def _oracle_rows(occ, sorb, noA, noB, h1, h2):
+    from oracle import oracle
+
+    bra = oracle.pm01_to_onv(occ, sorb)
+    comb, hm = oracle.comb_hij_fused(bra, h1, h2, sorb, noA + noB, noA, noB)
+    return bra, np.unpackbits(comb, axis=-1, bitorder="little")[..., :sorb], hm
+
+
+@pytest.mark.parametrize("sorb,noA,noB,ints", [(12, 3, 3, "syn"), (12, 2, 4, "syn"), (4, 1, 0, "syn"), (2, 1, 1, "syn"), (66, 3, 4, "syn"),
+                                               (130, 3, 2, "syn"), (40, 15, 15, "fe2s2")])
+def test_matrix_elements_match_the_oracle_column_by_column(sorb, noA, noB, ints):
+    h1, h2 = T.integrals(ints, sorb)
+    occ = rand_occ(2, sorb, noA, noB, seed=3)
+    _, bits, hm = _oracle_rows(occ, sorb, noA, noB, h1, h2)
+    for i in range(2):
+        st = X.structure(occ[i], h1, h2)
+        w = X.walker(R.regime_params("small", "real", sorb, 8, 0), st)
+        perm = X.match_columns(w, bits[i])
+        d = np.abs(st.h[perm] - hm[i, 1:].astype(X.LD)).astype(np.float64)
+        tol = st.t[perm] * X.U * st.a[perm]
+        assert bool((d <= tol).all()), float((d / np.maximum(tol, 1e-300)).max())
+        assert abs(float(st.h0 - X.LD(hm[i, 0]))) <= st.t0 * X.U * st.a0
+        assert st.t0 == (noA + noB) * (noA + noB + 1) // 2 and (not st.t.size or int(st.t.max()) <= max(noA + noB, 1))
+
+
+@pytest.mark.parametrize("sorb,noA,noB,H,regime", [(12, 3, 3, 20, "fe2s2"), (12, 3, 3, 20, "alt30"), (16, 5, 3, 24, "chunk-50"), (12, 3, 3, 20, "cross"),
+                                                   (40, 3, 2, 64, "two-200"), (66, 3, 4, 40, "spread-45"), (12, 3, 3, 20, "one-338-w")])
+def test_local_energy_matches_the_oracle(sorb, noA, noB, H, regime):
+    """oracle.eloc_simple_rbm forms psi(x') / psi(x) from two float64 products: its own error is (sorb + H + 16) u (cond(x) + cond(x')) per
+    column, far above the yardstick's; the agreement asserted is that of the oracle's rounding."""
+    from oracle import oracle
+
+    h1, h2 = synth_integrals(sorb)
+    occ = T.walkers(sorb, noA, noB, 2, regime)
+    rbm = R.regime_params(regime, "real", sorb, H, 0)
+    e, _ = oracle.eloc_simple_rbm(oracle.pm01_to_onv(occ, sorb), h1, h2, sorb, noA + noB, noA, noB, rbm.W, rbm.hb, rbm.vb)
+    for i in range(2):
+        w = X.walker(rbm, X.structure(occ[i], h1, h2))
+        tol = 2 * X.U * (sorb + H + 16) * float(w.psi.cond[0] + 2 * R.hidden_scale(rbm).sum() + 1) * w.A
+        print(sorb, regime, float(w.E.real), e[i], abs(float(w.E.real) - e[i]), tol)
+        if np.isfinite(e[i]):  # (the oracle's products overflow in the saturated regimes; the yardstick does not)
+            assert abs(float(w.E.real - X.LD(e[i]))) <= tol
+        else:
+            assert regime in ("two-200", "one-338-w")
+        # the incremental theta of the yardstick against exact_ld on the rows themselves
+        ex = R.exact_ld(rbm, np.concatenate([occ[i:i + 1], w.st.bits]).astype(np.float64) * 2 - 1)
+        r = np.exp(ex.re[1:] - ex.re[0])
+        assert float(np.abs(r / w.r.real - 1).max()) <= 64 * R.U_LD * (sorb + H + 16) * float(ex.cond.max())
+
+
+def test_variational_energy_of_a_complete_space():
+    """All 36 determinants of c1_sorb8_all36.npz: sum_x |psi_x|^2 E_x / sum |psi|^2 = <psi|H|psi> / <psi|psi> with H from oracle.hij."""
+    from oracle import oracle
+
+    d = golden("c1_sorb8_all36.npz")
+    sorb, noA, noB = int(d["sorb"]), int(d["noA"]), int(d["noB"])
+    onv, occ, h1, h2 = np.ascontiguousarray(d["onv"]), d["occ"], d["h1e"], d["h2e"]
+    assert occ.shape == (36, sorb) and len({r.tobytes() for r in occ}) == 36
+    for kind in ("real", "complex"):
+        rbm = R.regime_params("fe2s2", kind, sorb, 12, 0)
+        ws = [X.walker(rbm, X.structure(o, h1, h2)) for o in occ]
+        psi = R.exact_ld(rbm, occ.astype(np.float64) * 2 - 1).psi()
+        p2 = np.abs(psi) ** 2
+        e_mc = (p2 * np.array([w.E for w in ws], dtype=X.CLD)).sum() / p2.sum()
+        Hm = oracle.hij(onv, onv, h1, h2, sorb, noA + noB).astype(X.LD)
+        e_var = (np.conj(psi) @ (Hm.astype(X.CLD) @ psi)) / p2.sum()
+        scale = float((np.abs(Hm) @ np.abs(psi) * np.abs(psi)).sum() / p2.sum())
+        print(kind, complex(e_mc), complex(e_var), scale)
+        assert abs(complex(e_mc - e_var)) <= 64 * X.U * scale  # (oracle.hij returns float64 matrix elements: t_k u a_k each)
+
+
+def _cols(ws):
+    return sum(w.r.size for w in ws)
+
+
+def test_gpu_cases_are_finite_visible_and_take_the_form_they_name():
+    kinds_reached, regimes_reached, forms, neg_tanh, words = set(), set(), set(), 0, set()
+    for c in ALL_CASES:
+        t0 = time.time()
+        ref = T.reference(c)
+        assert len(ref.walkers) == c.n
+        if c is T.FORCED_WINDOW_CASE:
+            import os
+            os.environ["PYNQS_CRBM_WINDOW"] = T.FORCED_WINDOW
+        try:
+            assert T.form_of(c) == c.form, (T.case_id(c), T.form_of(c))
+        finally:
+            if c is T.FORCED_WINDOW_CASE:
+                del os.environ["PYNQS_CRBM_WINDOW"]
+        forms.add((c.kernel, c.form))
+        kinds_reached.add((c.kernel, c.kind))
+        regimes_reached.add((c.kind if c.kind != "cos" else "complex", c.regime))
+        words.add((c.kernel, (c.sorb - 1) // 64 + 1))
+        vis_cols = tot_cols = 0
+        for w in ref.walkers:
+            b = w.bound()
+            lnx = float(w.psi.re[0])
+            if c.H == 1200:  # psi(x) itself is beyond float64 (the kernels must return inf); the ratios are finite all the same
+                assert lnx >= T.LN_OVERFLOW and np.isfinite(w.rabs).all() and w.rabs.min() > 0
+            else:  # psi(x) and every psi(x') is a finite normal double (LN_MAX but for 400 hidden units with eight at -50: LN_FINITE)
+                assert w.lnmax <= (T.LN_FINITE if (c.H, c.regime) == (400, "chunk-50") else R.LN_MAX), (T.case_id(c), w.lnmax)
+            assert np.isfinite(complex(w.E).real) and np.isfinite(complex(w.E).imag) and np.isfinite(w.A) and np.isfinite(b) and b > 0
+            assert b <= 1e-9 * w.A, (T.case_id(c), b, w.A)
+            vis_cols += int((np.abs(w.hr) > b).sum())
+            tot_cols += w.r.size
+            if c.kind == "tanh":
+                assert abs(w.vis0) >= 1e-3, (T.case_id(c), w.vis0)
+                neg_tanh += int((w.r.real < 0).sum())
+            if c.regime == "cross":
+                assert w.ncross > 0, T.case_id(c)
+            if c.regime == "one-338-w":  # all four forced orbitals fit 3 + 3 electrons: theta = -330 for x, down to -346 with both electrons of a double taken out
+                h3 = 3 if c.H > 3 else 0
+                th = ref.rbm.hb[h3] + (np.concatenate([w.st.occ[None], w.st.bits]).astype(np.float64) * 2 - 1) @ ref.rbm.W[h3]
+                assert float(th[0]) == -330.0 and float(th.min()) == -346.0, (float(th[0]), float(th.min()))
+        share = vis_cols / max(tot_cols, 1)
+        print(f"{T.case_id(c)}: columns {tot_cols}, above the walker's bound {share:.4f}, max bound / A {max(w.bound() / w.A for w in ref.walkers):.3g},"
+              f" {time.time() - t0:.2f} s")
+        if c.ints == "syn" and tot_cols:
+            assert share >= 0.99, (T.case_id(c), share)
+    assert neg_tanh > 0
+    assert forms >= {("rbm", T.R1), ("rbm", T.RC), ("rbm", T.W1), ("rbm", T.WC), ("crbm", T.R1), ("crbm", T.RC), ("crbm", T.W1), ("green", T.R1), ("green", T.W1)}
+    assert kinds_reached >= {("rbm", "real"), ("rbm", "tanh"), ("rbm", "pRBM"), ("crbm", "complex"), ("crbm", "cos"), ("green", "real"), ("green", "tanh")}
+    assert {r for k, r in regimes_reached if k == "real"} >= set(R.REGIMES_ANY + R.REGIMES_ELOC)
+    assert {r for k, r in regimes_reached if k == "complex"} >= {"small", "fe2s2", "alt30", "chunk-50", "imb50", "imb1000", "cross"}
+    for k in ("tanh", "pRBM"):
+        assert {r for kk, r in regimes_reached if kk == k} >= {"small", "alt30", "chunk-50", "cross"}, k
+    assert words >= {("rbm", 1), ("rbm", 2), ("rbm", 3), ("crbm", 1), ("crbm", 2), ("green", 1), ("green", 2)}
+
+
+def test_greens_rows_have_a_margin_on_every_decision():
+    for c in T.GREEN_CASES:
+        ref, lam, rows = T.green_reference(c)
+        clamps = [g.clamp for g in rows]
+        assert any(clamps) and not all(clamps), (T.case_id(c), lam)
+        for w, g in zip(ref.walkers, rows):
+            assert abs(float(g.k0)) >= 1e3 * g.bound[0], (T.case_id(c), float(g.k0), g.bound[0])
+            assert bool(g.sure.all()), (T.case_id(c), int((~g.sure).sum()))
+            assert bool(g.keep[1:].any()) and bool((~g.keep[1:]).any())
+            assert float(abs(complex(w.E).real - float(w.st.h0 + g.v_sf - g.g[1:].sum()))) <= 1e-12 * w.A  # E_loc is unchanged by the construction
+        print(T.case_id(c), "Lambda", lam, "clamped", sum(clamps), "of", len(clamps))
+
+
+def test_zz_run_time():
+    dt = time.time() - _CLOCK["t0"]
+    print(f"tests/test_eloc_exact.py: {dt:.1f} s")
+    assert dt < 60.0
