@@ -116,7 +116,13 @@ int pynqs_comb_hij_fused_plan(const uint64_t *bra, int64_t nbatch, int sorb, int
  * eloc.py:395-396, in one pass.  keys uint64[nkeys][len] sorted as for pynqs_wavefunction_lut; wf is
  * double[nkeys] or interleaved complex double[nkeys][2]; eloc / psi0 have the same element type ([nbatch] or
  * [nbatch][2]).  psi(x') = 0 for x' outside the table; psi0 = psi(x) (0 if x itself is not in the table,
- * eloc is then inf/nan exactly like the reference's division).  The sum is taken as (sum_k H_k psi_k) / psi_0. */
+ * eloc is then inf/nan exactly like the reference's division).  The sum is taken as (sum_k H_k psi_k) / psi_0.
+ * Scale: E_loc is homogeneous of degree 0 in psi, and every entry that divides by psi(x) -- the SAMPLE_SPACE entries below, their flip
+ * passes and pynqs_reduce_contract -- is correct for ANY finite non-zero psi whose sums sum_k H_k psi_k are finite: the complex
+ * division scales numerator and divisor by one power of two first (detcore.h: scaled_cdiv), so |psi(x)|^2 is never formed at the
+ * caller's scale (it would overflow above 2^512 and lose digits below 2^-511).  Multiplying every amplitude by 2^k changes no bit of a
+ * result that is added in a fixed order (the indexed form, the contraction).  psi(x) = 0 and non-finite amplitudes give a non-finite
+ * E_loc, as before. */
 int pynqs_eloc_sample_space(const uint64_t *bra, int64_t nbatch, int sorb, int nele, int noA, int noB,
                             const void *plan, const uint64_t *keys, int64_t nkeys, const double *wf,
                             int wf_is_complex, double *eloc, double *psi0, void *stream);

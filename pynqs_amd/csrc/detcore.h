@@ -160,6 +160,23 @@ __device__ __forceinline__ T two_body(const T *__restrict__ h2e, int i, int j, i
   return neg ? -v : v;
 }
 
+// ---- the local energies' division by psi(x) -----------------------------------------------------------
+// (ar + i ai) / (br + i bi) for amplitudes of any scale.  The textbook form (a conj b) / (br^2 + bi^2) squares the divisor: br^2 + bi^2
+// is inf for |b| above 2^512 (the quotient then nan) and subnormal below 2^-511 (digits lost), magnitudes an unnormalised ansatz reaches
+// (a complex RBM with ~320 hidden units has |psi| ~ 1e157).  Numerator and divisor are first scaled by the same power of two -- exact --
+// that takes the larger part of b to [1/2, 1): the squares then lie in [1/4, 2), and the quotient of a numerator of the divisor's own
+// scale is formed from numbers of order one.  E_loc is homogeneous of degree 0 in psi: it must not depend on the caller's normalisation.
+// b = 0 and non-finite b are left as they are (exponent 0): the result is non-finite as before, like the reference's division.
+__device__ __forceinline__ void scaled_cdiv(double ar, double ai, double br, double bi, double &qr, double &qi) {
+  const double big = fmax(fabs(br), fabs(bi));
+  int e = 0;
+  if (big > 0.0 && big < __builtin_inf()) (void)frexp(big, &e);
+  ar = ldexp(ar, -e); ai = ldexp(ai, -e); br = ldexp(br, -e); bi = ldexp(bi, -e);
+  const double d = br * br + bi * bi;
+  qr = (ar * br + ai * bi) / d;
+  qi = (ai * br - ar * bi) / d;
+}
+
 // ---- sorted-key table (WavefunctionLUT) -----------------------------------------------------------
 // cpu_tensor.cpp:589-637, little-endian branch: keys compare as multi-word integers, most significant
 // word LAST.  Returns the position of q or -1.

@@ -125,9 +125,8 @@ __device__ __forceinline__ void store_walker_sum(double re, double im, double (*
       // may still hold from before)
       if constexpr (CPLX) {
         const double br = __hip_atomic_load(psi0 + 2 * walker, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-        const double bi = __hip_atomic_load(psi0 + 2 * walker + 1, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT), d = br * br + bi * bi;
-        acc[2 * walker] = (sr * br + si * bi) / d;
-        acc[2 * walker + 1] = (si * br - sr * bi) / d;
+        const double bi = __hip_atomic_load(psi0 + 2 * walker + 1, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+        scaled_cdiv(sr, si, br, bi, acc[2 * walker], acc[2 * walker + 1]);
       } else acc[walker] = sr / __hip_atomic_load(psi0 + walker, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
     } else {
       if constexpr (CPLX) { atomicAdd(acc + 2 * walker, sr); atomicAdd(acc + 2 * walker + 1, si); }
@@ -794,10 +793,8 @@ __global__ __launch_bounds__(kBlock) void eloc_divide_kernel(double *__restrict_
   const int64_t i = (int64_t)blockIdx.x * kBlock + threadIdx.x;
   if (i >= n) return;
   if constexpr (CPLX) {
-    const double ar = acc[2 * i], ai = acc[2 * i + 1], br = psi0[2 * i], bi = psi0[2 * i + 1];
-    const double d = br * br + bi * bi;
-    acc[2 * i] = (ar * br + ai * bi) / d;
-    acc[2 * i + 1] = (ai * br - ar * bi) / d;
+    const double ar = acc[2 * i], ai = acc[2 * i + 1];
+    scaled_cdiv(ar, ai, psi0[2 * i], psi0[2 * i + 1], acc[2 * i], acc[2 * i + 1]);
   } else {
     acc[i] = acc[i] / psi0[i];
   }

@@ -456,9 +456,8 @@ __global__ __launch_bounds__(kBlock) void eloc_divide_keys_kernel(double *__rest
   const int64_t i = (int64_t)blockIdx.x * kBlock + threadIdx.x;
   if (i >= n) return;
   if constexpr (CPLX) {
-    const double a = acc[2 * i], b = acc[2 * i + 1], c = psi0[2 * i], d = psi0[2 * i + 1], den = c * c + d * d;
-    acc[2 * i] = (a * c + b * d) / den;
-    acc[2 * i + 1] = (b * c - a * d) / den;
+    const double a = acc[2 * i], b = acc[2 * i + 1];
+    scaled_cdiv(a, b, psi0[2 * i], psi0[2 * i + 1], acc[2 * i], acc[2 * i + 1]);
   } else {
     acc[i] = acc[i] / psi0[i];
   }

@@ -580,9 +580,9 @@ __global__ __launch_bounds__(kBlock) void reduce_contract_kernel(int64_t nbatch,
   if (lane == 0) {
     if (anybad) { ar = ai = __builtin_nan(""); }
     if constexpr (CPLX) {
-      const double dn = xr * xr + xi * xi;
-      eloc[2 * walker] = divide ? (ar * xr + ai * xi) / dn : ar;
-      eloc[2 * walker + 1] = divide ? (ai * xr - ar * xi) / dn : ai;
+      if (divide) scaled_cdiv(ar, ai, xr, xi, ar, ai);
+      eloc[2 * walker] = ar;
+      eloc[2 * walker + 1] = ai;
       psi_x[2 * walker] = xr; psi_x[2 * walker + 1] = xi;
     } else {
       eloc[walker] = divide ? ar / xr : ar;
