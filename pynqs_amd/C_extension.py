@@ -526,7 +526,28 @@ def hash_lookup(ht: HashTable, onv: Tensor) -> Tuple[Tensor, Tensor]:
 _SPIN_FLIP_CALLS = 0
 
 
-class RBMTable:
+class _RBMTableBase:
+    """What RBMTable and CRBMTable share: stage the normalised parameters, size and allocate the table, build it
+    (pynqs_<kind>_table_bytes / _build), and wait for the build whenever it read a copy of the caller's tensors.
+    Attributes: nhidden, sorb, device, buf."""
+
+    def _build(self, kind: str, given, params, nhidden: int, sorb: int) -> None:
+        dev, ts, _ = _stage(*params)
+        self.nhidden, self.sorb, self.device = nhidden, sorb, dev
+        nbytes = getattr(N.lib(), f"pynqs_{kind}_table_bytes")(sorb, nhidden)
+        if nbytes < 0:
+            raise RuntimeError(f"bad RBM sizes: sorb = {sorb}, num_hidden = {nhidden}")
+        self.buf = torch.empty(nbytes // 8, dtype=torch.float64, device=dev)
+        N.check(getattr(N.lib(), f"pynqs_{kind}_table_build")(ts[0].data_ptr(), ts[1].data_ptr(), ts[2].data_ptr() if len(ts) > 2 else None,
+                                                              sorb, nhidden, self.buf.data_ptr(), _stream(dev)), f"{kind}_table_build")
+        if any(a.data_ptr() != b.data_ptr() for a, b in zip(given, ts)):
+            torch.cuda.current_stream(dev).synchronize()  # staging copies must outlive the build kernel
+
+    def data_ptr(self) -> int:
+        return self.buf.data_ptr()
+
+
+class RBMTable(_RBMTableBase):
     """Device-resident re-layout of a real RBM's parameters for the fused SIMPLE local energy
     (include/pynqs_amd.h: pynqs_rbm_table_build; reference amplitude: vmc/ansatz/rbm/rbm.py:186-211).
     weights [num_hidden, sorb], hidden_bias [num_hidden], visible_bias [sorb] or None; float64.
@@ -540,33 +561,22 @@ class RBMTable:
         ts = [weights, hidden_bias] + ([visible_bias] if visible_bias is not None else [])
         if any(t.dtype != torch.float64 for t in ts):
             raise RuntimeError("the fused RBM local energy is float64 only")
-        src = ts
-        dev, ts, _ = _stage(*[t.detach().contiguous() for t in ts])
-        self.nhidden, self.sorb, self.device = int(weights.size(0)), int(weights.size(1)), dev
-        nbytes = N.lib().pynqs_rbm_table_bytes(self.sorb, self.nhidden)
-        if nbytes < 0:
-            raise RuntimeError(f"bad RBM sizes: sorb = {self.sorb}, num_hidden = {self.nhidden}")
-        self.buf = torch.empty(nbytes // 8, dtype=torch.float64, device=dev)
-        N.check(N.lib().pynqs_rbm_table_build(ts[0].data_ptr(), ts[1].data_ptr(), ts[2].data_ptr() if len(ts) > 2 else None,
-                                              self.sorb, self.nhidden, self.buf.data_ptr(), _stream(dev)), "rbm_table_build")
-        if any(a.data_ptr() != b.data_ptr() for a, b in zip(src, ts)):
-            torch.cuda.current_stream(dev).synchronize()  # staging copies must outlive the build kernel
-
-    def data_ptr(self) -> int:
-        return self.buf.data_ptr()
+        self._build("rbm", ts, [t.detach().contiguous() for t in ts], int(weights.size(0)), int(weights.size(1)))
 
 
-RBM_FLAVOURS = {"real": N.RBM_REAL, "tanh": N.RBM_TANH, "pRBM": N.RBM_PHASE}  # rbm_type (rbm.py:199-211) -> include/pynqs_amd.h
+# rbm_type (rbm.py:199-211) -> include/pynqs_amd.h; RBM_FLAVOURS: the ones the real-parameter table and kernel serve
+RBM_TYPE_FLAVOUR = {"real": N.RBM_REAL, "tanh": N.RBM_TANH, "pRBM": N.RBM_PHASE, "complex": N.RBM_COMPLEX}
+RBM_FLAVOURS = {k: v for k, v in RBM_TYPE_FLAVOUR.items() if v != N.RBM_COMPLEX}
 
 
-def eloc_rbm(bra: Tensor, h1e: Tensor, h2e: Tensor, table: RBMTable, sorb: int, nele: int, noA: int, noB: int,
-             want_psi: bool = True, rbm_type: str = "real") -> Tuple[Tensor, "Tensor | None"]:
-    """SIMPLE local energy with the RBM amplitude ratio evaluated on chip (pynqs_eloc_rbm_flavour):
-    (eloc[n], psi(x)[n] or None), float64 for rbm_type "real" / "tanh", complex128 for "pRBM".  Equivalent to
-    vmc/energy/eloc.py:121-203 with ansatz = RBMWavefunction(rbm_type=...)."""
-    _check_onv(bra, "bra", sorb, (2,))
-    if rbm_type not in RBM_FLAVOURS:
-        raise RuntimeError(f"rbm_type {rbm_type!r} has no fused local energy (fused: {sorted(RBM_FLAVOURS)})")
+def _rbm_dtype(rbm_type: str) -> torch.dtype:
+    """dtype of psi and E_loc of a flavour"""
+    return torch.complex128 if rbm_type in ("pRBM", "complex") else torch.float64
+
+
+def _eloc_fused(bra: Tensor, h1e: Tensor, h2e: Tensor, table, sorb: int, want_psi: bool, dtype: torch.dtype, call):
+    """Checks, staging, plan lookup, outputs and CPU round trip of eloc_rbm / eloc_crbm; call(x, n, plan, eloc, psi ptr, stream)
+    is the native call."""
     if table.sorb != sorb:
         raise RuntimeError(f"RBM table was built for sorb = {table.sorb}, not {sorb}")
     if _fdtype(h1e, h2e) != N.PYNQS_F64:
@@ -578,15 +588,25 @@ def eloc_rbm(bra: Tensor, h1e: Tensor, h2e: Tensor, table: RBMTable, sorb: int, 
     if plan.device != dev or table.device != dev:
         raise RuntimeError("bra, integrals and RBM table must be on the same device")
     n = x.size(0)
-    dt = torch.complex128 if rbm_type == "pRBM" else torch.float64
-    eloc = torch.empty(n, dtype=dt, device=dev)
-    psi = torch.empty(n, dtype=dt, device=dev) if want_psi else None
-    N.check(N.lib().pynqs_eloc_rbm_flavour(x.data_ptr(), n, sorb, nele, noA, noB, plan.data_ptr(), table.data_ptr(), table.nhidden,
-                                           RBM_FLAVOURS[rbm_type], eloc.data_ptr(), psi.data_ptr() if want_psi else None, _stream(dev)),
-            "pynqs_eloc_rbm")
+    eloc = torch.empty(n, dtype=dtype, device=dev)
+    psi = torch.empty(n, dtype=dtype, device=dev) if want_psi else None
+    call(x, n, plan, eloc, psi.data_ptr() if want_psi else None, _stream(dev))
     if all_cpu and bra.device.type == "cpu":
         return eloc.cpu(), (psi.cpu() if want_psi else None)
     return eloc, psi
+
+
+def eloc_rbm(bra: Tensor, h1e: Tensor, h2e: Tensor, table: RBMTable, sorb: int, nele: int, noA: int, noB: int,
+             want_psi: bool = True, rbm_type: str = "real") -> Tuple[Tensor, "Tensor | None"]:
+    """SIMPLE local energy with the RBM amplitude ratio evaluated on chip (pynqs_eloc_rbm_flavour):
+    (eloc[n], psi(x)[n] or None), float64 for rbm_type "real" / "tanh", complex128 for "pRBM".  Equivalent to
+    vmc/energy/eloc.py:121-203 with ansatz = RBMWavefunction(rbm_type=...)."""
+    _check_onv(bra, "bra", sorb, (2,))
+    if rbm_type not in RBM_FLAVOURS:
+        raise RuntimeError(f"rbm_type {rbm_type!r} has no fused local energy (fused: {sorted(RBM_FLAVOURS)})")
+    return _eloc_fused(bra, h1e, h2e, table, sorb, want_psi, _rbm_dtype(rbm_type), lambda x, n, plan, eloc, psi, st: N.check(
+        N.lib().pynqs_eloc_rbm_flavour(x.data_ptr(), n, sorb, nele, noA, noB, plan.data_ptr(), table.data_ptr(), table.nhidden,
+                                       RBM_FLAVOURS[rbm_type], eloc.data_ptr(), psi, st), "pynqs_eloc_rbm"))
 
 
 def rbm_forward(onv: Tensor, weights: Tensor, hidden_bias: Tensor, visible_bias: "Tensor | None", sorb: int, rbm_type: str = "real") -> Tensor:
@@ -594,29 +614,20 @@ def rbm_forward(onv: Tensor, weights: Tensor, hidden_bias: Tensor, visible_bias:
     (pynqs_rbm_forward): onv uint8[n, 8 len] -> psi float64[n] (rbm_type "real" / "tanh") or complex128[n] ("pRBM"; "complex" with
     weights [H, sorb, 2], hidden_bias [H, 2], visible_bias [sorb, 2] as (re, im) pairs: the reference's params_* layout)."""
     _check_onv(onv, "onv", sorb, (2,))
-    flav = {"real": N.RBM_REAL, "tanh": N.RBM_TANH, "pRBM": N.RBM_PHASE, "complex": N.RBM_COMPLEX}.get(rbm_type)
-    if flav is None:
-        raise RuntimeError(f"rbm_type {rbm_type!r} has no fused forward")
-    cplx_par = rbm_type == "complex"
-    W = weights.detach().double().contiguous()
-    hb = hidden_bias.detach().double().contiguous()
-    vb = visible_bias.detach().double().contiguous() if visible_bias is not None else None
-    H = W.size(0)
-    if W.shape[:2] != (H, sorb) or W.dim() != (3 if cplx_par else 2) or hb.numel() != H * (2 if cplx_par else 1) or \
-            (vb is not None and vb.numel() != sorb * (2 if cplx_par else 1)):
-        raise RuntimeError("RBM parameter shapes do not match sorb / num_hidden")
+    flav, W, hb, vb, H = _rbm_params(weights, hidden_bias, visible_bias, sorb, rbm_type, on_gpu=False)
     if not (onv.is_cuda and W.is_cuda and hb.is_cuda and (vb is None or vb.is_cuda)):
         raise RuntimeError("rbm_forward: determinants and parameters must be on the GPU")
     n = onv.size(0)
-    out_c = rbm_type in ("pRBM", "complex")
-    psi = torch.empty(n, dtype=torch.complex128 if out_c else torch.float64, device=onv.device)
+    psi = torch.empty(n, dtype=_rbm_dtype(rbm_type), device=onv.device)
     N.check(N.lib().pynqs_rbm_forward(onv.data_ptr(), n, sorb, W.data_ptr(), hb.data_ptr(), vb.data_ptr() if vb is not None else None, H, flav,
                                       psi.data_ptr(), _stream(onv.device)), "pynqs_rbm_forward")
     return psi
 
 
-def _rbm_params(weights, hidden_bias, visible_bias, sorb, rbm_type):
-    flav = {"real": N.RBM_REAL, "tanh": N.RBM_TANH, "pRBM": N.RBM_PHASE, "complex": N.RBM_COMPLEX}.get(rbm_type)
+def _rbm_params(weights, hidden_bias, visible_bias, sorb, rbm_type, on_gpu=True):
+    """(flavour, W, hidden bias, visible bias or None, num_hidden): detached contiguous float64 parameters with checked shapes;
+    on_gpu: they must be on the GPU (a caller with a requirement and message of its own passes False)"""
+    flav = RBM_TYPE_FLAVOUR.get(rbm_type)
     if flav is None:
         raise RuntimeError(f"rbm_type {rbm_type!r} has no fused forward")
     cplx_par = rbm_type == "complex"
@@ -627,13 +638,13 @@ def _rbm_params(weights, hidden_bias, visible_bias, sorb, rbm_type):
     if W.shape[:2] != (H, sorb) or W.dim() != (3 if cplx_par else 2) or hb.numel() != H * (2 if cplx_par else 1) or \
             (vb is not None and vb.numel() != sorb * (2 if cplx_par else 1)):
         raise RuntimeError("RBM parameter shapes do not match sorb / num_hidden")
-    if not (W.is_cuda and hb.is_cuda and (vb is None or vb.is_cuda)):
+    if on_gpu and not (W.is_cuda and hb.is_cuda and (vb is None or vb.is_cuda)):
         raise RuntimeError("RBM parameters must be on the GPU")
     return flav, W, hb, vb, H
 
 
 def rbm_forward_children_supported(sorb: int, num_hidden: int, rbm_type: str = "real") -> bool:
-    flav = {"real": N.RBM_REAL, "tanh": N.RBM_TANH, "pRBM": N.RBM_PHASE, "complex": N.RBM_COMPLEX}.get(rbm_type)
+    flav = RBM_TYPE_FLAVOUR.get(rbm_type)
     return flav is not None and bool(N.lib().pynqs_rbm_forward_children_supported(sorb, num_hidden, flav))
 
 
@@ -657,15 +668,14 @@ def rbm_forward_children(onv: Tensor, parent: Tensor, walkers: Tensor, weights: 
     wk = walkers.contiguous()
     N.check(N.lib().pynqs_rbm_children_prepare(wk.data_ptr(), nw, sorb, W.data_ptr(), hb.data_ptr(), vb.data_ptr() if vb is not None else None,
                                                H, flav, table.data_ptr(), st), "pynqs_rbm_children_prepare")
-    out_c = rbm_type in ("pRBM", "complex")
-    psi = out if out is not None else torch.empty(n, dtype=torch.complex128 if out_c else torch.float64, device=dev)
+    psi = out if out is not None else torch.empty(n, dtype=_rbm_dtype(rbm_type), device=dev)
     N.check(N.lib().pynqs_rbm_forward_children(onv.contiguous().data_ptr(), n, count.data_ptr() if count is not None else None, parent.data_ptr(),
                                                wk.data_ptr(), nw, table.data_ptr(), sorb, W.data_ptr(), hb.data_ptr(),
                                                vb.data_ptr() if vb is not None else None, H, flav, psi.data_ptr(), st), "pynqs_rbm_forward_children")
     return psi
 
 
-class CRBMTable:
+class CRBMTable(_RBMTableBase):
     """Device-resident re-layout of an RBM with COMPLEX parameters for the fused SIMPLE local energy (pynqs_crbm_table_build;
     rbm.py:199-211, rbm_type "complex").  weights [num_hidden, sorb], hidden_bias [num_hidden], visible_bias [sorb] or None:
     complex128 tensors, or float64 tensors with a trailing (re, im) axis (the reference's params_* layout)."""
@@ -683,22 +693,8 @@ class CRBMTable:
         vb = as_pairs(visible_bias).reshape(-1, 2) if visible_bias is not None else None
         if w.dim() != 3 or hb.size(0) != w.size(0) or (vb is not None and vb.size(0) != w.size(1)):
             raise RuntimeError("weights must be [num_hidden, sorb], hidden_bias [num_hidden], visible_bias [sorb]")
-        ts = [w, hb] + ([vb] if vb is not None else [])
-        dev, st, _ = _stage(*ts)
-        self.nhidden, self.sorb, self.device = int(w.size(0)), int(w.size(1)), dev
-        nbytes = N.lib().pynqs_crbm_table_bytes(self.sorb, self.nhidden)
-        if nbytes < 0:
-            raise RuntimeError(f"bad RBM sizes: sorb = {self.sorb}, num_hidden = {self.nhidden}")
-        self.buf = torch.empty(nbytes // 8, dtype=torch.float64, device=dev)
-        N.check(N.lib().pynqs_crbm_table_build(st[0].data_ptr(), st[1].data_ptr(), st[2].data_ptr() if len(st) > 2 else None,
-                                               self.sorb, self.nhidden, self.buf.data_ptr(), _stream(dev)), "crbm_table_build")
-        if any(a.device != dev for a in ts):
-            torch.cuda.current_stream(dev).synchronize()  # staging copies of host parameters must outlive the build kernel
-        # (device-side temporaries -- contiguous / view_as_real copies -- are freed in stream order: the caching allocator hands their
-        # memory only to later work on the same stream)
-
-    def data_ptr(self) -> int:
-        return self.buf.data_ptr()
+        given = [weights, hidden_bias] + ([visible_bias] if visible_bias is not None else [])
+        self._build("crbm", given, [w, hb] + ([vb] if vb is not None else []), int(w.size(0)), int(w.size(1)))
 
 
 def eloc_crbm(bra: Tensor, h1e: Tensor, h2e: Tensor, table: CRBMTable, sorb: int, nele: int, noA: int, noB: int,
@@ -706,24 +702,9 @@ def eloc_crbm(bra: Tensor, h1e: Tensor, h2e: Tensor, table: CRBMTable, sorb: int
     """SIMPLE local energy with the amplitude ratio of a complex-parameter RBM evaluated on chip (pynqs_eloc_crbm):
     (eloc complex128[n], psi(x) exp(-log_scale) complex128[n] or None)."""
     _check_onv(bra, "bra", sorb, (2,))
-    if table.sorb != sorb:
-        raise RuntimeError(f"RBM table was built for sorb = {table.sorb}, not {sorb}")
-    if _fdtype(h1e, h2e) != N.PYNQS_F64:
-        raise RuntimeError("the fused RBM local energy is float64 only")
-    plan = plan_for(h1e, h2e, sorb, bra.device)
-    if plan is None:
-        raise RuntimeError("the fused RBM local energy needs an even sorb")
-    dev, (x,), all_cpu = _stage(bra)
-    if plan.device != dev or table.device != dev:
-        raise RuntimeError("bra, integrals and RBM table must be on the same device")
-    n = x.size(0)
-    eloc = torch.empty(n, dtype=torch.complex128, device=dev)
-    psi = torch.empty(n, dtype=torch.complex128, device=dev) if want_psi else None
-    N.check(N.lib().pynqs_eloc_crbm(x.data_ptr(), n, sorb, nele, noA, noB, plan.data_ptr(), table.data_ptr(), table.nhidden, float(log_scale),
-                                    eloc.data_ptr(), psi.data_ptr() if want_psi else None, _stream(dev)), "pynqs_eloc_crbm")
-    if all_cpu and bra.device.type == "cpu":
-        return eloc.cpu(), (psi.cpu() if want_psi else None)
-    return eloc, psi
+    return _eloc_fused(bra, h1e, h2e, table, sorb, want_psi, torch.complex128, lambda x, n, plan, eloc, psi, st: N.check(
+        N.lib().pynqs_eloc_crbm(x.data_ptr(), n, sorb, nele, noA, noB, plan.data_ptr(), table.data_ptr(), table.nhidden, float(log_scale),
+                                eloc.data_ptr(), psi, st), "pynqs_eloc_crbm"))
 
 
 # ---- two ansatz-side helpers of the reference module (outside the local-energy path; SURVEY.md 2.2) so that its autoregressive

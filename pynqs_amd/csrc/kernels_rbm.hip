@@ -17,6 +17,8 @@
 // excitation table x 4 entries of its "slow" table (hole pairs x particle pairs, alpha singles x beta singles:
 // detcore.h) -- and runs over the hidden units with 16 running products in registers:
 //   per hidden unit and lane: 16 LDS reads, 8 multiplications for the 8 pair products, 16 x (fma + mul).
+// The cut into blocks and tiles, phase A's diagonal and singles, the sums over waves, the tail of the LDS layout and the host-side
+// launch rules are shared with the complex-parameter kernel (kernels_rbm_complex.hip): rbm_tiles.h.
 // The kernel is bound by the f64 vector rate (84 % busy), not by HBM.  When sorb x
 // num_hidden does not fit the LDS the WINDOWED variant streams q' through it (see eloc_rbm_kernel).
 // Matrix elements come from the integral plan exactly as in kernels_plan.hip.
@@ -34,11 +36,9 @@
 // h_k r_k < 0 (the reference's cos(phase difference + gamma) < 0) and then has weight g_k = -h_k r_k; the others add to the
 // sign-flip potential v_sf = sum h_k r_k on the diagonal: g_0 = max(0, Lambda - h_0 - v_sf).  The row is written in the
 // reference's column order (column = 1 + rank, excitation.cpp:43-109 incl. the `idx % noAA` rotation); E_loc is unchanged.
-#include "detcore.h"
-#include "launch.h"
-#include "plan.h"
-#include "plan_dev.h"
 #include "rbm.h"
+#include "rbm_math.h"
+#include "rbm_tiles.h"
 
 namespace pynqs {
 
@@ -58,29 +58,8 @@ __global__ __launch_bounds__(kBlock) void rbm_table_kernel(const double *__restr
   if (i < rl.total - rl.offVb) tab[rl.offVb + i] = (vb && i < rl.sorb) ? vb[i] : 0.0;
 }
 
-// How the excitations of one walker are cut into 4 x 4 blocks: class k has nbf[k] x nbs[k] blocks
-// (k = 0 singles x nothing, 1 alpha-alpha, 2 beta-beta, 3 alpha-beta); b[k] = cumulative block counts.
-struct RbmBlocks {
-  uint32_t nbf[4];
-  uint32_t b[4];
-  uint32_t ntiles;  // tiles of 64 blocks
-  MagicDiv dv[4];   // division by nbf[k]
-};
-
-static inline RbmBlocks make_rbm_blocks(const SDParams &p) {
-  RbmBlocks B;
-  const uint32_t nf[4] = {p.d1, (uint32_t)p.noAA, (uint32_t)p.noBB, (uint32_t)p.nSa};
-  const uint32_t ns[4] = {p.d1 ? 1u : 0u, (uint32_t)p.nvAA, (uint32_t)p.nvBB, (uint32_t)p.nSb};
-  uint32_t acc = 0;
-  for (int k = 0; k < 4; ++k) {
-    B.nbf[k] = (nf[k] + 3) / 4;
-    B.dv[k] = make_magic(B.nbf[k]);
-    acc += B.nbf[k] * ((ns[k] + 3) / 4);
-    B.b[k] = acc;
-  }
-  B.ntiles = (acc + 63) / 64;
-  return B;
-}
+constexpr int kRbmFB = 4;   // a lane owns 4 x 4 excitations (rbm_tiles.h)
+constexpr int kRbmRed = 1;  // doubles per wave in the LDS trailer
 
 // LDS after the walker tables (16-byte aligned): [q / staging][mn][sh][Cq][hs]
 //   q   [sorb + 1][hw+1] row r(o) = o/2 for alpha, sorb/2 + o/2 for beta orbitals (a wave mostly reads rows of one
@@ -90,14 +69,14 @@ static inline RbmBlocks make_rbm_blocks(const SDParams &p) {
 //   sh  [Hq]            s_h
 //   Cq  [sorb + 2]      C(o) by orbital, 1 for the dummy orbital `sorb`
 //   hs  [d1 + 2]        <x|H|x>, then the singles
+// then rowaddr and the trailer (rbm_tiles.h)
+__device__ __forceinline__ uint32_t rbm_row(uint32_t o, uint32_t K) { return (o >> 1) + ((o & 1u) ? K : 0u); }
 typedef __attribute__((address_space(3))) const double lds_cdouble;  // read through a 32-bit LDS address
 
 struct RbmLds {
   double *q, *mn, *sh, *Cq, *Aq, *hs;  // Aq [sorb + 2]: exp(-4 x_o a_o) (tanh flavour: exp(2 a.x') = exp(2 a.x) prod over the flipped orbitals)
   uint32_t *rowaddr;  // [sorb + 2]: LDS byte address of an orbital's q row (the dummy's at index sorb)
 };
-
-__host__ __device__ inline size_t rbm_q_offset(const SDParams &p) { return (lds_fixed_bytes(p) + 15) & ~(size_t)15; }
 
 // `hw` = hidden units resident in LDS at a time: rl.Hloop (all of them, the fast kernel) or a multiple of 8 (the
 // windowed kernel for sorb x num_hidden beyond the LDS); row stride hw + 1 doubles (odd: see rbm.h)
@@ -107,10 +86,8 @@ __host__ __device__ inline size_t rbm_region_bytes(const SDParams &p, uint32_t h
 
 __host__ __device__ inline size_t lds_bytes_rbm(const SDParams &p, const RbmLayout &rl, uint32_t hw) {
   return rbm_q_offset(p) + rbm_region_bytes(p, hw) +
-         8 * (3 * (size_t)rl.Hq + 2 * (size_t)(p.sorb + 2) + (size_t)(p.d1 + 2)) + 4 * (((size_t)p.sorb + 2 + 3) & ~(size_t)3) + 144;  // + red (up to 16 waves), counters
+         8 * (3 * (size_t)rl.Hq + 2 * (size_t)(p.sorb + 2) + (size_t)(p.d1 + 2)) + 4 * (((size_t)p.sorb + 2 + 3) & ~(size_t)3) + rbm_trailer_bytes(kRbmRed);
 }
-
-__device__ __forceinline__ uint32_t rbm_row(uint32_t o, uint32_t K) { return (o >> 1) + ((o & 1u) ? K : 0u); }
 
 // WINDOWED = false: all hidden units of q' live in LDS, waves pull tiles from a counter (the fast kernel).
 // WINDOWED = true : sorb x num_hidden does not fit: the workgroup streams q' through LDS `hw` hidden units at a time;
@@ -118,28 +95,9 @@ __device__ __forceinline__ uint32_t rbm_row(uint32_t o, uint32_t K) { return (o 
 //                   windows (two barriers per window).
 enum : int { kRbmReal = 0, kRbmTanh = 1, kRbmPhase = 2 };
 
-// sin and cos of a moderate argument (|x| < 1e5: here the logarithm of an amplitude ratio) without the library's large-argument
-// path, whose code and registers the 16-column epilogue of the phase flavour pays for on every call: x = k pi/2 + r by two fmas
-// (pi/2 split in two doubles), then the fdlibm kernels on |r| <= pi/4 (errors < 1 ulp of the result for these magnitudes).
-__device__ __forceinline__ void sincos_moderate(double x, double &sn, double &cs) {
-  const double k = rint(x * 0.63661977236758134308);  // 2 / pi
-  double r = fma(-k, 1.57079632679489655800e+00, x);
-  r = fma(-k, 6.12323399573676603587e-17, r);
-  const double z = r * r;
-  const double ps = fma(z, fma(z, fma(z, fma(z, fma(z, 1.58969099521155010221e-10, -2.50507602534068634195e-08), 2.75573137070700676789e-06),
-                                     -1.98412698298579493134e-04), 8.33333333332248946124e-03), -1.66666666666666324348e-01);
-  const double pc = fma(z, fma(z, fma(z, fma(z, fma(z, -1.13596475577881948265e-11, 2.08757232129817482790e-09), -2.75573143513906633035e-07),
-                                     2.48015872894767294178e-05), -1.38888888888741095749e-03), 4.16666666666666019037e-02);
-  const double s0 = fma(r * z, ps, r), c0 = fma(z * z, pc, fma(-0.5, z, 1.0));
-  const int q = (int)k;
-  const double a = (q & 1) ? c0 : s0, b = (q & 1) ? s0 : c0;
-  sn = (q & 2) ? -a : a;
-  cs = ((q + 1) & 2) ? -b : b;
-}
-
 template <int LEN, bool WINDOWED, int FLAVOUR, bool GREEN>
 __global__ __launch_bounds__(1024, 4) void eloc_rbm_kernel(const uint64_t *__restrict__ bra, SDParams p, PlanLayout pl, RbmLayout rl,
-                                                          RbmBlocks B, uint32_t nchunks, uint32_t hw, const double *__restrict__ plan,
+                                                          RbmBlocks<kRbmFB> B, uint32_t nchunks, uint32_t hw, const double *__restrict__ plan,
                                                           const double *__restrict__ rbm, double *__restrict__ eloc,
                                                           double *__restrict__ psi, double lambda, double *__restrict__ green,
                                                           uint8_t *__restrict__ clamped) {
@@ -147,15 +105,13 @@ __global__ __launch_bounds__(1024, 4) void eloc_rbm_kernel(const uint64_t *__res
   // no static __shared__ here: with the dynamic region at LDS address 0 the row offsets below are the addresses and
   // the ds_read immediates carry the rest (a static in front costs one v_add per read)
   extern __shared__ __attribute__((aligned(16))) unsigned char smem[];
-  double *red = reinterpret_cast<double *>(smem + lds_bytes_rbm(p, rl, hw) - 144);  // [16]: one per wave
-  uint32_t *next_tile_p = reinterpret_cast<uint32_t *>(red + 16);
-  uint32_t *next_single_p = next_tile_p + 1;
+  const RbmTrailer T = rbm_trailer(smem, lds_bytes_rbm(p, rl, hw), kRbmRed);
   const uint64_t wg = blockIdx.x;
   const uint64_t walker = wg / nchunks;
   const uint32_t chunk = (uint32_t)(wg - walker * nchunks);
   const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
   const int nthreads = blockDim.x, nwaves = nthreads >> 6;  // 3 or 4 waves: whichever divides the walker's tiles better
-  if (tid == 0) { *next_tile_p = 0; *next_single_p = 0; }
+  if (tid == 0) { *T.next_tile = 0; *T.next_single = 0; }
   Walker<LEN> wk;
   load_walker<LEN>(bra + walker * LEN, wk);
   const LdsLayout L = carve_lds(smem, p);
@@ -182,16 +138,12 @@ __global__ __launch_bounds__(1024, 4) void eloc_rbm_kernel(const uint64_t *__res
   //   last wave  : <x|H|x> (ordered sum of nele(nele+1)/2 terms by one lane: the longest serial job)
   //   other waves: theta_h -> m_h, n_h, s_h (and ln psi(x)), then the singles' matrix elements in tiles of 16
   // The singles / diagonal are staged in wave-private quarters of the region q will occupy afterwards.
-  const uint32_t tS = (B.b[0] + 63) / 64;
-  const bool need_hs = chunk < max(tS, 1u);
+  const bool need_hs = rbm_needs_hs(B, chunk);
   const double *__restrict__ Wt = rbm + rl.offWt;
   double lnpsi = 0.0;
   const int kThetaThreads = nthreads - 64;
   if (wave == nwaves - 1) {
-    if (need_hs) {
-      const double hii = fast_diag<double>(p, pl, L, plan);
-      if (lane == 0) R.hs[0] = hii;
-    }
+    rbm_diagonal(need_hs, lane, p, pl, L, plan, R.hs);
   } else {
     for (int h = tid; h < Hq; h += kThetaThreads) {
       double m = 1.0, n = 0.0, s = 1.0;
@@ -211,16 +163,7 @@ __global__ __launch_bounds__(1024, 4) void eloc_rbm_kernel(const uint64_t *__res
       R.mn[h] = m; R.mn[Hq + h] = n; R.sh[h] = s;
     }
   }
-  if (need_hs) {  // every wave, as it becomes free: 64 singles per pass
-    const uint32_t nst = (p.d1 + 63) / 64;
-    for (;;) {
-      uint32_t t = 0;
-      if (lane == 0) t = atomicAdd(next_single_p, 1u);
-      t = __builtin_amdgcn_readfirstlane(t);
-      if (t >= nst) break;
-      if (t * 64 + lane < p.d1) R.hs[1 + t * 64 + lane] = fast_single<double>(t * 64 + lane, p, pl, L, nocc, plan);
-    }
-  }
+  rbm_singles(need_hs, lane, p, pl, L, nocc, plan, R.hs, T.next_single);  // every wave, as it becomes free
   __syncthreads();
 #if defined(PYNQS_RBM_STOP) && PYNQS_RBM_STOP == 2
   if (tid == 0) eloc[walker] = R.hs[0];
@@ -362,7 +305,7 @@ __global__ __launch_bounds__(1024, 4) void eloc_rbm_kernel(const uint64_t *__res
       }
     } else {
       double sn, cs;
-      sincos_moderate(log(ok ? t : 1.0), sn, cs);
+      sincos_mod(log(ok ? t : 1.0), sn, cs);
       esum += (ok ? h : 0.0) * cs;
       esum_im += (ok ? h : 0.0) * sn;
     }
@@ -373,7 +316,7 @@ __global__ __launch_bounds__(1024, 4) void eloc_rbm_kernel(const uint64_t *__res
       if (round >= nrounds) break;       // workgroup-uniform: the windows below contain barriers
       lt = round * nwaves + wave;        // >= my_tiles: a wave without a tile still helps to build the windows
     } else {
-      if (lane == 0) lt = atomicAdd(next_tile_p, 1u);
+      if (lane == 0) lt = atomicAdd(T.next_tile, 1u);
       lt = __builtin_amdgcn_readfirstlane(lt);
       if (lt >= my_tiles) break;
     }
@@ -515,8 +458,10 @@ __global__ __launch_bounds__(1024, 4) void eloc_rbm_kernel(const uint64_t *__res
         if constexpr (FLAVOUR == kRbmPhase) {
 #pragma unroll
           for (int k = 0; k < 16; ++k) {
+            // (not the library's sincos: its large-argument path costs code and registers on each of the 16 columns, and the
+            // argument, the logarithm of an amplitude ratio, is moderate: |x| < 1e5)
             double sn, cs;
-            sincos_moderate(acc[k], sn, cs);
+            sincos_mod(acc[k], sn, cs);
             esum += hv[k] * cs;
             esum_im += hv[k] * sn;
           }
@@ -525,7 +470,7 @@ __global__ __launch_bounds__(1024, 4) void eloc_rbm_kernel(const uint64_t *__res
     }
   }
   if (chunk == 0 && tid == 0) esum += R.hs[0];  // x' = x
-  // fixed-order reductions: lanes, then waves.  kRbmPhase: eloc / psi hold (re, im) pairs
+  // fixed-order reductions: lanes, then waves (rbm_over_waves: valid in thread 0).  kRbmPhase: eloc / psi hold (re, im) pairs
   constexpr int kOut = FLAVOUR == kRbmPhase ? 2 : 1;
 #pragma unroll
   for (int o = 32; o > 0; o >>= 1) {
@@ -533,22 +478,13 @@ __global__ __launch_bounds__(1024, 4) void eloc_rbm_kernel(const uint64_t *__res
     lnpsi += __shfl_xor(lnpsi, o);
     if constexpr (FLAVOUR == kRbmPhase || GREEN) esum_im += __shfl_xor(esum_im, o);
   }
-  auto over_waves = [&](double v) {  // workgroup-uniform calls; the sum is valid in thread 0
-    __syncthreads();
-    if (lane == 0) red[wave] = v;
-    __syncthreads();
-    double s = 0.0;
-    if (tid == 0)
-      for (int w = 0; w < nwaves; ++w) s += red[w];
-    return s;
-  };
-  const double e_re = over_waves(esum);
+  const double e_re = rbm_over_waves(esum, T.red, tid, nwaves);
   if (tid == 0) {
     if (nchunks == 1) eloc[kOut * walker] = e_re;
     else atomicAdd(eloc + kOut * walker, e_re);
   }
   if constexpr (GREEN) {  // (launched with one workgroup per walker)
-    const double v_sf = over_waves(esum_im);
+    const double v_sf = rbm_over_waves(esum_im, T.red, tid, nwaves);
     if (tid == 0) {
       const double k0 = lambda - (R.hs[0] + v_sf);
       grow[0] = k0 < 0.0 ? 0.0 : k0;
@@ -556,14 +492,14 @@ __global__ __launch_bounds__(1024, 4) void eloc_rbm_kernel(const uint64_t *__res
     }
   }
   if constexpr (FLAVOUR == kRbmPhase) {
-    const double e_im = over_waves(esum_im);
+    const double e_im = rbm_over_waves(esum_im, T.red, tid, nwaves);
     if (tid == 0) {
       if (nchunks == 1) eloc[2 * walker + 1] = e_im;
       else atomicAdd(eloc + 2 * walker + 1, e_im);
     }
   }
   if (psi != nullptr && chunk == 0) {  // workgroup-uniform
-    const double s = over_waves(lnpsi);
+    const double s = rbm_over_waves(lnpsi, T.red, tid, nwaves);
     if (tid == 0) {
       if constexpr (FLAVOUR == kRbmReal) psi[walker] = exp(s);
       else if constexpr (FLAVOUR == kRbmTanh) psi[walker] = tanh(ax) * exp(s);
@@ -577,7 +513,10 @@ __global__ __launch_bounds__(1024, 4) void eloc_rbm_kernel(const uint64_t *__res
 // =================================================================================================
 using namespace pynqs;
 
-static constexpr size_t kRbmMaxLds = 158 * 1024;  // of the CU's 160 KiB
+static int rbm_block_env() {  // PYNQS_RBM_BLOCK, read once
+  static const int blk_env = getenv("PYNQS_RBM_BLOCK") ? atoi(getenv("PYNQS_RBM_BLOCK")) : 0;
+  return blk_env;
+}
 
 // Shape of the windowed kernel (sorb x num_hidden does not fit in LDS), by the number of tiles a walker's row has:
 // many tiles -> ONE workgroup of 1024 threads per CU around a 136 KiB window (16 waves share it, half as many windows
@@ -589,7 +528,7 @@ struct RbmShape {
   size_t window_lds;
 };
 static RbmShape rbm_windowed_shape(uint32_t ntiles) {
-  static const int blk_env = getenv("PYNQS_RBM_BLOCK") ? atoi(getenv("PYNQS_RBM_BLOCK")) : 0;
+  const int blk_env = rbm_block_env();
   static const int win_env = getenv("PYNQS_RBM_WINDOW_KB") ? atoi(getenv("PYNQS_RBM_WINDOW_KB")) : 0;
   RbmShape s;
   s.threads = (blk_env == 256 || blk_env == 512 || blk_env == 1024) ? (uint32_t)blk_env : (ntiles >= 64 ? 1024u : (ntiles >= 24 ? 512u : 256u));
@@ -608,33 +547,25 @@ static uint32_t rbm_window(const SDParams &p, const RbmLayout &rl, size_t window
   return 0;
 }
 
-// The form a launch takes: workgroups per walker (few walkers: a walker's tiles are cut over several workgroups, each of which
-// repeats the per-walker set-up and adds its part with an atomic), the windowed kernel's shape, the hidden units resident in LDS.
+// The form a launch takes: workgroups per walker (rbm_chunks), the windowed kernel's shape, the hidden units resident in LDS.
 struct RbmForm {
   uint32_t nchunks, hw;
   RbmShape shape;
 };
-static RbmForm rbm_form(const SDParams &p, const RbmLayout &rl, const RbmBlocks &B, int64_t nbatch, bool green) {
+static RbmForm rbm_form(const SDParams &p, const RbmLayout &rl, const RbmBlocks<kRbmFB> &B, int64_t nbatch, bool green) {
   RbmForm f;
-  f.nchunks = 1;
-  if (nbatch < 1024 && !green) {  // (the Green's-function row finishes its diagonal in the kernel: one workgroup per walker)
-    f.nchunks = (uint32_t)((1024 + nbatch - 1) / nbatch);
-    const uint32_t maxc = B.ntiles / 4 > 0 ? B.ntiles / 4 : 1;
-    if (f.nchunks > maxc) f.nchunks = maxc;
-  }
+  f.nchunks = green ? 1 : rbm_chunks(B.ntiles, nbatch);  // (the Green's-function row finishes its diagonal in the kernel: one workgroup per walker)
   f.shape = rbm_windowed_shape(B.ntiles / f.nchunks);
   f.hw = rbm_window(p, rl, f.shape.window_lds);
   return f;
 }
 
 extern "C" int pynqs_eloc_rbm_form(int64_t nbatch, int sorb, int nele, int noA, int noB, int nhidden, int green) {
-  SDParams p;
-  PlanLayout pl;
-  RbmLayout rl;
-  if (nbatch < 1 || !make_sd_params(sorb, nele, noA, noB, &p) || !make_plan_layout(sorb, &pl) || !make_rbm_layout(sorb, nhidden, &rl)) return -1;
-  const RbmForm f = rbm_form(p, rl, make_rbm_blocks(p), nbatch, green != 0);
+  RbmSystem<RbmLayout> s;
+  if (nbatch < 1 || rbm_system(sorb, nele, noA, noB, nhidden, make_rbm_layout, &s)) return -1;
+  const RbmForm f = rbm_form(s.p, s.rl, make_rbm_blocks<kRbmFB>(s.p), nbatch, green != 0);
   if (f.hw == 0) return -1;
-  return (f.hw < (uint32_t)rl.Hloop ? 1 : 0) | (f.nchunks > 1 ? 2 : 0);
+  return (f.hw < (uint32_t)s.rl.Hloop ? 1 : 0) | (f.nchunks > 1 ? 2 : 0);
 }
 
 extern "C" int64_t pynqs_rbm_table_bytes(int sorb, int nhidden) {
@@ -644,11 +575,9 @@ extern "C" int64_t pynqs_rbm_table_bytes(int sorb, int nhidden) {
 }
 
 extern "C" int pynqs_eloc_rbm_supported(int sorb, int nele, int noA, int noB, int nhidden) {
-  SDParams p;
-  PlanLayout pl;
-  RbmLayout rl;
-  if (!make_sd_params(sorb, nele, noA, noB, &p) || !make_plan_layout(sorb, &pl) || !make_rbm_layout(sorb, nhidden, &rl)) return 0;
-  return rbm_window(p, rl, kRbmMaxLds) > 0 ? 1 : 0;
+  RbmSystem<RbmLayout> s;
+  if (rbm_system(sorb, nele, noA, noB, nhidden, make_rbm_layout, &s)) return 0;
+  return rbm_window(s.p, s.rl, kRbmMaxLds) > 0 ? 1 : 0;
 }
 
 extern "C" int pynqs_rbm_table_build(const double *weights, const double *hidden_bias, const double *visible_bias, int sorb,
@@ -670,54 +599,28 @@ static int eloc_rbm_impl(const uint64_t *bra, int64_t nbatch, int sorb, int nele
   pynqs::DeviceScope device_scope_(bra);
   if (flavour < PYNQS_RBM_REAL || flavour > PYNQS_RBM_PHASE) return set_error(PYNQS_EINVAL, "unknown RBM flavour");
   if (green && (flavour == PYNQS_RBM_PHASE || !clamped)) return set_error(PYNQS_EINVAL, "the Green's-function row needs a real-valued flavour");
-  SDParams p;
-  PlanLayout pl;
-  RbmLayout rl;
-  if (!make_sd_params(sorb, nele, noA, noB, &p)) return set_error(PYNQS_EINVAL, "bad sorb/noA/noB");
-  if (!make_plan_layout(sorb, &pl)) return set_error(PYNQS_EINVAL, "plan needs an even sorb in [2, 192]");
-  if (!make_rbm_layout(sorb, nhidden, &rl)) return set_error(PYNQS_EINVAL, "bad nhidden");
-  if (nbatch < 0 || nbatch > 0x7fffffffll) return set_error(PYNQS_EINVAL, "bad nbatch");
+  RbmSystem<RbmLayout> sys;
+  if (const char *bad = rbm_system(sorb, nele, noA, noB, nhidden, make_rbm_layout, &sys)) return set_error(PYNQS_EINVAL, bad);
+  if (const int rc = rbm_batch(nbatch, 0x7fffffffll, bra, plan, rbm_table, eloc)) return rc;
   if (nbatch == 0) return PYNQS_OK;
-  if (!bra || !plan || !rbm_table || !eloc) return set_error(PYNQS_EINVAL, "null pointer");
-  const RbmBlocks B = make_rbm_blocks(p);
+  const auto &[p, pl, rl] = sys;
+  const RbmBlocks<kRbmFB> B = make_rbm_blocks<kRbmFB>(p);
   const RbmForm form = rbm_form(p, rl, B, nbatch, green != nullptr);
   const uint32_t nchunks = form.nchunks, hw = form.hw;
-  const RbmShape shape = form.shape;
   if (hw == 0) return set_error(PYNQS_EINVAL, "the walker tables of this system leave no LDS for the RBM rows");
   const bool windowed = hw < (uint32_t)rl.Hloop;
   const size_t lds = lds_bytes_rbm(p, rl, hw);
-  const uint64_t grid = (uint64_t)nbatch * nchunks;
-  if (grid > 0x7fffffffull) return set_error(PYNQS_EINVAL, "grid too large");
   hipStream_t st = (hipStream_t)stream;
-  if (nchunks > 1 && hipMemsetAsync(eloc, 0, (flavour == PYNQS_RBM_PHASE ? 16 : 8) * (size_t)nbatch, st) != hipSuccess)
-    return check_launch("memset");
+  uint32_t grid;
+  if (const int rc = rbm_grid(nbatch, nchunks, eloc, flavour == PYNQS_RBM_PHASE ? 16 : 8, st, &grid)) return rc;
   const int len = (sorb - 1) / 64 + 1;
   // (3-wave workgroups divide Fe2S2's 9 tiles evenly but leave only 12 waves per CU -- LDS allows 4 workgroups --
   // and were 8 % slower at 80 hidden units; the kernel itself runs with any multiple of 64 threads >= 128)
-  // resident q': the workgroup size that puts the most waves on a CU (the registers allow 16; a workgroup's waves share
-  // its LDS), as long as the walker has at least two tiles per wave.  Fe2S2 (31 KiB): 256 threads, 4 workgroups per CU;
-  // sorb 56 with 112 hidden units (58 KiB): two workgroups per CU -> 512 threads.
-  uint32_t threads = shape.threads;
-  if (!windowed) {
-    static const int blk_env = getenv("PYNQS_RBM_BLOCK") ? atoi(getenv("PYNQS_RBM_BLOCK")) : 0;
-    threads = kBlock;
-    size_t best = 0;
-    for (uint32_t b = kBlock; b <= 1024; b *= 2) {
-      size_t waves = (160 * 1024 / (lds + 256)) * (b / 64);
-      if (waves > 16) waves = 16;
-      if (b > kBlock && B.ntiles / nchunks < 2 * (b / 64)) break;
-      if (waves > best) { best = waves; threads = b; }
-    }
-    if (blk_env == 256 || blk_env == 512 || blk_env == 1024) threads = (uint32_t)blk_env;
-  }
-#define PYNQS_RBM_LAUNCH(W, F, G)                                                                                                     \
-  do {                                                                                                                                \
-    if (lds > 64 * 1024 && hipFuncSetAttribute(reinterpret_cast<const void *>(&eloc_rbm_kernel<LEN, W, F, G>),                       \
-                                               hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds) != hipSuccess)                  \
-      return check_launch("hipFuncSetAttribute");                                                                                     \
-    hipLaunchKernelGGL((eloc_rbm_kernel<LEN, W, F, G>), dim3((uint32_t)grid), dim3(threads), lds, st, bra, p, pl, rl, B, nchunks, hw, \
-                       (const double *)plan, (const double *)rbm_table, eloc, psi, lambda, green, clamped);                          \
-  } while (0)
+  const uint32_t threads = windowed ? form.shape.threads : rbm_resident_threads(lds, B.ntiles / nchunks, 1024, rbm_block_env());
+  int rc = PYNQS_OK;
+#define PYNQS_RBM_LAUNCH(W, F, G)                                                                                                            \
+  rc = rbm_launch("eloc_rbm", eloc_rbm_kernel<LEN, W, F, G>, grid, threads, lds, st, bra, p, pl, rl, B, nchunks, hw, (const double *)plan, \
+                  (const double *)rbm_table, eloc, psi, lambda, green, clamped)
 #define PYNQS_RBM_FLAVOURS(W)                                                \
   do {                                                                       \
     if (green && flavour == PYNQS_RBM_REAL) PYNQS_RBM_LAUNCH(W, kRbmReal, true);  \
@@ -732,7 +635,7 @@ static int eloc_rbm_impl(const uint64_t *bra, int64_t nbatch, int sorb, int nele
   });
 #undef PYNQS_RBM_FLAVOURS
 #undef PYNQS_RBM_LAUNCH
-  return check_launch("eloc_rbm");
+  return rc;
 }
 
 extern "C" int pynqs_eloc_rbm_flavour(const uint64_t *bra, int64_t nbatch, int sorb, int nele, int noA, int noB, const void *plan,

@@ -3,7 +3,10 @@
 //   psi(x) = exp(a.x) prod_h 2 cosh(theta_h(x)),  theta_h = b_h + sum_o W[h][o] x_o,   a, b, W complex, x_o = +-1
 // (vmc/ansatz/rbm/rbm.py:199-211, rbm_type "complex"; rbm_type "cos", prod_h cos(theta_h) with real parameters, is the same
 // function of i*W, i*b up to the constant 2^H: cos t = cosh(i t)).
-// Same algebra as kernels_rbm.hip with complex numbers: an excitation flips the orbitals F, theta' = theta - delta,
+// Same algebra as kernels_rbm.hip with complex numbers, and the same cut into blocks and tiles, phase-A diagonal and singles, sums over
+// waves, LDS trailer and host-side launch rules: those live in rbm_tiles.h.  This file has what complex numbers change: 2 x 4 blocks,
+// the theta loop, the window builder, the hidden-unit loop on ds_read_b128, the epilogue and the window rule.
+// An excitation flips the orbitals F, theta' = theta - delta,
 // delta_h = 2 sum_{o in F} W[h][o] x_o; with s_h = sign(Re theta_h), rho_h = exp(-2 s_h theta_h) (|rho| <= 1), m_h = 1/(1 + rho_h):
 //   cosh(theta_h - delta_h)/cosh(theta_h) = exp(-s_h delta_h) (m_h + m_h rho_h prod_{o in F} q_h(o)),  q_h(o) = exp(4 s_h W[h][o] x_o),
 //   psi(x')/psi(x) = prod_{o in F} C(o) * prod_h (m_h + prod_{o in F} q'_h(o)),   q'_h(o) = (m_h rho_h)^(1/4) q_h(o),
@@ -15,11 +18,8 @@
 // When sorb x num_hidden rows do not fit the LDS the kernel runs WINDOWED (round 3), like the real-parameter kernel: the workgroup
 // streams q' through the LDS `hw` hidden units at a time, and in every round each wave keeps the 8 x 64 running products of ONE tile in
 // registers across the windows (two barriers per window; the rows of a window are rebuilt every round: ~1 % of a round's work).
-#include "detcore.h"
-#include "launch.h"
-#include "plan.h"
-#include "plan_dev.h"
 #include "rbm.h"
+#include "rbm_tiles.h"
 
 namespace pynqs {
 
@@ -51,40 +51,19 @@ __global__ __launch_bounds__(kBlock) void crbm_table_kernel(const cplx *__restri
   if (i < cl.sorb) tab[cl.offVb + i] = vb ? vb[i] : cplx{0.0, 0.0};
 }
 
-// 2 x 4 blocks: class k (0 singles x nothing, 1 alpha-alpha, 2 beta-beta, 3 alpha-beta) has nbf[k] x nbs blocks
-struct CrbmBlocks {
-  uint32_t nbf[4];
-  uint32_t b[4];  // cumulative block counts
-  uint32_t ntiles;
-  MagicDiv dv[4];
-};
-
-static inline CrbmBlocks make_crbm_blocks(const SDParams &p) {
-  CrbmBlocks B;
-  const uint32_t nf[4] = {p.d1, (uint32_t)p.noAA, (uint32_t)p.noBB, (uint32_t)p.nSa};
-  const uint32_t ns[4] = {p.d1 ? 1u : 0u, (uint32_t)p.nvAA, (uint32_t)p.nvBB, (uint32_t)p.nSb};
-  uint32_t acc = 0;
-  for (int k = 0; k < 4; ++k) {
-    B.nbf[k] = (nf[k] + 1) / 2;
-    B.dv[k] = make_magic(B.nbf[k]);
-    acc += B.nbf[k] * ((ns[k] + 3) / 4);
-    B.b[k] = acc;
-  }
-  B.ntiles = (acc + 63) / 64;
-  return B;
-}
+constexpr int kCrbmFB = 2;   // a lane owns 2 x 4 excitations (rbm_tiles.h)
+constexpr int kCrbmRed = 2;  // doubles per wave in the LDS trailer
 
 // LDS after the walker tables (16-byte aligned): q [sorb + 1][Hs] cplx | m [Hs] cplx | n4 [Hs] cplx | Cq [sorb + 2] cplx |
-// sh [Hs] double | hs [d1 + 2] double | rowaddr [sorb + 2] u32 | red [2 * 16] double, counters
-__host__ __device__ inline size_t crbm_q_offset(const SDParams &p) { return (lds_fixed_bytes(p) + 15) & ~(size_t)15; }
+// sh [Hs] double | hs [d1 + 2] double | rowaddr [sorb + 2] u32 | the trailer (rbm_tiles.h)
 // `hw`: hidden units of q' resident at a time (even): cl.Hloop (all of them) or the window of the WINDOWED kernel; row stride hw + 1
 __host__ __device__ inline size_t lds_bytes_crbm(const SDParams &p, const CrbmLayout &cl, uint32_t hw) {
-  return crbm_q_offset(p) + 16 * ((size_t)(p.sorb + 1) * (hw + 1) + 2 * (size_t)cl.Hs + (size_t)(p.sorb + 2)) +
-         8 * ((size_t)cl.Hs + (size_t)(p.d1 + 2) + 1) + 4 * (((size_t)p.sorb + 2 + 3) & ~(size_t)3) + 8 * 32 + 16;
+  return rbm_q_offset(p) + 16 * ((size_t)(p.sorb + 1) * (hw + 1) + 2 * (size_t)cl.Hs + (size_t)(p.sorb + 2)) +
+         8 * ((size_t)cl.Hs + (size_t)(p.d1 + 2) + 1) + 4 * (((size_t)p.sorb + 2 + 3) & ~(size_t)3) + rbm_trailer_bytes(kCrbmRed);
 }
 
 template <int LEN, bool WINDOWED>
-__global__ __launch_bounds__(512) void eloc_crbm_kernel(const uint64_t *__restrict__ bra, SDParams p, PlanLayout pl, CrbmLayout cl, CrbmBlocks B,
+__global__ __launch_bounds__(512) void eloc_crbm_kernel(const uint64_t *__restrict__ bra, SDParams p, PlanLayout pl, CrbmLayout cl, RbmBlocks<kCrbmFB> B,
                                                         uint32_t nchunks, uint32_t hw, const double *__restrict__ plan,
                                                         const cplx *__restrict__ rbm, double log_scale, double *__restrict__ eloc,
                                                         double *__restrict__ psi) {
@@ -97,17 +76,15 @@ __global__ __launch_bounds__(512) void eloc_crbm_kernel(const uint64_t *__restri
   const int sorb = p.sorb, H = cl.H, Hs = cl.Hs;
   const uint32_t K = (uint32_t)sorb >> 1;
   const uint32_t stride = hw + 1;  // complex elements per q' row
-  cplx *q = reinterpret_cast<cplx *>(smem + crbm_q_offset(p));
+  cplx *q = reinterpret_cast<cplx *>(smem + rbm_q_offset(p));
   cplx *mm = q + (size_t)(sorb + 1) * stride;
   cplx *n4 = mm + Hs;
   cplx *Cq = n4 + Hs;
   double *sh = reinterpret_cast<double *>(Cq + (sorb + 2));
   double *hs = sh + Hs;
   uint32_t *rowaddr = reinterpret_cast<uint32_t *>(hs + (p.d1 + 2) + 1);
-  double *red = reinterpret_cast<double *>(smem + lds_bytes_crbm(p, cl, hw) - (8 * 32 + 16));
-  uint32_t *next_tile_p = reinterpret_cast<uint32_t *>(red + 32);
-  uint32_t *next_single_p = next_tile_p + 1;
-  if (tid == 0) { *next_tile_p = 0; *next_single_p = 0; }
+  const RbmTrailer T = rbm_trailer(smem, lds_bytes_crbm(p, cl, hw), kCrbmRed);
+  if (tid == 0) { *T.next_tile = 0; *T.next_single = 0; }
   Walker<LEN> wk;
   load_walker<LEN>(bra + walker * LEN, wk);
   const LdsLayout L = carve_lds(smem, p);
@@ -115,16 +92,12 @@ __global__ __launch_bounds__(512) void eloc_crbm_kernel(const uint64_t *__restri
 
   // ---- phase A (no barrier inside): last wave <x|H|x>; the others theta_h -> m_h, (m_h rho_h)^(1/4), s_h, ln 2cosh(theta_h); then
   // every wave the singles' matrix elements
-  const uint32_t tS = (B.b[0] + 63) / 64;
-  const bool need_hs = chunk < max(tS, 1u);
+  const bool need_hs = rbm_needs_hs(B, chunk);
   const cplx *__restrict__ Wt = rbm + cl.offWt;
   cplx lnpsi = {0.0, 0.0};
   const int kThetaThreads = nthreads - 64;
   if (wave == nwaves - 1) {
-    if (need_hs) {
-      const double hii = fast_diag<double>(p, pl, L, plan);
-      if (lane == 0) hs[0] = hii;
-    }
+    rbm_diagonal(need_hs, lane, p, pl, L, plan, hs);
   } else {
     for (int h = tid; h < Hs; h += kThetaThreads) {
       cplx m = {1.0, 0.0}, nq = {0.0, 0.0};
@@ -148,16 +121,7 @@ __global__ __launch_bounds__(512) void eloc_crbm_kernel(const uint64_t *__restri
       mm[h] = m; n4[h] = nq; sh[h] = s;
     }
   }
-  if (need_hs) {
-    const uint32_t nst = (p.d1 + 63) / 64;
-    for (;;) {
-      uint32_t t = 0;
-      if (lane == 0) t = atomicAdd(next_single_p, 1u);
-      t = __builtin_amdgcn_readfirstlane(t);
-      if (t >= nst) break;
-      if (t * 64 + lane < p.d1) hs[1 + t * 64 + lane] = fast_single<double>(t * 64 + lane, p, pl, L, nocc, plan);
-    }
-  }
+  rbm_singles(need_hs, lane, p, pl, L, nocc, plan, hs, T.next_single);
   __syncthreads();
   // ---- phase B: q'[o][h] = (m_h rho_h)^(1/4) exp(4 s_h x_o W[h][o]) for the hidden units [h0, h0 + hw), a wave per row, and (with_sum:
   // the window is all of them) sum_h s_h W[h][o]
@@ -202,7 +166,7 @@ __global__ __launch_bounds__(512) void eloc_crbm_kernel(const uint64_t *__restri
     }
   }
   __syncthreads();
-  const uint32_t qbase = __builtin_amdgcn_groupstaticsize() + (uint32_t)crbm_q_offset(p), rowB = stride * 16u;
+  const uint32_t qbase = __builtin_amdgcn_groupstaticsize() + (uint32_t)rbm_q_offset(p), rowB = stride * 16u;
   for (int o = tid; o <= sorb; o += nthreads) {
     rowaddr[o] = qbase + rbm_row((uint32_t)o) * rowB;
     cplx c = {1.0, 0.0};
@@ -229,7 +193,7 @@ __global__ __launch_bounds__(512) void eloc_crbm_kernel(const uint64_t *__restri
       lt = round * (uint32_t)nwaves + (uint32_t)wave;
       active = lt < my_tiles;
     } else {
-      if (lane == 0) lt = atomicAdd(next_tile_p, 1u);
+      if (lane == 0) lt = atomicAdd(T.next_tile, 1u);
       lt = __builtin_amdgcn_readfirstlane(lt);
       if (lt >= my_tiles) break;
     }
@@ -335,28 +299,19 @@ __global__ __launch_bounds__(512) void eloc_crbm_kernel(const uint64_t *__restri
     }
   }
   if (chunk == 0 && tid == 0) esum.x += hs[0];  // x' = x
-  // fixed-order reductions: lanes, then waves
+  // fixed-order reductions: lanes, then waves (rbm_over_waves: valid in thread 0)
 #pragma unroll
   for (int o = 32; o > 0; o >>= 1) {
     esum.x += __shfl_xor(esum.x, o); esum.y += __shfl_xor(esum.y, o);
     lnpsi.x += __shfl_xor(lnpsi.x, o); lnpsi.y += __shfl_xor(lnpsi.y, o);
   }
-  auto over_waves = [&](cplx v) {  // workgroup-uniform calls; valid in thread 0
-    __syncthreads();
-    if (lane == 0) { red[2 * wave] = v.x; red[2 * wave + 1] = v.y; }
-    __syncthreads();
-    cplx s = {0.0, 0.0};
-    if (tid == 0)
-      for (int w = 0; w < nwaves; ++w) { s.x += red[2 * w]; s.y += red[2 * w + 1]; }
-    return s;
-  };
-  const cplx e = over_waves(esum);
+  const cplx e = rbm_over_waves(esum, T.red, tid, nwaves);
   if (tid == 0) {
     if (nchunks == 1) { eloc[2 * walker] = e.x; eloc[2 * walker + 1] = e.y; }
     else { atomicAdd(eloc + 2 * walker, e.x); atomicAdd(eloc + 2 * walker + 1, e.y); }
   }
   if (psi != nullptr && chunk == 0) {  // workgroup-uniform
-    const cplx s = over_waves(lnpsi);
+    const cplx s = rbm_over_waves(lnpsi, T.red, tid, nwaves);
     if (tid == 0) {
       const cplx v = cexp(cplx{s.x - log_scale, s.y});
       psi[2 * walker] = v.x; psi[2 * walker + 1] = v.y;
@@ -369,45 +324,30 @@ __global__ __launch_bounds__(512) void eloc_crbm_kernel(const uint64_t *__restri
 // =================================================================================================
 using namespace pynqs;
 
-static constexpr size_t kCrbmMaxLds = 158 * 1024;
-
 // hidden units of q' resident at a time: all of them (cl.Hloop) if they fit, else the largest even window that leaves room for two
 // workgroups per CU when it can (PYNQS_CRBM_WINDOW forces a window, for tests); 0: not even a window of two fits
 static uint32_t crbm_window(const SDParams &p, const CrbmLayout &cl) {
   const int win_env = getenv("PYNQS_CRBM_WINDOW") ? atoi(getenv("PYNQS_CRBM_WINDOW")) : 0;  // (read per call: tests switch it)
   if (win_env >= 2) {
     const uint32_t hw = (uint32_t)win_env & ~1u;
-    return hw >= (uint32_t)cl.Hloop ? (uint32_t)cl.Hloop : (lds_bytes_crbm(p, cl, hw) <= kCrbmMaxLds ? hw : 0u);
+    return hw >= (uint32_t)cl.Hloop ? (uint32_t)cl.Hloop : (lds_bytes_crbm(p, cl, hw) <= kRbmMaxLds ? hw : 0u);
   }
-  if (lds_bytes_crbm(p, cl, (uint32_t)cl.Hloop) <= kCrbmMaxLds) return (uint32_t)cl.Hloop;
+  if (lds_bytes_crbm(p, cl, (uint32_t)cl.Hloop) <= kRbmMaxLds) return (uint32_t)cl.Hloop;
   const size_t fixed = lds_bytes_crbm(p, cl, 0u), row = 16 * (size_t)(p.sorb + 1);
-  for (size_t budget : {(size_t)(79 * 1024), kCrbmMaxLds}) {
+  for (size_t budget : {(size_t)(79 * 1024), kRbmMaxLds}) {
     if (fixed + 3 * row > budget) continue;
     uint32_t hw = (uint32_t)((budget - fixed) / row - 1) & ~1u;
-    if (hw >= 16u || budget == kCrbmMaxLds) return hw >= 2u ? hw : 0u;
+    if (hw >= 16u || budget == kRbmMaxLds) return hw >= 2u ? hw : 0u;
   }
   return 0u;
 }
 
-// few walkers: a walker's tiles over several workgroups (each repeats the per-walker set-up and adds its part with an atomic)
-static uint32_t crbm_chunks(const CrbmBlocks &B, int64_t nbatch) {
-  uint32_t nchunks = 1;
-  if (nbatch < 1024) {
-    nchunks = (uint32_t)((1024 + nbatch - 1) / nbatch);
-    const uint32_t maxc = B.ntiles / 4 > 0 ? B.ntiles / 4 : 1;
-    if (nchunks > maxc) nchunks = maxc;
-  }
-  return nchunks;
-}
-
 extern "C" int pynqs_eloc_crbm_form(int64_t nbatch, int sorb, int nele, int noA, int noB, int nhidden) {
-  SDParams p;
-  PlanLayout pl;
-  CrbmLayout cl;
-  if (nbatch < 1 || !make_sd_params(sorb, nele, noA, noB, &p) || !make_plan_layout(sorb, &pl) || !make_crbm_layout(sorb, nhidden, &cl)) return -1;
-  const uint32_t hw = crbm_window(p, cl);
+  RbmSystem<CrbmLayout> s;
+  if (nbatch < 1 || rbm_system(sorb, nele, noA, noB, nhidden, make_crbm_layout, &s)) return -1;
+  const uint32_t hw = crbm_window(s.p, s.rl);
   if (hw == 0) return -1;
-  return (hw < (uint32_t)cl.Hloop ? 1 : 0) | (crbm_chunks(make_crbm_blocks(p), nbatch) > 1 ? 2 : 0);
+  return (hw < (uint32_t)s.rl.Hloop ? 1 : 0) | (rbm_chunks(make_rbm_blocks<kCrbmFB>(s.p).ntiles, nbatch) > 1 ? 2 : 0);
 }
 
 extern "C" int64_t pynqs_crbm_table_bytes(int sorb, int nhidden) {
@@ -417,11 +357,9 @@ extern "C" int64_t pynqs_crbm_table_bytes(int sorb, int nhidden) {
 }
 
 extern "C" int pynqs_eloc_crbm_supported(int sorb, int nele, int noA, int noB, int nhidden) {
-  SDParams p;
-  PlanLayout pl;
-  CrbmLayout cl;
-  if (!make_sd_params(sorb, nele, noA, noB, &p) || !make_plan_layout(sorb, &pl) || !make_crbm_layout(sorb, nhidden, &cl)) return 0;
-  return crbm_window(p, cl) > 0 ? 1 : 0;
+  RbmSystem<CrbmLayout> s;
+  if (rbm_system(sorb, nele, noA, noB, nhidden, make_crbm_layout, &s)) return 0;
+  return crbm_window(s.p, s.rl) > 0 ? 1 : 0;
 }
 
 extern "C" int pynqs_crbm_table_build(const double *weights, const double *hidden_bias, const double *visible_bias, int sorb, int nhidden,
@@ -440,44 +378,27 @@ extern "C" int pynqs_crbm_table_build(const double *weights, const double *hidde
 extern "C" int pynqs_eloc_crbm(const uint64_t *bra, int64_t nbatch, int sorb, int nele, int noA, int noB, const void *plan,
                                const void *crbm_table, int nhidden, double log_scale, double *eloc, double *psi, void *stream) {
   pynqs::DeviceScope device_scope_(bra);
-  SDParams p;
-  PlanLayout pl;
-  CrbmLayout cl;
-  if (!make_sd_params(sorb, nele, noA, noB, &p)) return set_error(PYNQS_EINVAL, "bad sorb/noA/noB");
-  if (!make_plan_layout(sorb, &pl)) return set_error(PYNQS_EINVAL, "plan needs an even sorb in [2, 192]");
-  if (!make_crbm_layout(sorb, nhidden, &cl)) return set_error(PYNQS_EINVAL, "bad nhidden");
-  if (nbatch < 0 || nbatch > 0x3fffffffll) return set_error(PYNQS_EINVAL, "bad nbatch");
+  RbmSystem<CrbmLayout> sys;
+  if (const char *bad = rbm_system(sorb, nele, noA, noB, nhidden, make_crbm_layout, &sys)) return set_error(PYNQS_EINVAL, bad);
+  if (const int rc = rbm_batch(nbatch, 0x3fffffffll, bra, plan, crbm_table, eloc)) return rc;
   if (nbatch == 0) return PYNQS_OK;
-  if (!bra || !plan || !crbm_table || !eloc) return set_error(PYNQS_EINVAL, "null pointer");
+  const auto &[p, pl, cl] = sys;
   const uint32_t hw = crbm_window(p, cl);
   if (hw == 0) return set_error(PYNQS_EINVAL, "the per-hidden-unit arrays of this RBM do not fit the LDS (pynqs_eloc_crbm_supported)");
   const bool windowed = hw < (uint32_t)cl.Hloop;
   const size_t lds = lds_bytes_crbm(p, cl, hw);
-  const CrbmBlocks B = make_crbm_blocks(p);
-  const uint32_t nchunks = crbm_chunks(B, nbatch);
-  const uint64_t grid = (uint64_t)nbatch * nchunks;
-  if (grid > 0x7fffffffull) return set_error(PYNQS_EINVAL, "grid too large");
+  const RbmBlocks<kCrbmFB> B = make_rbm_blocks<kCrbmFB>(p);
+  const uint32_t nchunks = rbm_chunks(B.ntiles, nbatch);
   hipStream_t st = (hipStream_t)stream;
-  if (nchunks > 1 && hipMemsetAsync(eloc, 0, 16 * (size_t)nbatch, st) != hipSuccess) return check_launch("memset");
-  // workgroup size: the one that puts the most waves on a CU (a workgroup's waves share its LDS), as long as the walker has at
-  // least two tiles per wave; PYNQS_CRBM_BLOCK overrides
+  uint32_t grid;
+  if (const int rc = rbm_grid(nbatch, nchunks, eloc, 16, st, &grid)) return rc;
   static const int blk_env = getenv("PYNQS_CRBM_BLOCK") ? atoi(getenv("PYNQS_CRBM_BLOCK")) : 0;
-  uint32_t threads = kBlock;
-  size_t best = 0;
-  for (uint32_t b = kBlock; b <= 512; b *= 2) {
-    size_t waves = (160 * 1024 / (lds + 256)) * (b / 64);
-    if (waves > 16) waves = 16;
-    if (b > kBlock && B.ntiles / nchunks < 2 * (b / 64)) break;
-    if (waves > best) { best = waves; threads = b; }
-  }
-  if (blk_env == 128 || blk_env == 256 || blk_env == 512) threads = (uint32_t)blk_env;
+  const uint32_t threads = rbm_resident_threads(lds, B.ntiles / nchunks, 512, blk_env);  // (the windowed form too)
   const int len = (sorb - 1) / 64 + 1;
+  int rc = PYNQS_OK;
   DISPATCH_LEN(len, {
-    auto kfn = windowed ? eloc_crbm_kernel<LEN, true> : eloc_crbm_kernel<LEN, false>;
-    if (lds > 64 * 1024 && hipFuncSetAttribute(reinterpret_cast<const void *>(kfn), hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds) != hipSuccess)
-      return check_launch("hipFuncSetAttribute");
-    hipLaunchKernelGGL(kfn, dim3((uint32_t)grid), dim3(threads), lds, st, bra, p, pl, cl, B, nchunks, hw, (const double *)plan,
-                       (const cplx *)crbm_table, log_scale, eloc, psi);
+    rc = rbm_launch("eloc_crbm", windowed ? eloc_crbm_kernel<LEN, true> : eloc_crbm_kernel<LEN, false>, grid, threads, lds, st, bra, p, pl, cl, B,
+                    nchunks, hw, (const double *)plan, (const cplx *)crbm_table, log_scale, eloc, psi);
   });
-  return check_launch("eloc_crbm");
+  return rc;
 }

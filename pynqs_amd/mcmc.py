@@ -28,14 +28,13 @@ from .distributed import get_rank, get_world_size, shard_bounds
 
 __all__ = ["MCMCSampler", "mcmc_rbm_supported"]
 
-_FLAVOUR = {"real": N.RBM_REAL, "tanh": N.RBM_TANH, "pRBM": N.RBM_PHASE, "complex": N.RBM_COMPLEX}
 # chain-steps x hidden units of one fused launch at most: ~1 ms of kernel time at the Fe2S2 size, a few ms at sorb 192
 _LAUNCH_WORK = 1 << 28
 _MAX_STEPS_PER_LAUNCH = 256
 
 
 def mcmc_rbm_supported(sorb: int, num_hidden: int, rbm_type: str = "real") -> bool:
-    flav = _FLAVOUR.get(rbm_type)
+    flav = CX.RBM_TYPE_FLAVOUR.get(rbm_type)
     return flav is not None and bool(N.lib().pynqs_mcmc_rbm_supported(sorb, num_hidden, flav))
 
 
@@ -66,7 +65,7 @@ class _Fused:
             if W.size(1) != sorb:
                 raise RuntimeError(f"RBM weights have {W.size(1)} visible units, the sampler sorb = {sorb}")
             self.table = CX.CRBMTable(W, hb, vb)
-        self.flavour = _FLAVOUR[self.kind]
+        self.flavour = CX.RBM_TYPE_FLAVOUR[self.kind]
         self.nhidden = int(W.size(0))
 
     @staticmethod

@@ -64,6 +64,30 @@ def test_host_entry_points():
     assert lib.pynqs_eloc_crbm_supported(66, 4, 2, 2, 4000) == 0
 
 
+def test_rbm_launch_decisions_are_unchanged(monkeypatch):
+    """Window, chunks, refusal and table sizes of the two fused RBM local-energy kernels (pynqs_eloc_rbm_form / _supported,
+    pynqs_eloc_crbm_form / _supported, pynqs_rbm_table_bytes / pynqs_crbm_table_bytes: host logic, no GPU) over systems x hidden units x
+    batch sizes x green, against the values recorded before the two kernels' host code was merged (tests/golden/rbm_launch_forms.json,
+    written by tests/golden/make_golden_rbm_launch.py): every value equal, no tolerance."""
+    import importlib.util
+    import json
+
+    from pynqs_amd import _native as N
+
+    for k in [k for k in os.environ if k.startswith(("PYNQS_RBM_", "PYNQS_CRBM_"))]:
+        monkeypatch.delenv(k)
+    spec = importlib.util.spec_from_file_location("make_golden_rbm_launch", os.path.join(ROOT, "tests", "golden", "make_golden_rbm_launch.py"))
+    rec = importlib.util.module_from_spec(spec)
+    spec.loader.exec_module(rec)
+    want = json.load(open(os.path.join(ROOT, "tests", "golden", "rbm_launch_forms.json")))
+    got = json.loads(json.dumps(rec.record(N.lib())))
+    assert (got["systems"], got["hidden"], got["nbatch"]) == (want["systems"], want["hidden"], want["nbatch"])
+    assert len(want["rbm_form"]) == 6 * 6 * 5 * 2 and len(want["crbm_form"]) == 6 * 6 * 5
+    for key in ("rbm_table_bytes", "crbm_table_bytes", "rbm_supported", "crbm_supported", "rbm_form", "crbm_form"):
+        diff = [i for i, (a, b) in enumerate(zip(got[key], want[key])) if a != b]
+        assert len(got[key]) == len(want[key]) and not diff, (key, diff[:10])
+
+
 def test_integral_layout_matches_oracle():
     from pynqs_amd import C_extension as cx
 
