@@ -189,6 +189,17 @@ int pynqs_eloc_sample_space_indexed(const uint64_t *bra, int64_t nbatch, int sor
                                     const uint64_t *keys, int64_t nkeys, const void *index, const double *wf, int wf_is_complex,
                                     int flip, double *eloc, double *psi0, void *stream);
 
+/* [host] the form a SAMPLE_SPACE launch takes, from the very rule the launch uses (0 on success, PYNQS_EINVAL on bad arguments; nbatch >= 1).
+ *   pynqs_eloc_sample_space_form : the column-major entry points (hash = 0: pynqs_eloc_sample_space / _flip on sorted keys, hash = 1:
+ *       the _hash forms on a table of nkeys keys).  out = {kind, two_level, block, sweep, pre, lds_bytes, nchunks, chunk_len}:
+ *       kind 0 = sorted-key search, 1 = hash table without filters, 2 = the filtered kernel; two_level = second-level filter in use;
+ *       block = threads per workgroup; sweep = block sweeps (else rank-by-rank scan); pre = string prefilter; lds_bytes = dynamic LDS;
+ *       nchunks / chunk_len = workgroups per walker and columns per workgroup.
+ *   pynqs_eloc_sample_space_keys_form : pynqs_eloc_sample_space_keys (indexed = 0) / _indexed (indexed = 1).
+ *       out = {groups, nchunks, chunk_len}: workgroups along the walkers, chunks of the key array per group, keys per chunk. */
+int pynqs_eloc_sample_space_form(int64_t nbatch, int sorb, int nele, int noA, int noB, int64_t nkeys, int hash, int64_t out[8]);
+int pynqs_eloc_sample_space_keys_form(int64_t nbatch, int sorb, int64_t nkeys, int indexed, int64_t out[3]);
+
 /* ---- duplicates among determinants, without a sort (`Func`, vmc/energy/flip.py:44-50: torch.unique(dim=0,
  * return_inverse=True) on the x' that reach the ansatz).  first[i] = smallest j with onv[j] == onv[i] (int32[n]);
  * the rows with first[i] == i are the distinct determinants in order of first appearance.  Deterministic.

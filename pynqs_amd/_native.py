@@ -50,6 +50,8 @@ SIGNATURES = {
     "pynqs_keys_index_build": (_int, [_vp, _i64, _int, _vp, _vp, _vp]),
     "pynqs_keys_index_density": (_int, [_vp, _i64, _int, _vp, _vp]),
     "pynqs_eloc_sample_space_indexed": (_int, [_vp, _i64, _int, _int, _int, _int, _vp, _vp, _i64, _vp, _vp, _int, _int, _vp, _vp, _vp]),
+    "pynqs_eloc_sample_space_form": (_int, [_i64, _int, _int, _int, _int, _i64, _int, C.POINTER(_i64)]),
+    "pynqs_eloc_sample_space_keys_form": (_int, [_i64, _int, _i64, _int, C.POINTER(_i64)]),
     "pynqs_eloc_rbm_supported": (_int, [_int, _int, _int, _int, _int]),
     "pynqs_eloc_rbm_form": (_int, [_i64, _int, _int, _int, _int, _int, _int]),
     "pynqs_rbm_table_bytes": (_i64, [_int, _int]),

@@ -300,6 +300,9 @@ inline uint32_t hash_string_bits(int64_t nkeys) {  // host side; per spin
   return (uint32_t)b;
 }
 
+// the string filters exist beside an LDS filter only (they share its Zobrist values)
+inline uint32_t hash_string_bits_if(int64_t nkeys) { return hash_filter_bits(nkeys) ? hash_string_bits(nkeys) : 0u; }
+
 template <int LEN>
 __host__ __device__ inline void zobrist_strings(const uint64_t (&q)[LEN], uint32_t &za, uint32_t &zb) {
   za = 0; zb = 0;

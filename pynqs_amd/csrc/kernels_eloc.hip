@@ -1,19 +1,19 @@
-// kernels_eloc.hip -- fused local-energy kernels on the integral plan: the excitation list and its matrix
-// elements are consumed on chip, comb / Hmat are never written to HBM.
-//   eloc_sample_space_filtered_kernel : E_loc(x) = sum_x' <x|H|x'> psi(x') / psi(x), psi from the hash table of the sample
-//                              space (vmc/energy/eloc.py:326-401 + utils/public_function.py:817-838); a Zobrist-hash filter
-//                              decides per column before any other work, candidates are queued and evaluated 64 at a time
-//   eloc_sample_space_kernel : the same sum with every column evaluated in place (tile scheduler + LookupSink): sorted
-//                              keys (binary search), or a hash table built without filters
-//   hash_build / hash_lookup : the table (the reference's optional GPU table, cuda_tensor.cpp:489-559) and its filters
-//   reduce_count / reduce_emit : keep only |<x|H|x'>| >= eps (vmc/energy/eloc.py:297-298), compacted in a reproducible order
-// Matrix elements of the doubles are bit-identical to kernels_plan.hip (same helpers); the sample-space kernels add the
-// terms of <x|H|x> and of the singles in an order-free way (E_loc is a rounded sum, tolerance 1e-8 Ha).
+// kernels_eloc.hip -- SAMPLE_SPACE local energy, COLUMN-MAJOR, on the integral plan: the excitation list and its matrix elements
+// are consumed on chip, comb / Hmat are never written to HBM.
+//   E_loc(x) = sum_x' <x|H|x'> psi(x') / psi(x), psi from the table of the sample space (vmc/energy/eloc.py:326-401 +
+//   utils/public_function.py:817-838)
+//   eloc_sample_space_filtered_kernel : a Zobrist-hash filter decides per column before any other work, candidates are queued and
+//                                       evaluated 64 at a time (hash table with its filters, kernels_hash.hip)
+//   eloc_sample_space_kernel : every column evaluated in place (tile scheduler + LookupSink): sorted keys (binary search), or a hash
+//                              table built without filters
+// Matrix elements of the doubles are bit-identical to kernels_plan.hip (same helpers); the terms of <x|H|x> and of the singles are
+// added in an order-free way (E_loc is a rounded sum, tolerance 1e-8 Ha).  What is shared with the key-major kernel: ss_common.h.
 #include "detcore.h"
 #include "launch.h"
 #include "plan.h"
 #include "plan_dev.h"
 #include "plan_tiles.h"
+#include "ss_common.h"
 
 namespace pynqs {
 
@@ -23,20 +23,6 @@ namespace pynqs {
 // sum; the workgroup that owns column 0 also stores psi(x).  One workgroup per (walker, chunk); with more than
 // one chunk per walker partial sums meet through float atomics (the last bits then depend on arrival order).
 // HASH: `keys` is a hash table built by pynqs_hash_build (nkeys = its capacity) instead of the sorted keys.
-// Spin-flip partner of a determinant (vmc/energy/flip.py:322-418, utils/public_function.py:966-1007): alpha <-> beta occupations
-// exchanged (orbitals 2k <-> 2k + 1 live in the same word) and the sign (-1)^(doubly occupied spatial orbitals) of x' itself.
-template <int LEN>
-__device__ __forceinline__ bool spin_flip_ket(uint64_t (&ket)[LEN]) {
-  uint32_t pairs = 0;
-#pragma unroll
-  for (int i = 0; i < LEN; ++i) {
-    const uint64_t w = ket[i];
-    pairs += (uint32_t)__popcll(w & (w >> 1) & 0x5555555555555555ull);
-    ket[i] = ((w >> 1) & 0x5555555555555555ull) | ((w & 0x5555555555555555ull) << 1);
-  }
-  return pairs & 1u;  // true: eta_m = -1
-}
-
 template <int LEN, bool CPLX, bool HASH>
 struct LookupSink {
   const uint64_t *__restrict__ keys;
@@ -68,20 +54,11 @@ struct LookupSink {
     accumulate(col, h, pos);
   }
   __device__ __forceinline__ void accumulate(uint32_t col, double h, int64_t pos) {
-    double vr = 0.0, vi = 0.0;
-    if (pos >= 0) {
-      if constexpr (CPLX) {  // one 16-byte load: the kernel is bound by the number of vector-memory instructions (TD busy 91 %)
-        typedef double d2 __attribute__((ext_vector_type(2)));
-        const d2 v = *reinterpret_cast<const d2 *>(wf + 2 * pos);
-        vr = v[0]; vi = v[1];
-      } else vr = wf[pos];
-    }
+    double vr, vi;
+    table_value<CPLX>(wf, pos, vr, vi);
     re += h * vr;
     if constexpr (CPLX) im += h * vi;
-    if (col == 0 && !flip) {
-      psi0[0] = vr;
-      if constexpr (CPLX) psi0[1] = vi;
-    }
+    if (col == 0) store_psi0<CPLX>(psi0, vr, vi, flip);
   }
   __device__ __forceinline__ void tile_begin(uint32_t) const {}
   __device__ __forceinline__ void one(uint32_t col, double h, const uint64_t (&ket)[LEN]) { add(col, h, ket); }
@@ -267,19 +244,9 @@ struct Candidates {
     filter2_position(z2, f2bits, word, mask);
     return (filt2[word] & mask) == mask;
   }
-  __device__ __forceinline__ void value(int64_t pos, double &vr, double &vi) const {  // psi of table entry pos, 0 if pos < 0
-    vr = 0.0; vi = 0.0;
-    if (pos >= 0) {
-      if constexpr (CPLX) {
-        typedef double d2 __attribute__((ext_vector_type(2)));
-        const d2 v = *reinterpret_cast<const d2 *>(wf + 2 * pos);
-        vr = v[0]; vi = v[1];
-      } else vr = wf[pos];
-    }
-  }
   __device__ __forceinline__ void add(double h, int64_t pos) {
     double vr, vi;
-    value(pos, vr, vi);
+    table_value<CPLX>(wf, pos, vr, vi);
     re += h * vr;
     if constexpr (CPLX) im += h * vi;
   }
@@ -565,14 +532,10 @@ __global__ __launch_bounds__(BLOCK) void eloc_sample_space_filtered_kernel(const
           for (int i = 0; i < LEN; ++i) q[i] = wk.w[i];
           double hv = v;
           if (flip && spin_flip_ket<LEN>(q)) hv = -hv;
-          cand.value(hash_find<LEN>(table, (uint64_t)cap, q), vr, vi);
+          table_value<CPLX>(wf, hash_find<LEN>(table, (uint64_t)cap, q), vr, vi);
           cand.re += hv * vr;
           if constexpr (CPLX) cand.im += hv * vi;
-          if (!flip) {
-            double *__restrict__ out = psi0 + (CPLX ? 2 : 1) * walker;
-            out[0] = vr;
-            if constexpr (CPLX) out[1] = vi;
-          }
+          store_psi0<CPLX>(psi0 + (CPLX ? 2 : 1) * walker, vr, vi, flip);
         }
       }
       continue;
@@ -718,75 +681,6 @@ __global__ __launch_bounds__(BLOCK) void eloc_sample_space_filtered_kernel(const
   store_walker_sum<CPLX, BLOCK / 64>(cand.re, cand.im, red, nchunks, walker, acc, psi0);
 }
 
-// the string filters exist beside an LDS filter only (they share its Zobrist values)
-static inline uint32_t hash_string_bits_if(int64_t nkeys) { return hash_filter_bits(nkeys) ? hash_string_bits(nkeys) : 0u; }
-
-// Insert key i of the sorted key array: claim a slot by CAS on its index word, then write the key words
-// (lookups only start after the build kernel has finished).
-template <int LEN>
-__global__ __launch_bounds__(kBlock) void hash_build_kernel(const uint64_t *__restrict__ keys, int64_t nkeys, uint64_t cap,
-                                                            uint64_t *__restrict__ table, uint32_t fbits, uint32_t f2bits, uint32_t sbits) {
-  const int64_t i = (int64_t)blockIdx.x * kBlock + threadIdx.x;
-  if (i >= nkeys) return;
-  uint64_t q[LEN];
-#pragma unroll
-  for (int w = 0; w < LEN; ++w) q[w] = keys[i * LEN + w];
-  constexpr int W = hash_slot_words(LEN);
-  const uint64_t hq = hash_of<LEN>(q);
-  uint64_t s = hq & (cap - 1);
-  for (uint64_t probes = 0; probes < cap; ++probes) {
-    unsigned long long *idxp = reinterpret_cast<unsigned long long *>(table + s * W + (W - 1));
-    const unsigned long long old = atomicCAS(idxp, ~0ull, (unsigned long long)i);
-    if (old == ~0ull) {
-#pragma unroll
-      for (int w = 0; w < LEN; ++w) table[s * W + w] = q[w];
-      if (fbits || f2bits) {
-        uint32_t z, z2, b0, b1;
-        zobrist_of<LEN>(q, z, z2);
-        uint32_t *filter = reinterpret_cast<uint32_t *>(table + cap * W);
-        if (fbits) {
-          filter_positions(z, fbits, b0, b1);
-          atomicOr(filter + (b0 >> 5), 1u << (b0 & 31u));
-          atomicOr(filter + (b1 >> 5), 1u << (b1 & 31u));
-          filter += fbits / 32;
-        }
-        if (f2bits) {  // second level
-          filter2_position(z2, f2bits, b0, b1);
-          atomicOr(filter + b0, b1);
-          filter += f2bits / 32;
-        }
-        if (sbits) {  // the key's alpha and beta strings
-          uint32_t za, zb;
-          zobrist_strings<LEN>(q, za, zb);
-          filter_positions(za, sbits, b0, b1);
-          atomicOr(filter + (b0 >> 5), 1u << (b0 & 31u));
-          atomicOr(filter + (b1 >> 5), 1u << (b1 & 31u));
-          filter += sbits / 32;
-          filter_positions(zb, sbits, b0, b1);
-          atomicOr(filter + (b0 >> 5), 1u << (b0 & 31u));
-          atomicOr(filter + (b1 >> 5), 1u << (b1 & 31u));
-        }
-      }
-      return;
-    }
-    s = (s + 1) & (cap - 1);
-  }
-}
-
-template <int LEN>
-__global__ __launch_bounds__(kBlock) void hash_lookup_kernel(const uint64_t *__restrict__ table, uint64_t cap,
-                                                             const uint64_t *__restrict__ onv, uint64_t n,
-                                                             int64_t *__restrict__ idx, uint8_t *__restrict__ mask) {
-  const uint64_t i = (uint64_t)blockIdx.x * kBlock + threadIdx.x;
-  if (i >= n) return;
-  uint64_t q[LEN];
-#pragma unroll
-  for (int w = 0; w < LEN; ++w) q[w] = onv[i * LEN + w];
-  const int64_t r = hash_find<LEN>(table, cap, q);
-  idx[i] = r;
-  mask[i] = r >= 0;
-}
-
 // eloc = acc / psi0 (complex division when CPLX), in place on acc
 template <bool CPLX>
 __global__ __launch_bounds__(kBlock) void eloc_divide_kernel(double *__restrict__ acc, const double *__restrict__ psi0, int64_t n) {
@@ -800,137 +694,30 @@ __global__ __launch_bounds__(kBlock) void eloc_divide_kernel(double *__restrict_
   }
 }
 
-// -------------------------------------------------------------------------------------------------
-// REDUCE front end: keep |h| >= eps (vmc/energy/eloc.py:297-298).  Two passes over the tile scheduler of the drop-in
-// kernel (plan_tiles.h), one workgroup per (walker, chunk), no workgroup barrier after the table build, no atomics:
-//   count: tile_counts[walker][chunk][tile] = kept columns of that tile (a wave owns a tile and visits its columns
-//          in a fixed order; the running count lives in a wave-private LDS word because some columns are produced
-//          inside divergent code)
-//   emit : the caller turns the counts into exclusive offsets; the wave writes its tile's records from there.
-// Records of a walker are therefore contiguous and in a reproducible order (tile by tile: diagonal and odd columns,
-// singles, the three classes of doubles), not in ascending column order: kept_col says which column each one is.
-template <int LEN, typename T, bool EMIT>
-struct ReduceSink {
-  T eps;
-  volatile uint32_t *run;              // this wave's running count inside the current tile (LDS)
-  uint32_t *__restrict__ tile_counts;  // count pass: this workgroup's slice
-  const int64_t *__restrict__ tile_off;  // emit pass: this workgroup's slice
-  int32_t *__restrict__ kept_col;
-  uint64_t *__restrict__ kept_onv;
-  T *__restrict__ kept_h;
-  uint32_t tile;    // current tile (0xffffffff: none)
-  int64_t base;     // emit: first record of the current tile
-
-  __device__ __forceinline__ void flush() {
-    if constexpr (!EMIT) {
-      if (tile != 0xffffffffu && (threadIdx.x & 63) == 0) tile_counts[tile] = *run;
-    }
-  }
-  __device__ __forceinline__ void tile_begin(uint32_t t) {
-    flush();
-    tile = t;
-    if ((threadIdx.x & 63) == 0) *run = 0;
-    if constexpr (EMIT) base = tile_off[t];
-  }
-  // emit pass: a tile that keeps nothing (the next offset equals this one) is not enumerated again (plan_tiles.h).
-  // `tiles_left` = entries of the offset array from this workgroup's slice to its end.
-  uint64_t tiles_left;
-  __device__ __forceinline__ bool skip_tile(uint32_t t) const {
-    if constexpr (EMIT) return (uint64_t)t + 1 < tiles_left && tile_off[t + 1] == tile_off[t];
-    else return false;
-  }
-  __device__ __forceinline__ void put(int64_t pos, uint32_t col, T h, const uint64_t (&ket)[LEN]) const {
-    kept_col[pos] = (int32_t)col;
-    kept_h[pos] = h;
-#pragma unroll
-    for (int i = 0; i < LEN; ++i) kept_onv[pos * LEN + i] = ket[i];
-  }
-  // adds `total` to the wave's running count and returns its previous value to all ACTIVE lanes
-  __device__ __forceinline__ uint32_t advance(uint32_t total) const {
-    const int lane = threadIdx.x & 63;
-    const int leader = __ffsll((long long)__ballot(1)) - 1;
-    uint32_t before = 0;
-    if (lane == leader) { before = *run; *run = before + total; }
-    return __shfl(before, leader);
-  }
-  __device__ __forceinline__ void one(uint32_t col, T h, const uint64_t (&ket)[LEN]) const {
-    const bool k = fabs(h) >= eps;
-    const uint64_t m = __ballot(k);
-    if (!m) return;
-    const uint32_t before = advance((uint32_t)__popcll(m));
-    if constexpr (EMIT) {
-      const int lane = threadIdx.x & 63;
-      if (k) put(base + before + __popcll(m & ((1ull << lane) - 1ull)), col, h, ket);
-    }
-  }
-  __device__ __forceinline__ void two(uint32_t c0, T h0, const uint64_t (&k0)[LEN], uint32_t c1, T h1, const uint64_t (&k1)[LEN]) const {
-    const bool a = fabs(h0) >= eps, b = fabs(h1) >= eps;
-    const uint64_t ma = __ballot(a), mb = __ballot(b);
-    if (!(ma | mb)) return;
-    const uint32_t before = advance((uint32_t)(__popcll(ma) + __popcll(mb)));
-    if constexpr (EMIT) {
-      const int lane = threadIdx.x & 63;
-      const uint64_t below = (1ull << lane) - 1ull;
-      const int64_t mine = base + before + __popcll(ma & below) + __popcll(mb & below);
-      if (a) put(mine, c0, h0, k0);
-      if (b) put(mine + (a ? 1 : 0), c1, h1, k1);
-    }
-  }
-  __device__ __forceinline__ void pair(uint32_t col, T h0, T h1, const uint64_t (&k0)[LEN], const uint64_t (&k1)[LEN]) const {
-    two(col, h0, k0, col + 1, h1, k1);
-  }
-};
-
-template <int LEN, typename T, bool EMIT>
-__global__ __launch_bounds__(kBlock) void reduce_tiles_kernel(const uint64_t *__restrict__ bra, SDParams p, PlanLayout pl,
-                                                              uint32_t nchunks, uint32_t chunk_len, uint32_t max_tiles, bool xcd_map,
-                                                              const T *__restrict__ plan, T eps, uint32_t *__restrict__ tile_counts,
-                                                              const int64_t *__restrict__ tile_off, int32_t *__restrict__ kept_col,
-                                                              uint64_t *__restrict__ kept_onv, T *__restrict__ kept_h) {
-  extern __shared__ __attribute__((aligned(16))) unsigned char smem[];
-  __shared__ uint32_t wave_run[kBlock / 64];
-  __shared__ uint32_t next_tile;
-  uint64_t walker;
-  uint32_t chunk;
-  map_workgroup(nchunks, xcd_map, walker, chunk);
-  const uint64_t slot = walker * nchunks + chunk;  // position of this (walker, chunk) in the per-tile arrays
-  const int tid = threadIdx.x;
-  if (tid == 0) next_tile = 0;
-  Walker<LEN> wk;
-  load_walker<LEN>(bra + walker * LEN, wk);
-  const LdsLayout L = carve_lds(smem, p);
-  const int nocc = build_walker_tables<LEN>(wk, p, L);
-  ReduceSink<LEN, T, EMIT> sink{eps, wave_run + (tid >> 6), EMIT ? nullptr : tile_counts + slot * max_tiles,
-                                EMIT ? tile_off + slot * max_tiles : nullptr, kept_col, kept_onv, kept_h, 0xffffffffu, 0,
-                                ((uint64_t)gridDim.x - slot) * max_tiles};
-  visit_tiles<LEN, T>(p, pl, L, nocc, plan, wk, nchunks, chunk, chunk_len, 0u, &next_tile, sink);
-  sink.flush();
-}
-
 }  // namespace pynqs
 
 // =================================================================================================
 using namespace pynqs;
 
-static int eloc_common_checks(int sorb, int nele, int noA, int noB, int64_t nbatch, SDParams *p, PlanLayout *pl) {
-  if (!make_sd_params(sorb, nele, noA, noB, p)) return set_error(PYNQS_EINVAL, "bad sorb/noA/noB");
-  if (!make_plan_layout(sorb, pl)) return set_error(PYNQS_EINVAL, "plan needs an even sorb in [2, 192]");
-  if (nbatch < 0 || nbatch > 0x7fffffffll) return set_error(PYNQS_EINVAL, "bad nbatch");
-  return PYNQS_OK;
+void pynqs::eloc_divide(double *acc, const double *psi0, int64_t nbatch, bool cplx, hipStream_t st) {
+  const uint32_t grid = (uint32_t)((nbatch + kBlock - 1) / kBlock);
+  if (cplx) hipLaunchKernelGGL((eloc_divide_kernel<true>), dim3(grid), dim3(kBlock), 0, st, acc, psi0, nbatch);
+  else hipLaunchKernelGGL((eloc_divide_kernel<false>), dim3(grid), dim3(kBlock), 0, st, acc, psi0, nbatch);
 }
 
-static int eloc_sample_space_impl(const uint64_t *bra, int64_t nbatch, int sorb, int nele, int noA, int noB, const void *plan,
-                                  const uint64_t *keys, int64_t nkeys, bool hash, const double *wf, int wf_is_complex,
-                                  double *eloc, double *psi0, void *stream, bool flip = false) {
-  SDParams p;
-  PlanLayout pl;
-  int rc = eloc_common_checks(sorb, nele, noA, noB, nbatch, &p, &pl);
-  if (rc != PYNQS_OK) return rc;
-  if (nbatch == 0) return PYNQS_OK;
-  if (!bra || !plan || !eloc || !psi0 || nkeys < 0 || (nkeys > 0 && (!keys || !wf))) return set_error(PYNQS_EINVAL, "null pointer");
-  const int len = (sorb - 1) / 64 + 1;
-  hipStream_t st = (hipStream_t)stream;
+// The form a column-major launch takes: which kernel (sorted keys / hash table without filters / filtered), one or two filter levels,
+// workgroup size, block sweeps or the rank-by-rank scan, string prefilter, filter sizes, LDS bytes and the chunks of a walker's row.
+// The five environment overrides are read here and nowhere else.
+enum { kSsSorted = 0, kSsHash = 1, kSsFiltered = 2 };
+struct SsForm {
+  int kind, block;
+  bool two_level, sweep, pre;
+  uint32_t fbits, f2bits, sbits, nchunks, chunk_len;
+  size_t lds;
+};
+static SsForm ss_form(const SDParams &p, int64_t nbatch, int64_t nkeys, bool hash) {
   uint32_t nchunks, chunk_len;
+  const int sorb = p.sorb, len = (sorb - 1) / 64 + 1;
   plan_chunks(nbatch, p.nsd + 1, &nchunks, &chunk_len);
   const uint32_t fbits = hash ? hash_filter_bits(nkeys) : 0u;
   // second-level filter when the LDS one has fewer than 6 bits per key (it then lets > 8 % of the columns through);
@@ -964,73 +751,80 @@ static int eloc_sample_space_impl(const uint64_t *bra, int64_t nbatch, int sorb,
   const uint32_t sbits = hash && fbits ? hash_string_bits(nkeys) : 0u;
   const bool pre = pre_env && filtered && sbits && !sweep && block == kBlock && p.nSa > 0 && p.nSb > 0;
   const size_t lds = lds_fixed + (filtered ? filtered_extra_lds(fbits, sorb, two_level, block) : 0) + (pre ? pre_lds_bytes(p) : 0);
+  return SsForm{filtered ? kSsFiltered : (hash ? kSsHash : kSsSorted), block, two_level, sweep, pre, fbits, f2bits, sbits, nchunks, chunk_len, lds};
+}
+
+extern "C" int pynqs_eloc_sample_space_form(int64_t nbatch, int sorb, int nele, int noA, int noB, int64_t nkeys, int hash, int64_t out[8]) {
+  SDParams p;
+  PlanLayout pl;
+  const int rc = eloc_common_checks(sorb, nele, noA, noB, nbatch, nkeys, &p, &pl);
+  if (rc != PYNQS_OK) return rc;
+  if (nbatch < 1 || !out) return set_error(PYNQS_EINVAL, "bad nbatch / out");
+  const SsForm f = ss_form(p, nbatch, nkeys, hash != 0);
+  const int64_t v[8] = {f.kind, f.two_level, f.block, f.sweep, f.pre, (int64_t)f.lds, f.nchunks, f.chunk_len};
+  for (int i = 0; i < 8; ++i) out[i] = v[i];
+  return PYNQS_OK;
+}
+
+static int eloc_sample_space_impl(const uint64_t *bra, int64_t nbatch, int sorb, int nele, int noA, int noB, const void *plan,
+                                  const uint64_t *keys, int64_t nkeys, bool hash, const double *wf, int wf_is_complex,
+                                  double *eloc, double *psi0, void *stream, bool flip = false) {
+  pynqs::DeviceScope device_scope_(bra);
+  SDParams p;
+  PlanLayout pl;
+  int rc = eloc_common_checks(sorb, nele, noA, noB, nbatch, nkeys, &p, &pl);
+  if (rc != PYNQS_OK) return rc;
+  if (nbatch == 0) return PYNQS_OK;
+  if (!bra || !plan || !eloc || !psi0 || (nkeys > 0 && (!keys || !wf))) return set_error(PYNQS_EINVAL, "null pointer");
+  const int len = (sorb - 1) / 64 + 1;
+  hipStream_t st = (hipStream_t)stream;
+  const SsForm form = ss_form(p, nbatch, nkeys, hash);
+  const uint32_t nchunks = form.nchunks;
   const uint64_t grid = (uint64_t)nbatch * nchunks;
   if (grid > 0x7fffffffull) return set_error(PYNQS_EINVAL, "grid too large");
   const size_t esz = wf_is_complex ? 16 : 8;
   if (nchunks > 1 && hipMemsetAsync(eloc, 0, esz * (size_t)nbatch, st) != hipSuccess) return check_launch("memset");
-  const double *pd = (const double *)plan;
   const int64_t size_arg = hash ? (int64_t)hash_capacity(nkeys) : nkeys;
-#define PYNQS_SS_ARGS dim3((uint32_t)grid), dim3(block), lds, st, bra, p, pl, nchunks, chunk_len, xcd_mapping(nchunks), pd, keys, size_arg, wf, eloc, psi0, flip
-#define PYNQS_SS_LAUNCH(KERNEL, ...)                                                                                              \
-  do {                                                                                                                            \
-    if (lds > 64 * 1024 && hipFuncSetAttribute(reinterpret_cast<const void *>(&KERNEL), hipFuncAttributeMaxDynamicSharedMemorySize, \
-                                               (int)lds) != hipSuccess)                                                           \
-      return check_launch("hipFuncSetAttribute");                                                                                \
-    hipLaunchKernelGGL((KERNEL), PYNQS_SS_ARGS, ##__VA_ARGS__);                                                                   \
-  } while (0)
-#define PYNQS_SS_FILTERED2(B, SW, PR)                                                                                              \
-  do {                                                                                                                             \
-    if (two_level) {                                                                                                               \
-      if (wf_is_complex) PYNQS_SS_LAUNCH((eloc_sample_space_filtered_kernel<LEN, true, true, B, SW, PR>), fbits, f2bits, sbits);    \
-      else PYNQS_SS_LAUNCH((eloc_sample_space_filtered_kernel<LEN, false, true, B, SW, PR>), fbits, f2bits, sbits);                \
-    } else {                                                                                                                       \
-      if (wf_is_complex) PYNQS_SS_LAUNCH((eloc_sample_space_filtered_kernel<LEN, true, false, B, SW, PR>), fbits, f2bits, sbits);   \
-      else PYNQS_SS_LAUNCH((eloc_sample_space_filtered_kernel<LEN, false, false, B, SW, PR>), fbits, f2bits, sbits);               \
-    }                                                                                                                              \
-  } while (0)
-#define PYNQS_SS_FILTERED(B) do { if (sweep) PYNQS_SS_FILTERED2(B, true, false); else PYNQS_SS_FILTERED2(B, false, false); } while (0)
-#define PYNQS_SS_FILTERED_PRE() PYNQS_SS_FILTERED2(kBlock, false, true)
-  DISPATCH_LEN(len, {
-    if (filtered) {  // hash table with its filters
-      if (pre) {
-        PYNQS_SS_FILTERED_PRE();
-      } else if constexpr (LEN >= 2) {
-        if (block == 1024) PYNQS_SS_FILTERED(1024);
-        else if (block == kBigBlock) PYNQS_SS_FILTERED(kBigBlock);
-        else PYNQS_SS_FILTERED(kBlock);
-      } else {
-        PYNQS_SS_FILTERED(kBlock);
-      }
-    } else if (wf_is_complex) {
-      if (hash) PYNQS_SS_LAUNCH((eloc_sample_space_kernel<LEN, true, true>)); else PYNQS_SS_LAUNCH((eloc_sample_space_kernel<LEN, true, false>));
-    } else {
-      if (hash) PYNQS_SS_LAUNCH((eloc_sample_space_kernel<LEN, false, true>)); else PYNQS_SS_LAUNCH((eloc_sample_space_kernel<LEN, false, false>));
-    }
-  });
-#undef PYNQS_SS_FILTERED_PRE
-#undef PYNQS_SS_FILTERED
-#undef PYNQS_SS_FILTERED2
-#undef PYNQS_SS_ARGS
-#undef PYNQS_SS_LAUNCH
-  if (nchunks > 1) {  // (one chunk per walker: the kernel divided by psi(x) itself)
-    const uint32_t g2 = (uint32_t)((nbatch + kBlock - 1) / kBlock);
-    if (wf_is_complex) hipLaunchKernelGGL((eloc_divide_kernel<true>), dim3(g2), dim3(kBlock), 0, st, eloc, psi0, nbatch);
-    else hipLaunchKernelGGL((eloc_divide_kernel<false>), dim3(g2), dim3(kBlock), 0, st, eloc, psi0, nbatch);
-  }
+  // every kernel takes the same leading arguments; the filtered one the filter sizes after them
+  auto launch = [&](auto kernel, auto... filter_bits) {
+    return ss_launch(kernel, (uint32_t)grid, (uint32_t)form.block, form.lds, st, bra, p, pl, nchunks, form.chunk_len, xcd_mapping(nchunks),
+                     (const double *)plan, keys, size_arg, wf, eloc, psi0, flip, filter_bits...);
+  };
+  DISPATCH_LEN(len, rc = with_bool(wf_is_complex, [&](auto cplx) {
+    constexpr bool CPLX = decltype(cplx)::value;
+    if (form.kind != kSsFiltered)
+      return with_bool(hash, [&](auto h) { return launch(eloc_sample_space_kernel<LEN, CPLX, decltype(h)::value>); });
+    return with_bool(form.two_level, [&](auto two) {  // hash table with its filters
+      constexpr bool TWO = decltype(two)::value;
+      auto filtered = [&](auto block, auto sweep, auto pre) {
+        return launch(eloc_sample_space_filtered_kernel<LEN, CPLX, TWO, decltype(block)::value, decltype(sweep)::value, decltype(pre)::value>,
+                      form.fbits, form.f2bits, form.sbits);
+      };
+      // (the string prefilter goes with 256 threads and the rank scan only; one-word systems never get larger workgroups)
+      if (form.pre) return filtered(std::integral_constant<int, kBlock>{}, std::false_type{}, std::true_type{});
+      return with_bool(form.sweep, [&](auto sweep) {
+        if constexpr (LEN >= 2) {
+          if (form.block == 1024) return filtered(std::integral_constant<int, 1024>{}, sweep, std::false_type{});
+          if (form.block == kBigBlock) return filtered(std::integral_constant<int, kBigBlock>{}, sweep, std::false_type{});
+        }
+        return filtered(std::integral_constant<int, kBlock>{}, sweep, std::false_type{});
+      });
+    });
+  }));
+  if (rc != PYNQS_OK) return rc;
+  if (nchunks > 1) eloc_divide(eloc, psi0, nbatch, wf_is_complex != 0, st);  // (one chunk per walker: the kernel divided by psi(x) itself)
   return check_launch("eloc_sample_space");
 }
 
 extern "C" int pynqs_eloc_sample_space(const uint64_t *bra, int64_t nbatch, int sorb, int nele, int noA, int noB,
                                        const void *plan, const uint64_t *keys, int64_t nkeys, const double *wf,
                                        int wf_is_complex, double *eloc, double *psi0, void *stream) {
-  pynqs::DeviceScope device_scope_(bra);
   return eloc_sample_space_impl(bra, nbatch, sorb, nele, noA, noB, plan, keys, nkeys, false, wf, wf_is_complex, eloc, psi0, stream);
 }
 
 extern "C" int pynqs_eloc_sample_space_hash(const uint64_t *bra, int64_t nbatch, int sorb, int nele, int noA, int noB,
                                             const void *plan, const void *table, int64_t nkeys, const double *wf,
                                             int wf_is_complex, double *eloc, double *psi0, void *stream) {
-  pynqs::DeviceScope device_scope_(bra);
   return eloc_sample_space_impl(bra, nbatch, sorb, nele, noA, noB, plan, (const uint64_t *)table, nkeys, true, wf, wf_is_complex,
                                 eloc, psi0, stream);
 }
@@ -1041,120 +835,12 @@ extern "C" int pynqs_eloc_sample_space_hash(const uint64_t *bra, int64_t nbatch,
 extern "C" int pynqs_eloc_sample_space_flip(const uint64_t *bra, int64_t nbatch, int sorb, int nele, int noA, int noB,
                                             const void *plan, const uint64_t *keys, int64_t nkeys, const double *wf,
                                             int wf_is_complex, const double *psi0, double *out, void *stream) {
-  pynqs::DeviceScope device_scope_(bra);
   return eloc_sample_space_impl(bra, nbatch, sorb, nele, noA, noB, plan, keys, nkeys, false, wf, wf_is_complex, out, (double *)psi0, stream, true);
 }
 
 extern "C" int pynqs_eloc_sample_space_hash_flip(const uint64_t *bra, int64_t nbatch, int sorb, int nele, int noA, int noB,
                                                  const void *plan, const void *table, int64_t nkeys, const double *wf,
                                                  int wf_is_complex, const double *psi0, double *out, void *stream) {
-  pynqs::DeviceScope device_scope_(bra);
   return eloc_sample_space_impl(bra, nbatch, sorb, nele, noA, noB, plan, (const uint64_t *)table, nkeys, true, wf, wf_is_complex, out,
                                 (double *)psi0, stream, true);
-}
-
-extern "C" int64_t pynqs_hash_bytes(int64_t nkeys, int sorb) {
-  if (nkeys < 0 || sorb < 1 || sorb > kMaxSorb) return -1;
-  const int len = (sorb - 1) / 64 + 1;
-  return (int64_t)(hash_capacity(nkeys) * (uint64_t)hash_slot_words(len) * 8 + hash_filter_bits(nkeys) / 8 + hash_filter2_bits(nkeys) / 8 +
-                   2 * (size_t)hash_string_bits_if(nkeys) / 8);
-}
-
-extern "C" int pynqs_hash_build(const uint64_t *keys, int64_t nkeys, int sorb, void *table, void *stream) {
-  pynqs::DeviceScope device_scope_(keys);
-  if (nkeys < 0 || sorb < 1 || sorb > kMaxSorb) return set_error(PYNQS_EINVAL, "bad nkeys/sorb");
-  if (!table || (nkeys > 0 && !keys)) return set_error(PYNQS_EINVAL, "null pointer");
-  const int len = (sorb - 1) / 64 + 1;
-  const uint64_t cap = hash_capacity(nkeys);
-  hipStream_t st = (hipStream_t)stream;
-  if ((uintptr_t)table & 15u) return set_error(PYNQS_EINVAL, "table must be 16-byte aligned");
-  const size_t slot_bytes = cap * (size_t)hash_slot_words(len) * 8;
-  const uint32_t fbits = hash_filter_bits(nkeys);
-  if (hipMemsetAsync(table, 0xFF, slot_bytes, st) != hipSuccess) return check_launch("hash memset");
-  const uint32_t f2bits = hash_filter2_bits(nkeys), sbits = hash_string_bits_if(nkeys);
-  if ((fbits || f2bits) && hipMemsetAsync((char *)table + slot_bytes, 0, fbits / 8 + f2bits / 8 + 2 * (size_t)sbits / 8, st) != hipSuccess)
-    return check_launch("filter memset");
-  if (nkeys == 0) return PYNQS_OK;
-  const uint32_t grid = (uint32_t)((nkeys + kBlock - 1) / kBlock);
-  DISPATCH_LEN(len, hipLaunchKernelGGL((hash_build_kernel<LEN>), dim3(grid), dim3(kBlock), 0, st, keys, nkeys, cap, (uint64_t *)table, fbits, f2bits, sbits));
-  return check_launch("hash_build");
-}
-
-extern "C" int pynqs_hash_lookup(const void *table, int64_t nkeys, const uint64_t *onv, int64_t n, int sorb, int64_t *idx,
-                                 uint8_t *mask, void *stream) {
-  pynqs::DeviceScope device_scope_(table);
-  if (nkeys < 0 || n < 0 || sorb < 1 || sorb > kMaxSorb) return set_error(PYNQS_EINVAL, "bad nkeys/n/sorb");
-  if (n == 0) return PYNQS_OK;
-  if (!table || !onv || !idx || !mask) return set_error(PYNQS_EINVAL, "null pointer");
-  const int len = (sorb - 1) / 64 + 1;
-  const uint64_t grid = ((uint64_t)n + kBlock - 1) / kBlock;
-  if (grid > 0x7fffffffull) return set_error(PYNQS_EINVAL, "n too large for one launch");
-  hipStream_t st = (hipStream_t)stream;
-  DISPATCH_LEN(len, hipLaunchKernelGGL((hash_lookup_kernel<LEN>), dim3((uint32_t)grid), dim3(kBlock), 0, st, (const uint64_t *)table,
-                                       hash_capacity(nkeys), onv, (uint64_t)n, idx, mask));
-  return check_launch("hash_lookup");
-}
-
-static int reduce_geometry(int64_t nbatch, const SDParams &p, uint32_t *nchunks, uint32_t *chunk_len, uint32_t *max_tiles) {
-  plan_chunks(nbatch, p.nsd + 1, nchunks, chunk_len);
-  *max_tiles = max_tiles_per_chunk(p, *nchunks, *chunk_len);
-  return 0;
-}
-
-extern "C" int64_t pynqs_reduce_tiles(int64_t nbatch, int sorb, int nele, int noA, int noB) {
-  SDParams p;
-  if (nbatch < 0 || !make_sd_params(sorb, nele, noA, noB, &p)) return -1;
-  uint32_t nchunks, chunk_len, max_tiles;
-  reduce_geometry(nbatch, p, &nchunks, &chunk_len, &max_tiles);
-  return (int64_t)nchunks * max_tiles;
-}
-
-template <bool EMIT>
-static int launch_reduce(const uint64_t *bra, int64_t nbatch, int sorb, int nele, int noA, int noB, const void *plan, int dtype,
-                         double eps, uint32_t *tile_counts, const int64_t *tile_off, int32_t *kept_col, uint64_t *kept_onv,
-                         void *kept_h, void *stream) {
-  SDParams p;
-  PlanLayout pl;
-  int rc = eloc_common_checks(sorb, nele, noA, noB, nbatch, &p, &pl);
-  if (rc != PYNQS_OK) return rc;
-  if (dtype != PYNQS_F32 && dtype != PYNQS_F64) return set_error(PYNQS_EINVAL, "bad dtype");
-  if (nbatch == 0) return PYNQS_OK;
-  if (!bra || !plan) return set_error(PYNQS_EINVAL, "null pointer");
-  if (EMIT ? (!tile_off || !kept_col || !kept_onv || !kept_h) : !tile_counts) return set_error(PYNQS_EINVAL, "null pointer");
-  const int len = (sorb - 1) / 64 + 1;
-  hipStream_t st = (hipStream_t)stream;
-  const size_t esz = dtype == PYNQS_F64 ? 8 : 4;
-  uint32_t nchunks, chunk_len, max_tiles;
-  reduce_geometry(nbatch, p, &nchunks, &chunk_len, &max_tiles);
-  const uint64_t grid = (uint64_t)nbatch * nchunks;
-  if (grid > 0x7fffffffull) return set_error(PYNQS_EINVAL, "grid too large");
-  const size_t lds = lds_bytes(p, esz);
-  // tiles a workgroup does not have keep the count 0
-  if (!EMIT && hipMemsetAsync(tile_counts, 0, 4 * (size_t)grid * max_tiles, st) != hipSuccess) return check_launch("memset");
-  DISPATCH_LEN(len, {
-    if (dtype == PYNQS_F64)
-      hipLaunchKernelGGL((reduce_tiles_kernel<LEN, double, EMIT>), dim3((uint32_t)grid), dim3(kBlock), lds, st, bra, p, pl, nchunks,
-                         chunk_len, max_tiles, xcd_mapping(nchunks), (const double *)plan, eps, tile_counts, tile_off, kept_col, kept_onv,
-                         (double *)kept_h);
-    else
-      hipLaunchKernelGGL((reduce_tiles_kernel<LEN, float, EMIT>), dim3((uint32_t)grid), dim3(kBlock), lds, st, bra, p, pl, nchunks,
-                         chunk_len, max_tiles, xcd_mapping(nchunks), (const float *)plan, (float)eps, tile_counts, tile_off, kept_col,
-                         kept_onv, (float *)kept_h);
-  });
-  return check_launch(EMIT ? "reduce_emit" : "reduce_count");
-}
-
-extern "C" int pynqs_reduce_count(const uint64_t *bra, int64_t nbatch, int sorb, int nele, int noA, int noB, const void *plan,
-                                  int dtype, double eps, uint32_t *tile_counts, void *stream) {
-  pynqs::DeviceScope device_scope_(bra);
-  return launch_reduce<false>(bra, nbatch, sorb, nele, noA, noB, plan, dtype, eps, tile_counts, nullptr, nullptr, nullptr, nullptr,
-                              stream);
-}
-
-extern "C" int pynqs_reduce_emit(const uint64_t *bra, int64_t nbatch, int sorb, int nele, int noA, int noB, const void *plan,
-                                 int dtype, double eps, const int64_t *tile_offsets, int32_t *kept_col, uint64_t *kept_onv,
-                                 void *kept_h, void *stream) {
-  pynqs::DeviceScope device_scope_(bra);
-  return launch_reduce<true>(bra, nbatch, sorb, nele, noA, noB, plan, dtype, eps, nullptr, tile_offsets, kept_col, kept_onv, kept_h,
-                             stream);
 }

@@ -26,8 +26,7 @@
 #include "launch.h"
 #include "plan.h"
 #include "plan_dev.h"
-
-#include <type_traits>
+#include "ss_common.h"
 
 namespace pynqs {
 
@@ -39,21 +38,8 @@ constexpr int kKeysWalkers = PYNQS_KEYS_W;   // walkers per wave (their 32-bit f
 #define PYNQS_INDEX_W 1
 #endif
 constexpr int kIndexWalkers = PYNQS_INDEX_W;  // ... of the INDEXED form: nothing is shared between the walkers of a wave there but the queues
+constexpr int64_t kMaxKeys = (1ll << 27) - 1;  // a parked candidate is walker << 28 | eta_m << 27 | key number
 constexpr uint32_t kKeysQueue = 128;  // < 64 left over + 64 parked by one comparison
-
-// alpha <-> beta occupations exchanged in place; returns true if eta_m = (-1)^(doubly occupied spatial orbitals) is -1 (the same for
-// a determinant and its partner)
-template <int LEN>
-__device__ __forceinline__ bool spin_flip_ket_keys(uint64_t (&ket)[LEN]) {
-  uint32_t pairs = 0;
-#pragma unroll
-  for (int i = 0; i < LEN; ++i) {
-    const uint64_t w = ket[i];
-    pairs += (uint32_t)__popcll(w & (w >> 1) & 0x5555555555555555ull);
-    ket[i] = ((w >> 1) & 0x5555555555555555ull) | ((w & 0x5555555555555555ull) << 1);
-  }
-  return pairs & 1u;
-}
 
 template <int LEN>
 __device__ __forceinline__ int lowest_bit(const uint64_t (&m)[LEN]) {
@@ -228,8 +214,7 @@ __global__ __launch_bounds__(kBlock) void eloc_sample_space_keys_kernel(const ui
           }
         }
         if (minus) h = -h;
-        if constexpr (CPLX) { vr = wf[2 * k]; vi = wf[2 * k + 1]; }
-        else vr = wf[k];
+        table_value<CPLX>(wf, k, vr, vi);
       }
     }
     count = __builtin_amdgcn_readfirstlane(count - n);
@@ -264,7 +249,7 @@ __global__ __launch_bounds__(kBlock) void eloc_sample_space_keys_kernel(const ui
     if (__ballot(in && cnt == 0)) {  // the key equal to the walker itself (keys are distinct: one lane, once per walker and launch)
       const double hd = diagonal(w);
       if (in && cnt == 0) {
-        double vr, vi = 0.0;
+        double vr, vi = 0.0;  // (not table_value: with it here the streamed one-word real form takes 96 VGPRs instead of 94)
         if constexpr (CPLX) { vr = wf[2 * k]; vi = wf[2 * k + 1]; }
         else vr = wf[k];
         const double hh = minus ? -hd : hd;
@@ -275,11 +260,7 @@ __global__ __launch_bounds__(kBlock) void eloc_sample_space_keys_kernel(const ui
             if constexpr (CPLX) aim[i] = fma(hh, vi, aim[i]);
           }
         }
-        if (!flip) {
-          double *__restrict__ out = psi0 + (CPLX ? 2 : 1) * (wbase + w);
-          out[0] = vr;
-          if constexpr (CPLX) out[1] = vi;
-        }
+        store_psi0<CPLX>(psi0 + (CPLX ? 2 : 1) * (wbase + w), vr, vi, flip);
       }
     }
     park(Doubles{}, code, y, in && cnt == 4);
@@ -296,7 +277,7 @@ __global__ __launch_bounds__(kBlock) void eloc_sample_space_keys_kernel(const ui
       uint64_t xw[LEN];
 #pragma unroll
       for (int i = 0; i < LEN; ++i) xw[i] = xs[wave][w][i];
-      if (flip) (void)spin_flip_ket_keys<LEN>(xw);  // flip(key) agrees with x in a block  <=>  the key agrees with flip(x) in it
+      if (flip) (void)spin_flip_ket<LEN>(xw);  // flip(key) agrees with x in a block  <=>  the key agrees with flip(x) in it
       int lo_bit = 0, hi_bit = 0;
 #pragma unroll
       for (int bb = 0; bb < NB; ++bb)
@@ -348,7 +329,7 @@ __global__ __launch_bounds__(kBlock) void eloc_sample_space_keys_kernel(const ui
         uint64_t y[LEN];
 #pragma unroll
         for (int i = 0; i < LEN; ++i) y[i] = in ? keys[k * LEN + i] : 0ull;
-        const uint32_t minus = flip && spin_flip_ket_keys<LEN>(y) ? (1u << 27) : 0u;
+        const uint32_t minus = flip && spin_flip_ket<LEN>(y) ? (1u << 27) : 0u;
         int cnt = 0;
         bool counted_before = false;
         uint64_t d[LEN];
@@ -394,7 +375,7 @@ __global__ __launch_bounds__(kBlock) void eloc_sample_space_keys_kernel(const ui
     for (int u = 0; u < U; ++u) {
       const int64_t k = k0 + 64 * u + lane;
       const bool in = k < k_hi;
-      const uint32_t minus = flip && spin_flip_ket_keys<LEN>(y[u]) ? (1u << 27) : 0u;  // y <- x' = flip(key); eta_m(x') = eta_m(key)
+      const uint32_t minus = flip && spin_flip_ket<LEN>(y[u]) ? (1u << 27) : 0u;  // y <- x' = flip(key); eta_m(x') = eta_m(key)
       // the cheap test (spin sectors and hole / particle balance are checked by the evaluation).  Common path: the 32-bit FOLD of a
       // determinant (XOR of its 32-bit quarters): folding never increases a Hamming distance, so fold(x) ^ fold(y) with more than four
       // bits set rules the pair out -- one xor and one popcount per (walker, key) whatever the word count, and for the W walkers of a
@@ -451,46 +432,53 @@ __global__ __launch_bounds__(kBlock) void eloc_sample_space_keys_kernel(const ui
   }
 }
 
-template <bool CPLX>
-__global__ __launch_bounds__(kBlock) void eloc_divide_keys_kernel(double *__restrict__ acc, const double *__restrict__ psi0, int64_t n) {
-  const int64_t i = (int64_t)blockIdx.x * kBlock + threadIdx.x;
-  if (i >= n) return;
-  if constexpr (CPLX) {
-    const double a = acc[2 * i], b = acc[2 * i + 1];
-    scaled_cdiv(a, b, psi0[2 * i], psi0[2 * i + 1], acc[2 * i], acc[2 * i + 1]);
-  } else {
-    acc[i] = acc[i] / psi0[i];
-  }
-}
-
 }  // namespace pynqs
 
 using namespace pynqs;
 
-static int launch_keys(const uint64_t *bra, int64_t nbatch, int sorb, int nele, int noA, int noB, const void *plan, const uint64_t *keys,
-                       int64_t nkeys, const void *index, const double *wf, int wf_is_complex, int flip, double *eloc, double *psi0,
-                       void *stream) {
-  SDParams p;
-  PlanLayout pl;
-  if (!make_sd_params(sorb, nele, noA, noB, &p)) return set_error(PYNQS_EINVAL, "bad sorb/noA/noB");
-  if (!make_plan_layout(sorb, &pl)) return set_error(PYNQS_EINVAL, "plan needs an even sorb in [2, 192]");
-  if (nbatch < 0 || nkeys < 0 || nkeys >= (1ll << 27)) return set_error(PYNQS_EINVAL, "bad nbatch / nkeys (nkeys < 2^27)");
-  if (nbatch == 0) return PYNQS_OK;
-  if (!bra || !plan || !eloc || !psi0 || (nkeys > 0 && (!keys || !wf))) return set_error(PYNQS_EINVAL, "null pointer");
-  hipStream_t st = (hipStream_t)stream;
-  const size_t esz = wf_is_complex ? 16 : 8;
-  const int kPerGroup = (kBlock / 64) * (index ? kIndexWalkers : kKeysWalkers);  // walkers per workgroup
+// The chunk rule of a key-major launch: workgroups along the walkers (groups), chunks of the key array per group, keys per chunk.
+// PYNQS_KEYS_WG is read here and nowhere else.
+struct KeysForm {
+  int64_t groups, nchunks, chunk_len;
+};
+static KeysForm keys_form(int64_t nbatch, int64_t nkeys, bool indexed) {
+  const int kPerGroup = (kBlock / 64) * (indexed ? kIndexWalkers : kKeysWalkers);  // walkers per workgroup
   const int64_t groups = (nbatch + kPerGroup - 1) / kPerGroup;
   // streamed form: enough workgroups to fill the chip, chunks of at least 2048 keys (the indexed form has one workgroup per group)
   static const int64_t want = getenv("PYNQS_KEYS_WG") ? atoll(getenv("PYNQS_KEYS_WG")) : 4096;
-  int64_t nchunks = groups >= want || index ? 1 : (want + groups - 1) / groups;
+  int64_t nchunks = groups >= want || indexed ? 1 : (want + groups - 1) / groups;
   const int64_t maxc = (nkeys + 2047) / 2048;
   if (nchunks > maxc) nchunks = maxc;
   if (nchunks < 1) nchunks = 1;
   int64_t chunk_len = (nkeys + nchunks - 1) / nchunks;
   chunk_len = (chunk_len + 63) & ~(int64_t)63;
   if (chunk_len < 64) chunk_len = 64;
-  nchunks = nkeys > 0 && !index ? (nkeys + chunk_len - 1) / chunk_len : 1;
+  nchunks = nkeys > 0 && !indexed ? (nkeys + chunk_len - 1) / chunk_len : 1;
+  return KeysForm{groups, nchunks, chunk_len};
+}
+
+extern "C" int pynqs_eloc_sample_space_keys_form(int64_t nbatch, int sorb, int64_t nkeys, int indexed, int64_t out[3]) {
+  PlanLayout pl;
+  if (!make_plan_layout(sorb, &pl)) return set_error(PYNQS_EINVAL, "plan needs an even sorb in [2, 192]");
+  if (nbatch < 1 || nbatch > 0x7fffffffll || nkeys < 0 || nkeys > kMaxKeys || !out) return set_error(PYNQS_EINVAL, "bad nbatch / nkeys / out");
+  const KeysForm f = keys_form(nbatch, nkeys, indexed && nkeys > 0);  // (an empty table has no index: pynqs_eloc_sample_space_indexed streams)
+  out[0] = f.groups; out[1] = f.nchunks; out[2] = f.chunk_len;
+  return PYNQS_OK;
+}
+
+static int launch_keys(const uint64_t *bra, int64_t nbatch, int sorb, int nele, int noA, int noB, const void *plan, const uint64_t *keys,
+                       int64_t nkeys, const void *index, const double *wf, int wf_is_complex, int flip, double *eloc, double *psi0,
+                       void *stream) {
+  SDParams p;
+  PlanLayout pl;
+  if (const int rc = eloc_common_checks(sorb, nele, noA, noB, nbatch, nkeys, &p, &pl)) return rc;
+  if (nkeys > kMaxKeys) return set_error(PYNQS_EINVAL, "bad nkeys (nkeys < 2^27)");
+  if (nbatch == 0) return PYNQS_OK;
+  if (!bra || !plan || !eloc || !psi0 || (nkeys > 0 && (!keys || !wf))) return set_error(PYNQS_EINVAL, "null pointer");
+  hipStream_t st = (hipStream_t)stream;
+  const size_t esz = wf_is_complex ? 16 : 8;
+  const KeysForm form = keys_form(nbatch, nkeys, index != nullptr);
+  const int64_t groups = form.groups, nchunks = form.nchunks, chunk_len = form.chunk_len;
   const uint64_t grid = (uint64_t)groups * (uint64_t)nchunks;
   if (grid > 0x7fffffffull) return set_error(PYNQS_EINVAL, "grid too large");
   if (nchunks > 1 && hipMemsetAsync(eloc, 0, esz * (size_t)nbatch, st) != hipSuccess) return check_launch("memset");
@@ -498,22 +486,13 @@ static int launch_keys(const uint64_t *bra, int64_t nbatch, int sorb, int nele, 
   const int len = (sorb - 1) / 64 + 1;
   const uint64_t *svals = (const uint64_t *)index;
   const uint32_t *perm = index ? (const uint32_t *)(svals + (size_t)kIndexBlocks * (size_t)nkeys) : nullptr;
-#define PYNQS_KEYS_LAUNCH(C, I)                                                                                                             \
-  hipLaunchKernelGGL((eloc_sample_space_keys_kernel<LEN, C, I>), dim3((uint32_t)grid), dim3(kBlock), 0, st, bra, nbatch, p, pl, (uint32_t)nchunks, \
-                     chunk_len, (const double *)plan, keys, nkeys, svals, perm, wf, eloc, psi0, flip != 0)
-  DISPATCH_LEN(len, {
-    if (index) {
-      if (wf_is_complex) PYNQS_KEYS_LAUNCH(true, true);
-      else PYNQS_KEYS_LAUNCH(false, true);
-    } else {
-      if (wf_is_complex) PYNQS_KEYS_LAUNCH(true, false);
-      else PYNQS_KEYS_LAUNCH(false, false);
-    }
-  });
-#undef PYNQS_KEYS_LAUNCH
-  const uint32_t g2 = (uint32_t)((nbatch + kBlock - 1) / kBlock);
-  if (wf_is_complex) hipLaunchKernelGGL((eloc_divide_keys_kernel<true>), dim3(g2), dim3(kBlock), 0, st, eloc, psi0, nbatch);
-  else hipLaunchKernelGGL((eloc_divide_keys_kernel<false>), dim3(g2), dim3(kBlock), 0, st, eloc, psi0, nbatch);
+  DISPATCH_LEN(len, with_bool(wf_is_complex, [&](auto cplx) {
+    return with_bool(index != nullptr, [&](auto indexed) {
+      return ss_launch(eloc_sample_space_keys_kernel<LEN, decltype(cplx)::value, decltype(indexed)::value>, (uint32_t)grid, kBlock, 0, st, bra,
+                       nbatch, p, pl, (uint32_t)nchunks, chunk_len, (const double *)plan, keys, nkeys, svals, perm, wf, eloc, psi0, flip != 0);
+    });
+  }));
+  eloc_divide(eloc, psi0, nbatch, wf_is_complex != 0, st);
   return check_launch(index ? "eloc_sample_space_indexed" : "eloc_sample_space_keys");
 }
 
@@ -529,6 +508,5 @@ extern "C" int pynqs_eloc_sample_space_indexed(const uint64_t *bra, int64_t nbat
                                                int wf_is_complex, int flip, double *eloc, double *psi0, void *stream) {
   pynqs::DeviceScope device_scope_(bra);
   if (nkeys > 0 && !index) return set_error(PYNQS_EINVAL, "null index");
-  if (nkeys == 0) return launch_keys(bra, nbatch, sorb, nele, noA, noB, plan, keys, nkeys, nullptr, wf, wf_is_complex, flip, eloc, psi0, stream);
-  return launch_keys(bra, nbatch, sorb, nele, noA, noB, plan, keys, nkeys, index, wf, wf_is_complex, flip, eloc, psi0, stream);
+  return launch_keys(bra, nbatch, sorb, nele, noA, noB, plan, keys, nkeys, nkeys > 0 ? index : nullptr, wf, wf_is_complex, flip, eloc, psi0, stream);
 }

@@ -1,7 +1,7 @@
 // plan_tiles.h -- the tile scheduler shared by the plan-based kernels: visits every column of a walker's
 // row range exactly once and hands (column, <x|H|x'>, ket) to a sink.  The drop-in kernel's sink stores to
 // comb / Hmat (kernels_plan.hip); the fused local-energy kernel's sink looks psi(x') up and accumulates
-// (kernels_eloc.hip).
+// (kernels_eloc.hip); REDUCE's sinks count and emit the kept columns (kernels_reduce_tiles.hip).
 //
 // Work distribution inside a workgroup.  After the (workgroup-wide) table build there is NO barrier: every wave
 // pulls tiles from an LDS counter until none is left.  Tile 0 holds the odd jobs (the few unpaired columns and

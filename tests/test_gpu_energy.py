@@ -398,12 +398,25 @@ def _excite(rng, words, sorb, count, singles):
 
 @pytest.mark.parametrize("sorb,no,nkeys,use_hash", [(40, 5, 150, True), (40, 5, 200, True), (72, 6, 150, True), (72, 6, 200, True),
                                                     (136, 4, 3000, True), (136, 4, 5000, True), (40, 5, 300_000, True),
-                                                    (40, 5, 200, False), (136, 4, 3000, False)])
+                                                    (40, 5, 200, False), (136, 4, 3000, False),
+                                                    # one row per variant of the filtered kernel that no other GPU test takes (words, threads,
+                                                    # scan, levels as pynqs_eloc_sample_space_form answers for the table each row builds)
+                                                    (64, 16, 50, True), (64, 16, 200, True),            # 1 word, SWEEP, one / two levels
+                                                    (66, 3, 300_000, True), (66, 3, 20_000, True),      # 2 words, rank scan: 256 no PRE, 512 one level
+                                                    (104, 2, 3000, True),                               # 2 words, 512, rank scan, two levels
+                                                    (80, 8, 50, True), (80, 8, 200, True),              # 2 words, SWEEP, 256, one / two levels
+                                                    (114, 5, 10_000, True), (114, 5, 200, True),        # 2 words, SWEEP, 512, one / two levels
+                                                    (114, 5, 15_000, True),                             # 2 words, SWEEP, 1024, two levels
+                                                    (130, 2, 50, True), (130, 2, 300_000, True),        # 3 words: PRE; 256 rank scan, no PRE
+                                                    (138, 2, 300, True),                                # 3 words, 512, rank scan, one level
+                                                    (132, 2, 20_000, True), (138, 2, 3000, True),       # 3 words, 1024, rank scan, one / two levels
+                                                    (136, 4, 50, True),                                 # 3 words, SWEEP, 256, one level
+                                                    (136, 4, 20_000, True), (136, 4, 7000, True)])      # 3 words, SWEEP, 1024, one / two levels
 @pytest.mark.parametrize("key_major", [False, True])
 def test_sample_space_kernel_filter_levels(sorb, no, nkeys, use_hash, key_major):
     """The fused SAMPLE_SPACE kernel with its candidate filters (Zobrist hash in LDS; second level in global memory
-    when the first has < 6 bits per key: 200 and 5000 keys here, 150 and 3000 keys take the one-level kernel), without
-    them, and with the sorted-key search, against the oracle, on sample spaces that hold the walkers, singles and doubles of them, and unrelated determinants."""
+    when the first has < 6 bits per key: 200 and 3000 keys here, 150 and 5000 keys take the one-level kernel; which variant a row takes is
+    what pynqs_eloc_sample_space_form answers), on the second-level filter alone, and with the sorted-key search, against the oracle, on sample spaces that hold the walkers, singles and doubles of them, and unrelated determinants."""
     from oracle import oracle as O
     from pynqs_amd import energy, public_function as pf
 
@@ -422,7 +435,7 @@ def test_sample_space_kernel_filter_levels(sorb, no, nkeys, use_hash, key_major)
     h2 = rng.standard_normal(pair * (pair + 1) // 2)
     L = x.shape[1]
     tb = lambda w: torch.from_numpy(w.view(np.uint8).reshape(-1, 8 * L)).to(dev)
-    # 300 000 keys: more than the LDS filter takes (< 1 bit per key) -> the unfiltered hash kernel; use_hash False: the
+    # 300 000 keys: more than the LDS filter takes (< 1 bit per key) -> the second-level filter alone; use_hash False: the
     # binary search over the sorted keys, as the reference does
     old_flag = pf.USE_HASH
     pf.USE_HASH = use_hash

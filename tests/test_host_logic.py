@@ -88,6 +88,33 @@ def test_rbm_launch_decisions_are_unchanged(monkeypatch):
         assert len(got[key]) == len(want[key]) and not diff, (key, diff[:10])
 
 
+def test_ss_launch_decisions_are_unchanged(monkeypatch):
+    """Kernel kind, filter levels, workgroup size, sweep / rank scan, string prefilter, LDS bytes and chunks of the column-major
+    SAMPLE_SPACE launches (pynqs_eloc_sample_space_form), groups and chunks of the key-major ones (pynqs_eloc_sample_space_keys_form),
+    pynqs_hash_bytes and pynqs_reduce_tiles (host logic, no GPU) over systems x table sizes x batch sizes x hash / indexed, against the
+    values recorded when the rules had only just been moved, verbatim, into functions (tests/golden/ss_launch_forms.json, written by
+    tests/golden/make_golden_ss_launch.py): every value equal, no tolerance."""
+    import importlib.util
+    import json
+
+    from pynqs_amd import _native as N
+
+    spec = importlib.util.spec_from_file_location("make_golden_ss_launch", os.path.join(ROOT, "tests", "golden", "make_golden_ss_launch.py"))
+    rec = importlib.util.module_from_spec(spec)
+    spec.loader.exec_module(rec)
+    for k in [k for k in os.environ if k.startswith(rec.OVERRIDES)]:
+        monkeypatch.delenv(k)
+    want = json.load(open(os.path.join(ROOT, "tests", "golden", "ss_launch_forms.json")))
+    got = json.loads(json.dumps(rec.record(N.lib())))
+    assert (got["systems"], got["nkeys"], got["nbatch"]) == (want["systems"], want["nkeys"], want["nbatch"])
+    ns, nk, nb = len(want["systems"]), len(want["nkeys"]), len(want["nbatch"])
+    assert len(want["ss_form"]) == ns * nk * nb * 2 and len(want["keys_form"]) == nk * nb * 2 and len(want["hash_bytes"]) == ns * nk and len(want["reduce_tiles"]) == ns * nb
+    assert {0, 1, 1 << 18, (1 << 18) + 1, 1 << 20, 18496, 65536} <= set(want["nkeys"]) and want["nbatch"] == [1, 7, 1024, 8192]
+    for key in ("hash_bytes", "reduce_tiles", "ss_form", "keys_form"):
+        diff = [i for i, (a, b) in enumerate(zip(got[key], want[key])) if a != b]
+        assert len(got[key]) == len(want[key]) and not diff, (key, diff[:10])
+
+
 def test_integral_layout_matches_oracle():
     from pynqs_amd import C_extension as cx
 
