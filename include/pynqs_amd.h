@@ -260,6 +260,45 @@ int pynqs_crbm_table_build(const double *weights, const double *hidden_bias, con
 int pynqs_eloc_crbm(const uint64_t *bra, int64_t nbatch, int sorb, int nele, int noA, int noB, const void *plan,
                     const void *crbm_table, int nhidden, double log_scale, double *eloc, double *psi, void *stream);
 
+/* ---- SIMPLE method, energy gradient and amplitudes of a real RBM times a two-body Jastrow factor (kernels_rbm.hip JASTROW,
+ * kernels_jastrow.hip, kernels_rbm_forward.hip) ------------------------------------------------------------------------------------
+ *   psi(x) = exp(visible_bias . x + x^T M x) * prod_h 2 cosh(hidden_bias[h] + sum_o weights[h][o] x_o),  x_o = +1 / -1:
+ * the reference's Jastrow (vmc/ansatz/rbm/rbm_other.py, exp(sum_ij M_ij x_i x_j), prod_dim = 1) multiplied onto its RBMWavefunction with
+ * rbm_type "real" (vmc/ansatz/hybrid/multi.py).  jastrow = M: double[sorb][sorb] row-major, any real matrix (not symmetric, diagonal
+ * allowed).  With S = M + M^T without its diagonal, x^T M x = tr M + sum_{i<j} S_ij x_i x_j, and flipping the orbitals F of an excitation
+ * changes it by  -2 sum_{i in F} x_i r_i + 4 sum_{i<j in F} S_ij x_i x_j,  r_i = sum_j S_ij x_j:  a per-orbital factor that joins the RBM
+ * kernel's per-walker table, and one (single) or six (double) pair factors exp(+-4 S_ij) read from the "Jastrow table".
+ *   pynqs_jastrow_table_bytes : [host] size of the table in bytes (pynqs_amd/csrc/rbm.h: S, exp(+4 S), exp(-4 S), tr M), -1 for a bad sorb
+ *   pynqs_jastrow_table_build : M -> the table, in caller-owned memory; rebuild after every parameter update (one small kernel)
+ *   pynqs_eloc_jrbm_supported : [host] 1 if pynqs_eloc_jrbm serves this problem: the resident form of pynqs_eloc_rbm (sorb x nhidden
+ *                               within the LDS).  There is no windowed form: 0 beyond it, and callers evaluate the module instead.
+ *   pynqs_eloc_jrbm_form      : [host] as pynqs_eloc_rbm_form: -1 if unsupported, else bit 1 = a walker's tiles are cut over several
+ *                               workgroups that add their parts with atomics (bit 0, the windowed kernel, is never set), bit 2 = the
+ *                               walker's pair factors are kept as a triangle in LDS (4 sorb (sorb - 1) bytes; where that would cost a
+ *                               workgroup per CU, and beyond 128 orbitals, they are read from the table in L2)
+ *   pynqs_eloc_jrbm           : as pynqs_eloc_rbm, same outputs and conventions; rbm_table from pynqs_rbm_table_build, jastrow_table from
+ *                               pynqs_jastrow_table_build.  psi (may be NULL) receives psi(x) including exp(tr M).
+ *   pynqs_jrbm_forward        : psi double[n] on a list of packed determinants from scratch, as pynqs_rbm_forward (one lane per
+ *                               determinant, nothing but the result written); visible_bias may be NULL.
+ *   pynqs_jastrow_grad        : the estimator of pynqs_rbm_grad for M (real parameters): d ln psi / d M_ij = x_i x_j, so
+ *                                 grad_jastrow[i][j] = 2 sum_n f_n x_i(n) x_j(n),  f_n = p_n (E_loc,n - <E> c_n)   (double[sorb][sorb], overwritten),
+ *                                 loss (may be NULL) = 2 sum_n f_n x_n^T M x_n: the Jastrow part of the loss, to be added to pynqs_rbm_grad's.
+ *                               prob, eloc double[n]; e_total: DEVICE pointer to <E>; pow: c_n double[n] or NULL for 1.  The gradients of
+ *                               weights and biases do not depend on M: they come from pynqs_rbm_grad, called as for the plain RBM.
+ *                               workspace: pynqs_jastrow_grad_workspace(n, sorb) bytes.  Sums run in a fixed order, no atomics: two calls
+ *                               give the same bits. */
+int64_t pynqs_jastrow_table_bytes(int sorb);
+int pynqs_jastrow_table_build(const double *jastrow, int sorb, void *table, void *stream);
+int pynqs_eloc_jrbm_supported(int sorb, int nele, int noA, int noB, int nhidden);
+int pynqs_eloc_jrbm_form(int64_t nbatch, int sorb, int nele, int noA, int noB, int nhidden);
+int pynqs_eloc_jrbm(const uint64_t *bra, int64_t nbatch, int sorb, int nele, int noA, int noB, const void *plan,
+                    const void *rbm_table, const void *jastrow_table, int nhidden, double *eloc, double *psi, void *stream);
+int pynqs_jrbm_forward(const uint64_t *onv, int64_t n, int sorb, const double *weights, const double *hidden_bias,
+                       const double *visible_bias, const double *jastrow, int nhidden, double *psi, void *stream);
+int64_t pynqs_jastrow_grad_workspace(int64_t n, int sorb);
+int pynqs_jastrow_grad(const uint64_t *onv, int64_t n, int sorb, const double *jastrow, const double *prob, const double *eloc,
+                       const double *e_total, const double *pow, double *grad_jastrow, double *loss, void *workspace, void *stream);
+
 /* ---- Green's-function Monte-Carlo move: gfmc/walker.py:260-279 (sample_update) in one kernel ---------------
  * green double[n][ncomb] (the fixed-node Green's function row of each walker, >= 0), rand_num double[n] in [0, 1),
  * comb uint64[n][ncomb][len] (get_comb_hij_fused's first output).  Per walker: beta = sum_k green[k];

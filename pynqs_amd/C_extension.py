@@ -33,7 +33,7 @@ USE_PLAN = True  # route get_comb_hij_fused through the cached integral plan (Fa
 
 __all__ = [
     "tensor_to_onv", "onv_to_tensor", "get_comb_tensor", "get_hij_torch", "get_comb_hij_fused",
-    "wavefunction_lut", "hash_build", "hash_lookup", "HashTable", "RBMTable", "eloc_rbm", "merge_rank_sample", "spin_flip_rand", "check_sorb", "compress_h1e_h2e", "decompress_h1e_h2e", "get_Num_SinglesDoubles",
+    "wavefunction_lut", "hash_build", "hash_lookup", "HashTable", "RBMTable", "eloc_rbm", "JastrowTable", "eloc_jrbm", "jrbm_forward", "eloc_jrbm_supported", "merge_rank_sample", "spin_flip_rand", "check_sorb", "compress_h1e_h2e", "decompress_h1e_h2e", "get_Num_SinglesDoubles",
     "MAX_SORB", "MAX_SORB_LEN", "MAX_NELE",
 ]
 
@@ -564,6 +564,31 @@ class RBMTable(_RBMTableBase):
         self._build("rbm", ts, [t.detach().contiguous() for t in ts], int(weights.size(0)), int(weights.size(1)))
 
 
+class JastrowTable:
+    """Device-resident table of the two-body Jastrow factor exp(x^T M x) for the fused SIMPLE local energy of a Jastrow-RBM
+    (include/pynqs_amd.h: pynqs_jastrow_table_build; reference: vmc/ansatz/rbm/rbm_other.py, class Jastrow, prod_dim = 1).
+    jastrow: M float64 [sorb, sorb], any real matrix.  Rebuild after every parameter update (one small kernel)."""
+
+    def __init__(self, jastrow: Tensor) -> None:
+        if jastrow.dim() != 2 or jastrow.size(0) != jastrow.size(1):
+            raise RuntimeError("jastrow must be [sorb, sorb]")
+        if jastrow.dtype != torch.float64:
+            raise RuntimeError("the fused Jastrow-RBM local energy is float64 only")
+        given = jastrow.detach().contiguous()
+        dev, (m,), _ = _stage(given)
+        self.sorb, self.device = int(m.size(0)), dev
+        nbytes = N.lib().pynqs_jastrow_table_bytes(self.sorb)
+        if nbytes < 0:
+            raise RuntimeError(f"bad Jastrow size: sorb = {self.sorb}")
+        self.buf = torch.empty(nbytes // 8, dtype=torch.float64, device=dev)
+        N.check(N.lib().pynqs_jastrow_table_build(m.data_ptr(), self.sorb, self.buf.data_ptr(), _stream(dev)), "jastrow_table_build")
+        if m.data_ptr() != jastrow.data_ptr():
+            torch.cuda.current_stream(dev).synchronize()  # a staging copy must outlive the build kernel
+
+    def data_ptr(self) -> int:
+        return self.buf.data_ptr()
+
+
 # rbm_type (rbm.py:199-211) -> include/pynqs_amd.h; RBM_FLAVOURS: the ones the real-parameter table and kernel serve
 RBM_TYPE_FLAVOUR = {"real": N.RBM_REAL, "tanh": N.RBM_TANH, "pRBM": N.RBM_PHASE, "complex": N.RBM_COMPLEX}
 RBM_FLAVOURS = {k: v for k, v in RBM_TYPE_FLAVOUR.items() if v != N.RBM_COMPLEX}
@@ -607,6 +632,40 @@ def eloc_rbm(bra: Tensor, h1e: Tensor, h2e: Tensor, table: RBMTable, sorb: int, 
     return _eloc_fused(bra, h1e, h2e, table, sorb, want_psi, _rbm_dtype(rbm_type), lambda x, n, plan, eloc, psi, st: N.check(
         N.lib().pynqs_eloc_rbm_flavour(x.data_ptr(), n, sorb, nele, noA, noB, plan.data_ptr(), table.data_ptr(), table.nhidden,
                                        RBM_FLAVOURS[rbm_type], eloc.data_ptr(), psi, st), "pynqs_eloc_rbm"))
+
+
+def eloc_jrbm_supported(sorb: int, nele: int, noA: int, noB: int, num_hidden: int) -> bool:
+    """whether pynqs_eloc_jrbm serves this problem (the resident form of the RBM kernel: sorb x num_hidden within the LDS)"""
+    return bool(N.lib().pynqs_eloc_jrbm_supported(sorb, nele, noA, noB, num_hidden))
+
+
+def eloc_jrbm(bra: Tensor, h1e: Tensor, h2e: Tensor, rbm_table: RBMTable, jastrow_table: JastrowTable, sorb: int, nele: int, noA: int, noB: int,
+              want_psi: bool = True) -> Tuple[Tensor, "Tensor | None"]:
+    """SIMPLE local energy of psi(x) = exp(a.x + x^T M x) prod_h 2cosh(theta_h), a real RBM times a two-body Jastrow factor, with the
+    amplitude ratio evaluated on chip (pynqs_eloc_jrbm): (eloc float64[n], psi(x) float64[n] or None)."""
+    _check_onv(bra, "bra", sorb, (2,))
+    if jastrow_table.sorb != sorb or jastrow_table.device != rbm_table.device:
+        raise RuntimeError(f"Jastrow table: sorb = {jastrow_table.sorb} on {jastrow_table.device}, RBM table: sorb = {sorb} on {rbm_table.device}")
+    return _eloc_fused(bra, h1e, h2e, rbm_table, sorb, want_psi, torch.float64, lambda x, n, plan, eloc, psi, st: N.check(
+        N.lib().pynqs_eloc_jrbm(x.data_ptr(), n, sorb, nele, noA, noB, plan.data_ptr(), rbm_table.data_ptr(), jastrow_table.data_ptr(),
+                                rbm_table.nhidden, eloc.data_ptr(), psi, st), "pynqs_eloc_jrbm"))
+
+
+def jrbm_forward(onv: Tensor, weights: Tensor, hidden_bias: Tensor, visible_bias: "Tensor | None", jastrow: Tensor, sorb: int) -> Tensor:
+    """psi(x) = exp(a.x + x^T M x) prod_h 2cosh(theta_h) on a list of determinants, one kernel (pynqs_jrbm_forward):
+    onv uint8[n, 8 len] -> psi float64[n]; weights [H, sorb], hidden_bias [H], visible_bias [sorb] or None, jastrow M [sorb, sorb]."""
+    _check_onv(onv, "onv", sorb, (2,))
+    _, W, hb, vb, H = _rbm_params(weights, hidden_bias, visible_bias, sorb, "real", on_gpu=False)
+    M = jastrow.detach().double().contiguous()
+    if M.shape != (sorb, sorb):
+        raise RuntimeError("jastrow must be [sorb, sorb]")
+    if not (onv.is_cuda and W.is_cuda and hb.is_cuda and (vb is None or vb.is_cuda) and M.is_cuda):
+        raise RuntimeError("jrbm_forward: determinants and parameters must be on the GPU")
+    n = onv.size(0)
+    psi = torch.empty(n, dtype=torch.float64, device=onv.device)
+    N.check(N.lib().pynqs_jrbm_forward(onv.data_ptr(), n, sorb, W.data_ptr(), hb.data_ptr(), vb.data_ptr() if vb is not None else None, M.data_ptr(),
+                                       H, psi.data_ptr(), _stream(onv.device)), "pynqs_jrbm_forward")
+    return psi
 
 
 def rbm_forward(onv: Tensor, weights: Tensor, hidden_bias: Tensor, visible_bias: "Tensor | None", sorb: int, rbm_type: str = "real") -> Tensor:

@@ -113,6 +113,14 @@ SIGNATURES.update({
     "pynqs_rdm_rbm_supported": (_int, [_int, _int, _int, _int, _int]),
     "pynqs_rdm_rbm_workspace": (_i64, [_i64, _int, _int]),
     "pynqs_rdm_rbm": (_int, [_vp, _i64, _int, _int, _int, _int, _vp, _vp, _int, _vp, _vp, _vp, _vp]),
+    "pynqs_jastrow_table_bytes": (_i64, [_int]),
+    "pynqs_jastrow_table_build": (_int, [_vp, _int, _vp, _vp]),
+    "pynqs_eloc_jrbm_supported": (_int, [_int, _int, _int, _int, _int]),
+    "pynqs_eloc_jrbm_form": (_int, [_i64, _int, _int, _int, _int, _int]),
+    "pynqs_eloc_jrbm": (_int, [_vp, _i64, _int, _int, _int, _int, _vp, _vp, _vp, _int, _vp, _vp, _vp]),
+    "pynqs_jrbm_forward": (_int, [_vp, _i64, _int, _vp, _vp, _vp, _vp, _int, _vp, _vp]),
+    "pynqs_jastrow_grad_workspace": (_i64, [_i64, _int]),
+    "pynqs_jastrow_grad": (_int, [_vp, _i64, _int, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp]),
 })
 
 _lib = None

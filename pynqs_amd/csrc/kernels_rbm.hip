@@ -36,6 +36,21 @@
 // h_k r_k < 0 (the reference's cos(phase difference + gamma) < 0) and then has weight g_k = -h_k r_k; the others add to the
 // sign-flip potential v_sf = sum h_k r_k on the diagonal: g_0 = max(0, Lambda - h_0 - v_sf).  The row is written in the
 // reference's column order (column = 1 + rank, excitation.cpp:43-109 incl. the `idx % noAA` rotation); E_loc is unchanged.
+//
+// JASTROW (real flavour, resident form): psi(x) = exp(a.x + x^T M x) prod_h 2cosh(theta_h), the two-body Jastrow factor of
+// vmc/ansatz/rbm/rbm_other.py (class Jastrow) multiplied onto the RBM.  With S = M + M^T (zero diagonal; the Jastrow table of rbm.h) and
+// r_o = sum_j S_oj x_j, flipping the orbitals F changes x^T M x by  -2 sum_{o in F} x_o r_o + 4 sum_{i<j in F} S_ij x_i x_j:
+//   the first term joins C(o) = exp(-2 x_o (a_o + r_o + sum_h s_h W[h][o])): nothing new per column, no LDS;
+//   the second is a product of pair factors exp(4 S_ij x_i x_j) = E4p[i][j] where the walker's x_i = x_j, else E4m[i][j]: one for a
+//   single, six for a double, read in the tile epilogue and multiplied onto the running products: a lane's 4 x 4 block takes 4 + 4
+//   loads for the pairs inside its fast and slow entries and 64 for the crossed pairs, 4.5 loads and 6 products per column.  They come
+//   from a per-walker triangle P[i > j] = exp(4 S_ij x_i x_j) in LDS behind the trailer (4 sorb (sorb - 1) bytes, built from the table
+//   next to C(o); `lambda` != 0) where three workgroups still fit a CU with it, else from the table itself (L2-resident, 16 sorb^2
+//   bytes).  Fe2S2, 8192 walkers: 0.97-1.13 ms from LDS, 1.00-1.17 ms from L2, pynqs_eloc_rbm 0.77 ms in the same run.
+// tr M scales psi(x) only.  Every statement of it stands under `if constexpr (JASTROW)`; the table comes in the slot of `green`, which
+// this form does not use, so that the kernel's arguments -- and the other instantiations -- are what they were.
+#include <string.h>
+
 #include "rbm.h"
 #include "rbm_math.h"
 #include "rbm_tiles.h"
@@ -95,13 +110,14 @@ __host__ __device__ inline size_t lds_bytes_rbm(const SDParams &p, const RbmLayo
 //                   windows (two barriers per window).
 enum : int { kRbmReal = 0, kRbmTanh = 1, kRbmPhase = 2 };
 
-template <int LEN, bool WINDOWED, int FLAVOUR, bool GREEN>
+template <int LEN, bool WINDOWED, int FLAVOUR, bool GREEN, bool JASTROW = false>
 __global__ __launch_bounds__(1024, 4) void eloc_rbm_kernel(const uint64_t *__restrict__ bra, SDParams p, PlanLayout pl, RbmLayout rl,
                                                           RbmBlocks<kRbmFB> B, uint32_t nchunks, uint32_t hw, const double *__restrict__ plan,
                                                           const double *__restrict__ rbm, double *__restrict__ eloc,
                                                           double *__restrict__ psi, double lambda, double *__restrict__ green,
                                                           uint8_t *__restrict__ clamped) {
   static_assert(!GREEN || FLAVOUR != kRbmPhase, "the fixed-node row needs a real-valued amplitude");
+  static_assert(!JASTROW || (FLAVOUR == kRbmReal && !GREEN && !WINDOWED), "the Jastrow factor: real flavour, resident form, no Green's row");
   // no static __shared__ here: with the dynamic region at LDS address 0 the row offsets below are the addresses and
   // the ds_read immediates carry the rest (a static in front costs one v_add per read)
   extern __shared__ __attribute__((aligned(16))) unsigned char smem[];
@@ -141,6 +157,7 @@ __global__ __launch_bounds__(1024, 4) void eloc_rbm_kernel(const uint64_t *__res
   const bool need_hs = rbm_needs_hs(B, chunk);
   const double *__restrict__ Wt = rbm + rl.offWt;
   double lnpsi = 0.0;
+  [[maybe_unused]] double xsx = 0.0;  // JASTROW: this thread's share of sum_{i<j} S_ij x_i x_j = sum_o x_o r_o / 2, summed apart from lnpsi
   const int kThetaThreads = nthreads - 64;
   if (wave == nwaves - 1) {
     rbm_diagonal(need_hs, lane, p, pl, L, plan, R.hs);
@@ -258,6 +275,18 @@ __global__ __launch_bounds__(1024, 4) void eloc_rbm_kernel(const uint64_t *__res
       if constexpr (FLAVOUR == kRbmTanh) {
         c = exp(-2.0 * x * R.Cq[o]);
         da = exp(-4.0 * x * a);
+      } else if constexpr (JASTROW) {
+        // r_o = sum_j S_jo x_j (S is symmetric: column o, so that consecutive lanes read consecutive words; S_oo = 0), 16 loads in flight
+        const double *__restrict__ S = green;
+        double r = 0.0;
+#pragma unroll 16
+        for (int j = 0; j < sorb; ++j) {
+          const double s = S[(uint32_t)j * (uint32_t)sorb + (uint32_t)o];
+          r += bit_of<LEN>(wk.w, j) ? s : -s;
+        }
+        c = exp(-2.0 * x * ((a + r) + R.Cq[o]));
+        lnpsi += x * a;
+        xsx += 0.5 * x * r;
       } else {
         c = exp(-2.0 * x * (a + R.Cq[o]));
         lnpsi += x * a;
@@ -265,6 +294,21 @@ __global__ __launch_bounds__(1024, 4) void eloc_rbm_kernel(const uint64_t *__res
     }
     R.Cq[o] = c;
     if constexpr (FLAVOUR == kRbmTanh) R.Aq[o] = da;
+  }
+  if constexpr (JASTROW) {
+    // the walker's pair factors in LDS (lambda != 0), behind the kernel's own layout (where they are is worked out again at each use:
+    // nothing of it lives across the hidden-unit loop)
+    // (one and two words only: at three the triangle is 66 KiB and more and never chosen, and the branch alone costs that
+    // instantiation a spill inside the hidden-unit loop)
+    double *jP = reinterpret_cast<double *>(smem + lds_bytes_rbm(p, rl, hw));
+    if (LEN < 3 && lambda != 0.0) {  // P[a (a - 1) / 2 + b] = exp(4 S_ab x_a x_b), b < a: a wave per row, consecutive lanes read consecutive words
+      const uint32_t n2 = (uint32_t)jastrow_pairs(sorb);
+      for (int a = 1 + wave; a < sorb; a += nwaves) {
+        const uint32_t xa = bit_of<LEN>(wk.w, a);
+        for (int b = lane; b < a; b += 64)
+          jP[(uint32_t)(a * (a - 1) / 2 + b)] = green[(bit_of<LEN>(wk.w, b) == xa ? n2 : 2u * n2) + (uint32_t)a * (uint32_t)sorb + (uint32_t)b];
+      }
+    }
   }
   double ax = 0.0, e2ax = 1.0, inv_tanh_ax = 1.0;  // tanh flavour: a.x (wave-uniform: scalar loads), exp(2 a.x), 1 / tanh(a.x)
   if constexpr (FLAVOUR == kRbmTanh) {
@@ -411,6 +455,56 @@ __global__ __launch_bounds__(1024, 4) void eloc_rbm_kernel(const uint64_t *__res
           as[i] = cls == 0 ? 1.0 : R.Aq[es[i] & 0xff] * R.Aq[(es[i] >> 8) & 0xff];
         }
       }
+      if constexpr (JASTROW) {
+        // exp(4 S_ab x_a x_b) of two flipped orbitals, from the walker's triangle in LDS or from the table; the sign x_a x_b from the
+        // walker's bits (hole-hole and particle-particle pairs +, hole-particle pairs -, whichever class and entry they come from).  The
+        // pair factors join the running products before the matrix elements are gathered: one fast entry at a time (its own pair and
+        // its 2 x 8 pairs with the slow entries' orbitals: 17 loads in flight), so that the 72 loads of a block never hold more
+        // registers than the hidden-unit loop leaves free.
+        auto join_pairs = [&](auto pair_factor) {  // pair_factor(a, b, ka, kb): a != b; ka, kb: the orbitals' bits in occ
+          if (cls == 0) {
+#pragma unroll
+            for (int i = 0; i < 4; ++i) acc[4 * i] *= pair_factor(ef[i] & 0xff, (ef[i] >> 8) & 0xff, 2 * i, 2 * i + 1);
+          } else {
+            double js[4];
+#pragma unroll
+            for (int j = 0; j < 4; ++j) js[j] = pair_factor(es[j] & 0xff, (es[j] >> 8) & 0xff, 8 + 2 * j, 9 + 2 * j);
+#pragma unroll
+            for (int i = 0; i < 4; ++i) {
+              const uint32_t a0 = ef[i] & 0xff, a1 = (ef[i] >> 8) & 0xff;
+              const double jf = pair_factor(a0, a1, 2 * i, 2 * i + 1);
+              double u[8];  // the two pairs of a0, a1 with each orbital of the slow entries
+#pragma unroll
+              for (int j = 0; j < 4; ++j) {
+                const uint32_t b0 = es[j] & 0xff, b1 = (es[j] >> 8) & 0xff;
+                u[2 * j] = pair_factor(a0, b0, 2 * i, 8 + 2 * j) * pair_factor(a1, b0, 2 * i + 1, 8 + 2 * j);
+                u[2 * j + 1] = pair_factor(a0, b1, 2 * i, 9 + 2 * j) * pair_factor(a1, b1, 2 * i + 1, 9 + 2 * j);
+              }
+#pragma unroll
+              for (int j = 0; j < 4; ++j) acc[4 * i + j] *= (jf * js[j]) * (u[2 * j] * u[2 * j + 1]);
+              asm volatile("" ::: "memory");
+            }
+          }
+        };
+        if (LEN < 3 && lambda != 0.0) {  // (workgroup-uniform)
+          const double *jP = reinterpret_cast<const double *>(smem + lds_bytes_rbm(p, rl, hw));
+          join_pairs([&](uint32_t a, uint32_t b, int, int) {
+            const uint32_t hi = max(a, b), lo = min(a, b);
+            return jP[((hi * (hi - 1u)) >> 1) + lo];
+          });
+        } else {
+          uint32_t occ = 0;  // the walker's bits of the 16 orbitals: bit 2 i + k of entry ef[i], bit 8 + 2 j + k of es[j] (k = 0: the low byte)
+#pragma unroll
+          for (int i = 0; i < 4; ++i) {
+            occ |= bit_of<LEN>(wk.w, (int)(ef[i] & 0xff)) << (2 * i) | bit_of<LEN>(wk.w, (int)((ef[i] >> 8) & 0xff)) << (2 * i + 1);
+            occ |= bit_of<LEN>(wk.w, (int)(es[i] & 0xff)) << (8 + 2 * i) | bit_of<LEN>(wk.w, (int)((es[i] >> 8) & 0xff)) << (9 + 2 * i);
+          }
+          const uint32_t n2 = (uint32_t)jastrow_pairs(sorb);
+          join_pairs([&](uint32_t a, uint32_t b, int ka, int kb) {
+            return green[((((occ >> ka) ^ (occ >> kb)) & 1u) ? 2u * n2 : n2) + a * (uint32_t)sorb + b];
+          });
+        }
+      }
       if (cls == 0) {
 #pragma unroll
         for (int i = 0; i < 4; ++i) {
@@ -500,8 +594,15 @@ __global__ __launch_bounds__(1024, 4) void eloc_rbm_kernel(const uint64_t *__res
   }
   if (psi != nullptr && chunk == 0) {  // workgroup-uniform
     const double s = rbm_over_waves(lnpsi, T.red, tid, nwaves);
+    [[maybe_unused]] double xmx = 0.0;
+    if constexpr (JASTROW) {  // x^T M x = tr M + sum_{i<j} S_ij x_i x_j, the sum apart from lnpsi: at most sorb - 1 of its additions round
+#pragma unroll
+      for (int o = 32; o > 0; o >>= 1) xsx += __shfl_xor(xsx, o);
+      xmx = rbm_over_waves(xsx, T.red, tid, nwaves) + green[3 * jastrow_pairs(sorb)];
+    }
     if (tid == 0) {
-      if constexpr (FLAVOUR == kRbmReal) psi[walker] = exp(s);
+      if constexpr (JASTROW) psi[walker] = exp(s + xmx);
+      else if constexpr (FLAVOUR == kRbmReal) psi[walker] = exp(s);
       else if constexpr (FLAVOUR == kRbmTanh) psi[walker] = tanh(ax) * exp(s);
       else sincos(s, &psi[2 * walker + 1], &psi[2 * walker]);
     }
@@ -653,4 +754,63 @@ extern "C" int pynqs_green_rbm(const uint64_t *bra, int64_t nbatch, int sorb, in
                                uint8_t *clamped, void *stream) {
   if (!green || !clamped) return set_error(PYNQS_EINVAL, "null pointer");
   return eloc_rbm_impl(bra, nbatch, sorb, nele, noA, noB, plan, rbm_table, nhidden, flavour, eloc, psi, lambda, green, clamped, stream);
+}
+
+// ---- the same with the two-body Jastrow factor exp(x^T M x) on the real RBM (JASTROW): the resident form only, one workgroup per walker
+// or chunked by the shared rules of rbm_tiles.h; the LDS, the cut into chunks and the workgroup size are those of pynqs_eloc_rbm
+static bool jrbm_resident(const RbmSystem<RbmLayout> &s) { return lds_bytes_rbm(s.p, s.rl, (uint32_t)s.rl.Hloop) <= kRbmMaxLds; }
+
+// The walker's pair factors as a triangle in LDS behind the kernel's own layout (4 sorb (sorb - 1) bytes) as long as three workgroups
+// still fit a CU (or as many as fitted without it, if fewer), else read from the table in L2.  Fe2S2: 35 + 6.1 KiB, three workgroups
+// per CU instead of four (12 of the 16 waves the registers allow).  PYNQS_JRBM_PAIRS=lds / l2 forces one of them where it fits.
+static size_t jrbm_pairs_bytes(const SDParams &p) { return 8 * ((size_t)p.sorb * (size_t)(p.sorb - 1) / 2); }
+static bool jrbm_pairs_in_lds(const RbmSystem<RbmLayout> &s) {
+  const char *env = getenv("PYNQS_JRBM_PAIRS");
+  const size_t base = lds_bytes_rbm(s.p, s.rl, (uint32_t)s.rl.Hloop), with = base + jrbm_pairs_bytes(s.p);
+  if (s.p.sorb > 128 || with > kRbmMaxLds || (env && !strcmp(env, "l2"))) return false;  // (the kernel has the LDS form for one and two words)
+  if (env && !strcmp(env, "lds")) return true;
+  const size_t per_cu = 160 * 1024 / (base + 256), per_cu_with = 160 * 1024 / (with + 256);
+  return per_cu_with >= (per_cu < 3 ? per_cu : 3);
+}
+
+extern "C" int pynqs_eloc_jrbm_supported(int sorb, int nele, int noA, int noB, int nhidden) {
+  RbmSystem<RbmLayout> s;
+  if (rbm_system(sorb, nele, noA, noB, nhidden, make_rbm_layout, &s)) return 0;
+  return jrbm_resident(s) ? 1 : 0;
+}
+
+extern "C" int pynqs_eloc_jrbm_form(int64_t nbatch, int sorb, int nele, int noA, int noB, int nhidden) {
+  RbmSystem<RbmLayout> s;
+  if (nbatch < 1 || rbm_system(sorb, nele, noA, noB, nhidden, make_rbm_layout, &s) || !jrbm_resident(s)) return -1;
+  return (rbm_chunks(make_rbm_blocks<kRbmFB>(s.p).ntiles, nbatch) > 1 ? 2 : 0) | (jrbm_pairs_in_lds(s) ? 4 : 0);
+}
+
+extern "C" int pynqs_eloc_jrbm(const uint64_t *bra, int64_t nbatch, int sorb, int nele, int noA, int noB, const void *plan,
+                               const void *rbm_table, const void *jastrow_table, int nhidden, double *eloc, double *psi, void *stream) {
+  pynqs::DeviceScope device_scope_(bra);
+  RbmSystem<RbmLayout> sys;
+  if (const char *bad = rbm_system(sorb, nele, noA, noB, nhidden, make_rbm_layout, &sys)) return set_error(PYNQS_EINVAL, bad);
+  if (const int rc = rbm_batch(nbatch, 0x7fffffffll, bra, plan, rbm_table, eloc)) return rc;
+  if (nbatch == 0) return PYNQS_OK;
+  if (!jastrow_table) return set_error(PYNQS_EINVAL, "null pointer");
+  if (!jrbm_resident(sys)) return set_error(PYNQS_EINVAL, "eloc_jrbm: sorb x nhidden beyond the LDS (pynqs_eloc_jrbm_supported)");
+  const auto &[p, pl, rl] = sys;
+  const RbmBlocks<kRbmFB> B = make_rbm_blocks<kRbmFB>(p);
+  const uint32_t nchunks = rbm_chunks(B.ntiles, nbatch), hw = (uint32_t)rl.Hloop;
+  const bool pairs_in_lds = jrbm_pairs_in_lds(sys);
+  const size_t lds = lds_bytes_rbm(p, rl, hw) + (pairs_in_lds ? jrbm_pairs_bytes(p) : 0);
+  hipStream_t st = (hipStream_t)stream;
+  uint32_t grid;
+  if (const int rc = rbm_grid(nbatch, nchunks, eloc, 8, st, &grid)) return rc;
+  const int len = (sorb - 1) / 64 + 1;
+  const uint32_t threads = rbm_resident_threads(lds, B.ntiles / nchunks, 1024, rbm_block_env());
+  // (the table travels in the kernel's `green` argument, which it only reads in this form, and `lambda` says where the pair factors are)
+  double *jas = const_cast<double *>(static_cast<const double *>(jastrow_table));
+  int rc = PYNQS_OK;
+#define PYNQS_JRBM_LAUNCH                                                                                                                  \
+  rc = rbm_launch("eloc_jrbm", eloc_rbm_kernel<LEN, false, kRbmReal, false, true>, grid, threads, lds, st, bra, p, pl, rl, B, nchunks, hw, \
+                  (const double *)plan, (const double *)rbm_table, eloc, psi, pairs_in_lds ? 1.0 : 0.0, jas, (uint8_t *)nullptr)
+  DISPATCH_LEN(len, { PYNQS_JRBM_LAUNCH; });
+#undef PYNQS_JRBM_LAUNCH
+  return rc;
 }

@@ -136,6 +136,32 @@ __global__ __launch_bounds__(kBlock) void rbm_forward_kernel(const uint64_t *__r
   write_psi<FLAVOUR>(psi, i, P, axr, axi);
 }
 
+// The real flavour times the two-body Jastrow factor exp(x^T M x) (vmc/ansatz/rbm/rbm_other.py, class Jastrow; M [sorb][sorb], any real
+// matrix), from scratch like the kernel above: x^T M x = sum_i x_i (sum_j M_ij x_j), the rows summed one by one (M_ij wave-uniform: scalar
+// loads) -- sorb^2 fused multiply-adds per determinant next to the sorb x H of theta, at most 2 sorb - 2 of them rounding on sum |M_ij|.
+template <int LEN>
+__global__ __launch_bounds__(kBlock) void jrbm_forward_kernel(const uint64_t *__restrict__ onv, int64_t n, int sorb, int H,
+                                                              const double *__restrict__ W, const double *__restrict__ hb,
+                                                              const double *__restrict__ vb, const double *__restrict__ M,
+                                                              double *__restrict__ psi) {
+  const int64_t i = (int64_t)blockIdx.x * kBlock + threadIdx.x;
+  const int64_t row = i < n ? i : n - 1;  // (idle lanes repeat the last determinant)
+  uint64_t ket[LEN];
+#pragma unroll
+  for (int w = 0; w < LEN; ++w) ket[w] = onv[row * LEN + w];
+  Prod P;
+  double axr, axi;
+  rbm_forward_row<LEN, PYNQS_RBM_REAL>(ket, sorb, H, W, hb, vb, P, axr, axi);
+  double xmx = 0.0;
+  for (int a = 0; a < sorb; ++a) {
+    double r = 0.0;
+    for (int b = 0; b < sorb; ++b) r = fma(pm1_of<LEN>(ket, b), M[(size_t)a * sorb + b], r);
+    xmx = fma(pm1_of<LEN>(ket, a), r, xmx);
+  }
+  if (i >= n) return;
+  write_psi<PYNQS_RBM_REAL>(psi, i, P, axr + xmx, axi);
+}
+
 // ---- psi on the distinct x' of a REDUCE front end, each from its parent walker -----------------------------------------------------
 // x' = x with <= 4 orbitals flipped, and   prod_h 2cosh(theta_h) = exp(sum_h theta_h) prod_h (1 + q_h),   q_h = exp(-2 theta_h).
 // Flipping orbital o to x'_o = +-1 changes theta_h by +-2 W_ho:  q_h *= exp(-+4 W_ho),  sum_h theta_h += +-2 sum_h W_ho,  a.x += +-2 a_o.
@@ -555,6 +581,21 @@ extern "C" int pynqs_rbm_forward(const uint64_t *onv, int64_t n, int sorb, const
   });
 #undef PYNQS_RF
   return check_launch("rbm_forward");
+}
+
+extern "C" int pynqs_jrbm_forward(const uint64_t *onv, int64_t n, int sorb, const double *weights, const double *hidden_bias,
+                                  const double *visible_bias, const double *jastrow, int nhidden, double *psi, void *stream) {
+  pynqs::DeviceScope device_scope_(onv);
+  if (n < 0 || n > 0x7fffffffll * kBlock || sorb < 1 || sorb > kMaxSorb || nhidden < 1) return set_error(PYNQS_EINVAL, "bad n/sorb/nhidden");
+  if (n == 0) return PYNQS_OK;
+  if (!onv || !weights || !hidden_bias || !jastrow || !psi) return set_error(PYNQS_EINVAL, "null pointer");
+  const int len = (sorb - 1) / 64 + 1;
+  const uint32_t grid = (uint32_t)((n + kBlock - 1) / kBlock);
+  DISPATCH_LEN(len, {
+    hipLaunchKernelGGL((jrbm_forward_kernel<LEN>), dim3(grid), dim3(kBlock), 0, (hipStream_t)stream, onv, n, sorb, nhidden, weights, hidden_bias,
+                       visible_bias, jastrow, psi);
+  });
+  return check_launch("jrbm_forward");
 }
 
 static size_t children_lds_bytes(int sorb, int nhidden, int flavour) {

@@ -33,6 +33,27 @@ inline bool make_rbm_layout(int sorb, int H, RbmLayout *L) {
   return true;
 }
 
+// The "Jastrow table" (pynqs_jastrow_table_build) of the two-body factor exp(x^T M x) that multiplies a real RBM (vmc/ansatz/rbm/
+// rbm_other.py, class Jastrow, prod_dim = 1; M [sorb][sorb] real, any matrix), in caller-owned memory, all double, row-major [sorb][sorb]:
+//   S   = M + M^T with a zero diagonal:  x^T M x = tr M + sum_{i<j} S_ij x_i x_j   (bitwise symmetric: a + b = b + a)
+//   E4p = exp(+4 S_ij), E4m = exp(-4 S_ij): the pair factor of two flipped orbitals i, j of a walker is E4p where x_i = x_j, else E4m
+//   tr  = sum_i M_ii (one double; it scales psi(x) only)
+struct JastrowLayout {
+  int sorb;
+  int64_t offS, offE4p, offE4m, offTr, total;  // in doubles
+};
+
+constexpr int64_t jastrow_pairs(int sorb) { return (int64_t)sorb * sorb; }  // doubles per matrix (the kernels form the offsets from it)
+
+inline bool make_jastrow_layout(int sorb, JastrowLayout *L) {
+  if (sorb < 1 || sorb > 192) return false;
+  const int64_t n2 = jastrow_pairs(sorb);
+  L->sorb = sorb;
+  L->offS = 0; L->offE4p = n2; L->offE4m = 2 * n2; L->offTr = 3 * n2;
+  L->total = (3 * n2 + 2) & ~(int64_t)1;
+  return true;
+}
+
 // The table of an RBM with COMPLEX parameters (pynqs_crbm_table_build), in caller-owned memory, complex double = 2 doubles, hidden index fastest, row stride Hs (odd: consecutive rows start in
 // different 16-byte bank groups):  Wt [sorb][Hs] | E4p = exp(+4W) [sorb][Hs] | E4m = exp(-4W) [sorb][Hs] | hb [Hs] | vb [sorb]
 struct CrbmLayout {

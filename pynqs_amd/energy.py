@@ -52,7 +52,7 @@ from .C_extension import get_comb_hij_fused, get_hij_torch
 from .distributed import get_rank, get_world_size
 from .public_function import (SpinProjection, WavefunctionLUT, ansatz_batch, check_para, get_nbatch, get_Num_SinglesDoubles,
                               spin_flip_onv, spin_flip_sign, split_batch_idx, unique_onv)
-from .rbm import ComplexRBM, RealRBM
+from .rbm import ComplexRBM, JastrowRBM, RealRBM
 
 _LOG = logging.getLogger("pynqs_amd")
 
@@ -264,6 +264,18 @@ def _complex_rbm_params(ansatz):
         W, hb = W.detach().double(), hb.detach().reshape(-1).double()
         return torch.stack([torch.zeros_like(W), W], -1), torch.stack([torch.zeros_like(hb), hb], -1), None, W.size(0) * math.log(2.0), True
     return None
+
+
+def _jastrow_rbm_params(ansatz):
+    """(weights [H, sorb], hidden_bias [H], visible_bias [sorb], jastrow [sorb, sorb]) if `ansatz` (possibly DDP-wrapped) is a
+    pynqs_amd.rbm.JastrowRBM with its parameters on the GPU, else None."""
+    m = getattr(ansatz, "module", ansatz)
+    if not isinstance(m, JastrowRBM):
+        return None
+    W, hb, vb, M = m.weights, m.hidden_bias, m.visible_bias, m.jastrow
+    if W.dtype not in (torch.float64, torch.float32) or not W.is_cuda or W.dim() != 2 or M.shape != (W.size(1), W.size(1)):
+        return None
+    return W.detach().double(), hb.detach().reshape(-1).double(), vb.detach().reshape(-1).double(), M.detach().double()
 
 
 def _rbm_lds_ok(sorb: int, nele: int, noa: int, nob: int, nhidden: int) -> bool:
@@ -826,6 +838,7 @@ def _eloc_simple_rbm(c):
     x, dtype, system = c.x, c.dtype, c.system
     prm = _real_rbm_params(c.ansatz)
     cprm = _complex_rbm_params(c.ansatz) if prm is None else None
+    jprm = _jastrow_rbm_params(c.ansatz) if prm is None and cprm is None else None
     # the phase flavour (pRBM) is complex-valued; the others need a real `dtype` like the module itself
     if (prm is not None and dtype in ((torch.complex128, torch.complex64) if prm[3] == "pRBM" else (torch.double, torch.float32))
             and _rbm_lds_ok(*system, prm[0].size(0))):
@@ -834,6 +847,11 @@ def _eloc_simple_rbm(c):
     elif (cprm is not None and dtype in ((torch.double, torch.float32) if cprm[4] else (torch.complex128, torch.complex64))
             and N.lib().pynqs_eloc_crbm_supported(*system, cprm[0].size(0))):
         table, run, psi_kw = CX.CRBMTable(*cprm[:3]), CX.eloc_crbm, dict(log_scale=cprm[3])
+    # a real RBM times a two-body Jastrow factor: the real kernel with the pair factors (pynqs_eloc_jrbm), real-valued
+    elif jprm is not None and dtype in (torch.double, torch.float32) and CX.eloc_jrbm_supported(*system, jprm[0].size(0)):
+        jtable = CX.JastrowTable(jprm[3])
+        table, psi_kw = CX.RBMTable(*jprm[:3]), {}
+        run = lambda x, h1, h2, tab, *sys, **kw: CX.eloc_jrbm(x, h1, h2, tab, jtable, *sys, **kw)  # noqa: E731
     else:
         return None
     eloc, psi0 = run(x, *CX.integrals_f64(c.h1e, c.h2e), table, *system, **psi_kw)

@@ -248,3 +248,101 @@ class FusedRbmGrad:
         for p, v in zip(params, self.views):
             p.grad = v
         return self.loss * ws if ws > 1 else self.loss.clone()
+
+
+class FusedJastrowRbmGrad:
+    """The estimator of grad() for pynqs_amd.rbm.JastrowRBM, psi(x) = exp(a.x + x^T M x) prod_h 2cosh(theta_h), analytically from the packed
+    determinants: pynqs_rbm_grad for weights and biases (d ln psi / d W, b, a do not depend on M) plus pynqs_jastrow_grad for M
+    (d ln psi / d M_ij = x_i x_j: grad = 2 sum_n f_n x_i x_j), and the loss as the sum of the two kernels' parts.  Calling convention,
+    flat buffer (all gradients and the loss: one all-reduce per step), mean over the ranks and p.grad views exactly as FusedRbmGrad, which
+    itself refuses this module (it would drop M).  The sums run in a fixed order: the gradient is bit-reproducible."""
+
+    names = ("weights", "hidden_bias", "visible_bias", "jastrow")
+
+    def __init__(self, nqs: nn.Module, sorb: int) -> None:
+        from . import _native as N
+        from .rbm import JastrowRBM
+
+        m = getattr(nqs, "module", nqs)
+        if not isinstance(m, JastrowRBM):
+            raise ValueError("FusedJastrowRbmGrad: the module is not a pynqs_amd.rbm.JastrowRBM")
+        self.N, self.module, self.sorb = N, m, sorb
+        params = [getattr(m, nm) for nm in self.names]
+        if any(p.dtype != torch.float64 or not p.is_cuda for p in params):
+            raise ValueError("FusedJastrowRbmGrad: float64 parameters on the GPU")
+        if params[0].size(1) != sorb:
+            raise ValueError(f"FusedJastrowRbmGrad: the module has {params[0].size(1)} orbitals, not {sorb}")
+        dev = params[0].device
+        self.H = params[0].size(0)
+        self.shapes = [p.shape for p in params]
+        # one buffer for the gradients AND the loss (its last element): one all-reduce per step over the ranks, not two
+        self.flat = torch.zeros(sum(p.numel() for p in params) + 1, dtype=torch.float64, device=dev)
+        self.views, o = [], 0
+        for p in params:
+            self.views.append(self.flat[o:o + p.numel()].view_as(p))
+            o += p.numel()
+        self.loss = self.flat[o:o + 1]
+        self.loss_jastrow = torch.zeros(1, dtype=torch.float64, device=dev)  # pynqs_jastrow_grad's part, added to pynqs_rbm_grad's
+        self.work = None
+        self.events = None
+
+    @property
+    def params(self):
+        """the module's parameters as they are NOW (see FusedRbmGrad.params)"""
+        ps = [getattr(self.module, nm) for nm in self.names]
+        if any(p.dtype != torch.float64 or p.device != self.flat.device for p in ps):
+            raise ValueError("FusedJastrowRbmGrad: float64 parameters on the GPU")
+        if [p.shape for p in ps] != self.shapes:
+            raise ValueError(f"FusedJastrowRbmGrad: parameter shapes changed since construction ({self.shapes} -> {[p.shape for p in ps]})")
+        return ps
+
+    def __call__(self, onv: Tensor, state_prob: Tensor, eloc: Tensor, e_total, extra_psi_pow=1.0) -> Tensor:
+        N, dev = self.N, self.flat.device
+        n = onv.size(0)
+        if onv.dtype != torch.uint8 or onv.dim() != 2 or onv.size(1) != 8 * ((self.sorb - 1) // 64 + 1) or onv.device != dev:
+            raise ValueError("FusedJastrowRbmGrad: walkers as packed onv uint8[n, 8 len] on the parameters' device")
+        if eloc.is_complex():
+            raise ValueError("FusedJastrowRbmGrad: the amplitude is real: a real local energy")
+        prob = (state_prob.real if state_prob.is_complex() else state_prob).to(torch.float64).contiguous()
+        el = eloc.to(torch.float64).contiguous()
+        et = (e_total if isinstance(e_total, Tensor) else torch.as_tensor(e_total)).to(device=dev, dtype=torch.float64).reshape(1).contiguous()
+        pw = None
+        if isinstance(extra_psi_pow, Tensor):
+            if extra_psi_pow.is_complex():
+                raise ValueError("FusedJastrowRbmGrad: extra_psi_pow must be real")
+            pw = extra_psi_pow.to(torch.float64).contiguous()
+        elif float(extra_psi_pow) != 1.0:
+            pw = torch.full((n,), float(extra_psi_pow), dtype=torch.float64, device=dev)
+        lib = N.lib()
+        need = max(lib.pynqs_rbm_grad_workspace(n, self.sorb, self.H, N.RBM_REAL), lib.pynqs_jastrow_grad_workspace(n, self.sorb))
+        if self.work is None or self.work.numel() * 8 < need:
+            self.work = torch.empty(max(need // 8, 1), dtype=torch.float64, device=dev)
+        params = self.params
+        W, hb, vb, M = (p.detach().contiguous() for p in params)
+        gw, ghb, gvb, gm = self.views
+        x = onv.contiguous()
+        st = torch.cuda.current_stream(dev).cuda_stream
+        pwp = pw.data_ptr() if pw is not None else None
+        # (the two calls share the workspace: they run one after the other on the stream)
+        N.check(lib.pynqs_rbm_grad(x.data_ptr(), n, self.sorb, W.data_ptr(), hb.data_ptr(), vb.data_ptr(), self.H, N.RBM_REAL, prob.data_ptr(),
+                                   el.data_ptr(), 0, et.data_ptr(), pwp, gw.data_ptr(), ghb.data_ptr(), gvb.data_ptr(), self.loss.data_ptr(),
+                                   self.work.data_ptr(), st), "pynqs_rbm_grad")
+        N.check(lib.pynqs_jastrow_grad(x.data_ptr(), n, self.sorb, M.data_ptr(), prob.data_ptr(), el.data_ptr(), et.data_ptr(), pwp, gm.data_ptr(),
+                                       self.loss_jastrow.data_ptr(), self.work.data_ptr(), st), "pynqs_jastrow_grad")
+        self.loss += self.loss_jastrow
+        ws = get_world_size()
+        ev = None
+        if self.events is not None:
+            ev = [torch.cuda.Event(enable_timing=True) for _ in range(2)]
+            ev[0].record()
+        if ws > 1:
+            import torch.distributed as dist
+
+            dist.all_reduce(self.flat, dist.ReduceOp.SUM)
+            self.flat.div_(ws)  # gradients: mean over the ranks (DDP's convention); the loss is a sum: undone below
+        if ev is not None:
+            ev[1].record()
+            self.events.append(ev)
+        for p, v in zip(params, self.views):
+            p.grad = v
+        return self.loss * ws if ws > 1 else self.loss.clone()

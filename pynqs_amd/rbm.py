@@ -70,6 +70,35 @@ class RealRBM(nn.Module):
         return (z[:, -1] + lncosh).exp()
 
 
+class JastrowRBM(nn.Module):
+    """A real RBM times a two-body Jastrow factor: psi(x) = exp(a.x + x^T M x) prod_h 2 cosh(b_h + sum_o W_ho x_o), the product
+    (vmc/ansatz/hybrid/multi.py) of the reference's RBMWavefunction, rbm_type "real", and its Jastrow (vmc/ansatz/rbm/rbm_other.py:
+    exp(sum_ij M_ij x_i x_j), prod_dim = 1).  jastrow: M [sorb, sorb], any real matrix -- not symmetric, diagonal allowed (it scales psi).
+    forward() is plain torch, so every generic route of the package works with it; the fused routes are its own: SIMPLE local energies
+    (pynqs_amd.energy, pynqs_eloc_jrbm) and pynqs_amd.grad.FusedJastrowRbmGrad.  On purpose NOT a RealRBM and without an `rbm_type`: the
+    fused routes of the plain RBMs recognise their modules by those two and would drop M."""
+
+    def __init__(self, weights: Tensor, hidden_bias: Tensor, visible_bias: Tensor, jastrow: Tensor) -> None:
+        super().__init__()
+        if jastrow.dim() != 2 or jastrow.size(0) != jastrow.size(1) or jastrow.size(0) != weights.size(1):
+            raise ValueError("jastrow must be [sorb, sorb]")
+        self.weights = nn.Parameter(weights.clone())            # [num_hidden, sorb]
+        self.hidden_bias = nn.Parameter(hidden_bias.clone())    # [num_hidden]
+        self.visible_bias = nn.Parameter(visible_bias.clone())  # [sorb]
+        self.jastrow = nn.Parameter(jastrow.clone())            # [sorb, sorb]
+
+    def forward(self, x: Tensor) -> Tensor:
+        x = x.to(self.weights.dtype)
+        # theta, a.x and the rows M x from one GEMM (as RealRBM: _SkinnyLinear's backward sums over the walkers in slabs)
+        H = self.weights.size(0)
+        wext = torch.cat([self.weights, self.visible_bias.unsqueeze(0), self.jastrow], 0)
+        z = _SkinnyLinear.apply(x, wext)
+        lncosh = (2 * (z[:, :H] + self.hidden_bias).cosh()).log().sum(-1)
+        xmx = (x * z[:, H + 1:]).sum(-1)
+        # exp of the sum, not a product: no host synchronisation in the backward (see RealRBM)
+        return (z[:, H] + xmx + lncosh).exp()
+
+
 class ComplexRBM(nn.Module):
     """psi(x) = exp(a.x) prod_h 2 cosh(W x + b)_h with complex128 parameters stored as (re, im) pairs, the layout of the
     reference's rbm_type "complex" (rbm.py:61-73,147-168; its own psi() cannot run: it casts x back to float64 before
