@@ -329,6 +329,11 @@ int64_t pynqs_moments_workspace(void);
  * the ranks; inv_world = 1 / world_size as in comm.py:62-67): out5 = mean_re, mean_im, var, sd, se = sd / sqrt(counts). */
 int pynqs_stats_finish(const double *moments, double inv_world, double counts, double *out5, void *stream);
 int pynqs_weighted_moments(const double *x, int is_complex, const double *prob, int64_t n, void *workspace, void *stream);
+/* pynqs_weighted_moments followed by pynqs_stats_finish on workspace[0..3] in ONE launch, for a single rank (no all-reduce in between):
+ * the workgroup that finishes last does the closing arithmetic on the sums it has just formed.  workspace[0..3] and out5 hold bit for bit
+ * what the two calls leave. */
+int pynqs_weighted_moments_finish(const double *x, int is_complex, const double *prob, int64_t n, void *workspace, double inv_world,
+                                  double counts, double *out5, void *stream);
 
 /* REDUCE method front end: vmc/energy/eloc.py:205-324 with eps_sample == 0 keeps the columns with
  * |<x|H|x'>| >= eps (eloc.py:297-298; column 0 is treated like any other).  Two passes, nothing materialised, no
@@ -521,12 +526,32 @@ int pynqs_rbm_forward_children(const uint64_t *onv, int64_t n, const int32_t *co
                                const double *hidden_bias, const double *visible_bias, int nhidden, int flavour, double *psi,
                                void *stream);
 int pynqs_rbm_forward_children_supported(int sorb, int nhidden, int flavour);
+/* The same pair with ONE launch for the prepare step (the same table bit for bit).  Within one launch the flag cannot be reset and then
+ * raised, so a parent out of range stores the call's `stamp` there and pynqs_rbm_forward_children_stamped takes the flag for raised only if
+ * it holds its own stamp: pass the same number in [1, 2^53) to both calls and a different one to every prepare call that may meet the same
+ * table memory (a process-wide call counter).  A stale stamp or the garbage of a fresh buffer reads as "not raised"; garbage that equals
+ * the stamp sends the call down the from-scratch path, which is right for every input.  Do not mix the stamped and the plain entry points
+ * on one table. */
+int pynqs_rbm_children_prepare_stamped(const uint64_t *walkers, int64_t nwalkers, int sorb, const double *weights,
+                                       const double *hidden_bias, const double *visible_bias, int nhidden, int flavour, uint64_t stamp,
+                                       void *table, void *stream);
+int pynqs_rbm_forward_children_stamped(const uint64_t *onv, int64_t n, const int32_t *count_dev, const int32_t *parent,
+                                       const uint64_t *walkers, int64_t nwalkers, const void *table, int sorb, const double *weights,
+                                       const double *hidden_bias, const double *visible_bias, int nhidden, int flavour, uint64_t stamp,
+                                       double *psi, void *stream);
 
 int64_t pynqs_rbm_grad_workspace(int64_t n, int sorb, int nhidden, int flavour);
 int pynqs_rbm_grad(const uint64_t *onv, int64_t n, int sorb, const double *weights, const double *hidden_bias,
                    const double *visible_bias, int nhidden, int flavour, const double *prob, const double *eloc,
                    int eloc_is_complex, const double *e_total, const double *pow, double *grad_weights,
                    double *grad_hidden_bias, double *grad_visible_bias, double *loss, void *workspace, void *stream);
+/* the same; loss_copy (may be NULL) receives the loss a second time, e.g. a fresh one-element tensor for the caller to return while
+ * `loss` stays inside its flat all-reduce buffer: no copy launch */
+int pynqs_rbm_grad_loss(const uint64_t *onv, int64_t n, int sorb, const double *weights, const double *hidden_bias,
+                        const double *visible_bias, int nhidden, int flavour, const double *prob, const double *eloc,
+                        int eloc_is_complex, const double *e_total, const double *pow, double *grad_weights,
+                        double *grad_hidden_bias, double *grad_visible_bias, double *loss, double *loss_copy, void *workspace,
+                        void *stream);
 
 /* ---- stochastic reconfiguration for RBM amplitudes, matrix-free (kernels_rbm_sr.hip; vmc/grad/sr.py with vmc/grad/_jacobian.py, the
  * reference's `sr=True`, which builds a dense P x P matrix and inverts it) ---------------------------------------------------------------

@@ -15,6 +15,7 @@ like bind.cpp:290-299.
 """
 from __future__ import annotations
 
+import itertools
 import os
 import warnings
 import weakref
@@ -707,6 +708,9 @@ def rbm_forward_children_supported(sorb: int, num_hidden: int, rbm_type: str = "
     return flav is not None and bool(N.lib().pynqs_rbm_forward_children_supported(sorb, num_hidden, flav))
 
 
+_CHILDREN_STAMP = itertools.count(1)  # process-wide call counter of rbm_forward_children (the stamp of its table's flag)
+
+
 def rbm_forward_children(onv: Tensor, parent: Tensor, walkers: Tensor, weights: Tensor, hidden_bias: Tensor, visible_bias: "Tensor | None",
                          sorb: int, rbm_type: str = "real", count: "Tensor | None" = None, out: "Tensor | None" = None) -> Tensor:
     """psi of the reference's RBM amplitudes (vmc/ansatz/rbm/rbm.py:186-211) on the DISTINCT x' of a REDUCE front end, each from its parent
@@ -725,12 +729,16 @@ def rbm_forward_children(onv: Tensor, parent: Tensor, walkers: Tensor, weights: 
     table = torch.empty(max(nbytes // 8, 1), dtype=torch.float64, device=dev)
     st = _stream(dev)
     wk = walkers.contiguous()
-    N.check(N.lib().pynqs_rbm_children_prepare(wk.data_ptr(), nw, sorb, W.data_ptr(), hb.data_ptr(), vb.data_ptr() if vb is not None else None,
-                                               H, flav, table.data_ptr(), st), "pynqs_rbm_children_prepare")
+    # one launch prepares the table; its out-of-range flag is this call's stamp (the table memory is fresh from the allocator: whatever an
+    # earlier call left in the flag word carries another stamp)
+    stamp = next(_CHILDREN_STAMP)
+    N.check(N.lib().pynqs_rbm_children_prepare_stamped(wk.data_ptr(), nw, sorb, W.data_ptr(), hb.data_ptr(), vb.data_ptr() if vb is not None else None,
+                                                       H, flav, stamp, table.data_ptr(), st), "pynqs_rbm_children_prepare_stamped")
     psi = out if out is not None else torch.empty(n, dtype=_rbm_dtype(rbm_type), device=dev)
-    N.check(N.lib().pynqs_rbm_forward_children(onv.contiguous().data_ptr(), n, count.data_ptr() if count is not None else None, parent.data_ptr(),
-                                               wk.data_ptr(), nw, table.data_ptr(), sorb, W.data_ptr(), hb.data_ptr(),
-                                               vb.data_ptr() if vb is not None else None, H, flav, psi.data_ptr(), st), "pynqs_rbm_forward_children")
+    N.check(N.lib().pynqs_rbm_forward_children_stamped(onv.contiguous().data_ptr(), n, count.data_ptr() if count is not None else None,
+                                                       parent.data_ptr(), wk.data_ptr(), nw, table.data_ptr(), sorb, W.data_ptr(), hb.data_ptr(),
+                                                       vb.data_ptr() if vb is not None else None, H, flav, stamp, psi.data_ptr(), st),
+            "pynqs_rbm_forward_children_stamped")
     return psi
 
 

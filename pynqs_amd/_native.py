@@ -69,6 +69,7 @@ SIGNATURES = {
     "pynqs_moments_workspace": (_i64, []),
     "pynqs_stats_finish": (_int, [_vp, _dbl, _dbl, _vp, _vp]),
     "pynqs_weighted_moments": (_int, [_vp, _int, _vp, _i64, _vp, _vp]),
+    "pynqs_weighted_moments_finish": (_int, [_vp, _int, _vp, _i64, _vp, _dbl, _dbl, _vp, _vp]),
     "pynqs_reduce_tiles": (_i64, [_i64, _int, _int, _int, _int]),
     "pynqs_reduce_count": (_int, [_vp, _i64, _int, _int, _int, _int, _vp, _int, _dbl, _vp, _vp]),
     "pynqs_reduce_count_sums": (_int, [_vp, _i64, _int, _int, _int, _int, _vp, _int, _dbl, _vp, _vp, _vp]),
@@ -100,8 +101,11 @@ SIGNATURES.update({
     "pynqs_rbm_children_prepare": (_int, [_vp, _i64, _int, _vp, _vp, _vp, _int, _int, _vp, _vp]),
     "pynqs_rbm_forward_children": (_int, [_vp, _i64, _vp, _vp, _vp, _i64, _vp, _int, _vp, _vp, _vp, _int, _int, _vp, _vp]),
     "pynqs_rbm_forward_children_supported": (_int, [_int, _int, _int]),
+    "pynqs_rbm_children_prepare_stamped": (_int, [_vp, _i64, _int, _vp, _vp, _vp, _int, _int, C.c_uint64, _vp, _vp]),
+    "pynqs_rbm_forward_children_stamped": (_int, [_vp, _i64, _vp, _vp, _vp, _i64, _vp, _int, _vp, _vp, _vp, _int, _int, C.c_uint64, _vp, _vp]),
     "pynqs_rbm_grad_workspace": (_i64, [_i64, _int, _int, _int]),
     "pynqs_rbm_grad": (_int, [_vp, _i64, _int, _vp, _vp, _vp, _int, _int, _vp, _vp, _int, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp]),
+    "pynqs_rbm_grad_loss": (_int, [_vp, _i64, _int, _vp, _vp, _vp, _int, _int, _vp, _vp, _int, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp]),
     "pynqs_reduce_contract": (_int, [_i64, _int, _int, _int, _int, _int, _int, C.POINTER(ReduceIO), _vp, _vp, _int, _int, _vp, _vp, _vp]),    "pynqs_mcmc_rbm_supported": (_int, [_int, _int, _int]),
     "pynqs_mcmc_rbm": (_int, [_vp, _i64, _int, _int, _int, _vp, _int, _int, C.c_uint64, C.c_uint64, C.c_uint64, _int, _int, _vp, _vp, _vp, _vp]),
     "pynqs_rbm_sr_workspace": (_i64, [_i64, _int, _int, _int]),

@@ -164,9 +164,21 @@ namespace pynqs {
 
 constexpr int kMomentBlocks = 128;
 
-template <bool CPLX>
+// mean, var = E|O|^2 - |E O|^2 (2 - sum p), sd, se from the (all-reduced) moments: one thread instead of ten torch launches
+__device__ __forceinline__ void stats_finish(const double *m, double inv_world, double counts, double *__restrict__ out) {
+  const double re = m[0] * inv_world, im = m[1] * inv_world, m2 = m[2] * inv_world, ps = m[3] * inv_world;
+  double var = m2 - (re * re + im * im) * (2.0 - ps);
+  var = var > 0.0 ? var : 0.0;
+  const double sd = sqrt(var);
+  out[0] = re; out[1] = im; out[2] = var; out[3] = sd; out[4] = sd / sqrt(counts);
+}
+
+// FINISH (one rank: nothing happens between the moments and the closing arithmetic): the block that takes the last ticket also does
+// stats_finish on the four sums it has just formed -- the same additions in the same order, the same closing arithmetic, one launch less.
+template <bool CPLX, bool FINISH>
 __global__ __launch_bounds__(kBlock) void moments_kernel(const double *__restrict__ x, const double *__restrict__ prob, int64_t n,
-                                                         double *__restrict__ out, unsigned int *__restrict__ done) {
+                                                         double *__restrict__ out, unsigned int *__restrict__ done, double inv_world,
+                                                         double counts, double *__restrict__ out5) {
   __shared__ double red[4][kBlock / 64];
   __shared__ bool last;
   const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
@@ -198,22 +210,20 @@ __global__ __launch_bounds__(kBlock) void moments_kernel(const double *__restric
       double t = 0.0;
       for (unsigned b = 0; b < gridDim.x; ++b) t += out[4 * (1 + b) + tid];  // block order: reproducible
       out[tid] = t;
+      if constexpr (FINISH) red[0][tid] = t;
     }
     if (tid == 0) *done = 0;  // ready for the next call
+    if constexpr (FINISH) {
+      __syncthreads();  // (`last` is the same for the whole block)
+      if (tid == 0) stats_finish(&red[0][0], inv_world, counts, out5);
+    }
   }
 }
 
-}  // namespace pynqs
-
-namespace pynqs {
-// mean, var = E|O|^2 - |E O|^2 (2 - sum p), sd, se from the (all-reduced) moments: one thread instead of ten torch launches
 __global__ void stats_finish_kernel(const double *__restrict__ m, double inv_world, double counts, double *__restrict__ out) {
-  const double re = m[0] * inv_world, im = m[1] * inv_world, m2 = m[2] * inv_world, ps = m[3] * inv_world;
-  double var = m2 - (re * re + im * im) * (2.0 - ps);
-  var = var > 0.0 ? var : 0.0;
-  const double sd = sqrt(var);
-  out[0] = re; out[1] = im; out[2] = var; out[3] = sd; out[4] = sd / sqrt(counts);
+  stats_finish(m, inv_world, counts, out);
 }
+
 }  // namespace pynqs
 
 extern "C" int pynqs_stats_finish(const double *moments, double inv_world, double counts, double *out5, void *stream) {
@@ -225,17 +235,33 @@ extern "C" int pynqs_stats_finish(const double *moments, double inv_world, doubl
 
 extern "C" int64_t pynqs_moments_workspace(void) { return 8 * 4 * (pynqs::kMomentBlocks + 1) + 8; }
 
-extern "C" int pynqs_weighted_moments(const double *x, int is_complex, const double *prob, int64_t n, void *workspace, void *stream) {
+static int weighted_moments_launch(const double *x, int is_complex, const double *prob, int64_t n, void *workspace, bool finish, double inv_world,
+                                   double counts, double *out5, void *stream) {
   pynqs::DeviceScope device_scope_(x);
   if (n < 0) return set_error(PYNQS_EINVAL, "bad n");
   if (!workspace || (n > 0 && (!x || !prob))) return set_error(PYNQS_EINVAL, "null pointer");
+  if (finish && (!out5 || !(counts > 0.0))) return set_error(PYNQS_EINVAL, "bad arguments");
   double *out = (double *)workspace;
   unsigned int *done = (unsigned int *)(out + 4 * (kMomentBlocks + 1));
   int64_t blocks = (n + kBlock - 1) / kBlock;
   if (blocks > kMomentBlocks) blocks = kMomentBlocks;
   if (blocks < 1) blocks = 1;
   hipStream_t st = (hipStream_t)stream;
-  if (is_complex) hipLaunchKernelGGL((moments_kernel<true>), dim3((uint32_t)blocks), dim3(kBlock), 0, st, x, prob, n, out, done);
-  else hipLaunchKernelGGL((moments_kernel<false>), dim3((uint32_t)blocks), dim3(kBlock), 0, st, x, prob, n, out, done);
+#define PYNQS_MK(C, F) \
+  hipLaunchKernelGGL((moments_kernel<C, F>), dim3((uint32_t)blocks), dim3(kBlock), 0, st, x, prob, n, out, done, inv_world, counts, out5)
+  if (finish) { if (is_complex) PYNQS_MK(true, true); else PYNQS_MK(false, true); }
+  else { if (is_complex) PYNQS_MK(true, false); else PYNQS_MK(false, false); }
+#undef PYNQS_MK
   return check_launch("weighted_moments");
+}
+
+extern "C" int pynqs_weighted_moments(const double *x, int is_complex, const double *prob, int64_t n, void *workspace, void *stream) {
+  return weighted_moments_launch(x, is_complex, prob, n, workspace, false, 1.0, 1.0, nullptr, stream);
+}
+
+// pynqs_weighted_moments followed by pynqs_stats_finish in ONE launch (for one rank, where no all-reduce comes between them): the moments
+// land in the workspace as before, out5 gets bit for bit what the two calls give
+extern "C" int pynqs_weighted_moments_finish(const double *x, int is_complex, const double *prob, int64_t n, void *workspace, double inv_world,
+                                             double counts, double *out5, void *stream) {
+  return weighted_moments_launch(x, is_complex, prob, n, workspace, true, inv_world, counts, out5, stream);
 }

@@ -170,8 +170,9 @@ __global__ __launch_bounds__(kBlock) void jrbm_forward_kernel(const uint64_t *__
 //   parents [nwalkers][H + 2] : q_h(x) for h < H, then sum_h theta_h(x), then a.x
 //   factors [2 sorb + 1][HP]  : row 2 o (x'_o = +1) / 2 o + 1 (x'_o = -1): exp(-+4 W_ho) for h < H, +-2 sum_h W_ho, +-2 a_o;
 //                               the last row (1, ..., 1, 0, 0) stands for "no flip"; HP = H + 2 made odd (rows start in different banks)
-//   flag    one double after the factors: non-zero if some parent has Re theta_h < -340, where q_h = exp(-2 theta_h) leaves the range of a
-//           double: the children kernel then computes every row from scratch (rbm_forward_row, the plain kernel's body)
+//   flag    one double after the factors, raised if some parent has Re theta_h < -340, where q_h = exp(-2 theta_h) leaves the range of a
+//           double: the children kernel then computes every row from scratch (rbm_forward_row, the plain kernel's body).  Raised means
+//           non-zero for the two-launch prepare (which resets it), equal to the call's stamp for the one-launch prepare (which cannot)
 // all entries real or (re, im) by the flavour.
 // The factors 1 + q_h are NOT bounded for negative theta_h (the plain forward's are: it uses |theta_h|): q_h = e^100 for theta_h = -50, and
 // eight such factors between two renorm() calls, or one q_h beyond e^709 after four flips, overflow although psi itself is an ordinary
@@ -182,13 +183,25 @@ __global__ __launch_bounds__(kBlock) void jrbm_forward_kernel(const uint64_t *__
 // |4 Re W_ho| > 80 is stored as nan: a child that flips such an orbital gets a nan product and goes the same way.
 __host__ __device__ inline int children_hp(int H) { return (H + 2) | 1; }
 
+// (re, im) = sum_k W_ko, k ascending: the factor table's entry H before its factor +-2, and what the sums blocks of the one-launch prepare
+// kernel form again for themselves (the same loop: the same bits)
 template <bool CPLX>
-__global__ __launch_bounds__(kBlock) void rbm_children_factors_kernel(int sorb, int H, const double *__restrict__ W, const double *__restrict__ vb,
-                                                                      double *__restrict__ factors) {
+__device__ __forceinline__ void sum_w_column(const double *__restrict__ W, int sorb, int H, int o, double &re, double &im) {
+  constexpr int C = CPLX ? 2 : 1;
+  re = 0.0; im = 0.0;
+#pragma unroll 16
+  for (int k = 0; k < H; ++k) {  // (independent loads: 16 in flight)
+    re += W[((size_t)k * sorb + o) * C];
+    if constexpr (CPLX) im += W[((size_t)k * sorb + o) * C + 1];
+  }
+}
+
+// entry idx of the factor table
+template <bool CPLX>
+__device__ __forceinline__ void children_factor_entry(int idx, int sorb, int H, const double *__restrict__ W, const double *__restrict__ vb,
+                                                      double *__restrict__ factors) {
   constexpr int C = CPLX ? 2 : 1;
   const int HP = children_hp(H);
-  const int idx = blockIdx.x * kBlock + threadIdx.x;
-  if (idx == 0) factors[(size_t)(2 * sorb + 1) * HP * C] = 0.0;  // the flag (the parents kernel, launched next, may raise it)
   if (idx >= (2 * sorb + 1) * HP) return;
   const int row = idx / HP, h = idx - row * HP, o = row >> 1;
   const double sign = (row & 1) ? -1.0 : 1.0;  // x'_o
@@ -206,11 +219,7 @@ __global__ __launch_bounds__(kBlock) void rbm_children_factors_kernel(int sorb, 
       re = m;
     }
   } else if (h == H) {
-#pragma unroll 16
-    for (int k = 0; k < H; ++k) {  // (independent loads: 16 in flight)
-      re += W[((size_t)k * sorb + o) * C];
-      if constexpr (CPLX) im += W[((size_t)k * sorb + o) * C + 1];
-    }
+    sum_w_column<CPLX>(W, sorb, H, o, re, im);
     re *= 2.0 * sign; im *= 2.0 * sign;
   } else if (h == H + 1 && vb) {
     re = 2.0 * sign * vb[(size_t)o * C];
@@ -220,24 +229,23 @@ __global__ __launch_bounds__(kBlock) void rbm_children_factors_kernel(int sorb, 
   if constexpr (CPLX) factors[(size_t)idx * C + 1] = im;
 }
 
+template <bool CPLX>
+__global__ __launch_bounds__(kBlock) void rbm_children_factors_kernel(int sorb, int H, const double *__restrict__ W, const double *__restrict__ vb,
+                                                                      double *__restrict__ factors) {
+  constexpr int C = CPLX ? 2 : 1;
+  const int idx = blockIdx.x * kBlock + threadIdx.x;
+  if (idx == 0) factors[(size_t)(2 * sorb + 1) * children_hp(H) * C] = 0.0;  // the flag (the parents kernel, launched next, may raise it)
+  children_factor_entry<CPLX>(idx, sorb, H, W, vb, factors);
+}
+
 constexpr int kParentChunk = 4;
 
-// one lane per (walker, chunk of kParentChunk = 4 hidden units): blockIdx.y is the chunk, so that W_ho stays wave-uniform and 8192
-// walkers are 10 x 128 waves, not 128 (80 -> 28 us with chunks of 8 -> 17 us for Fe2S2).  Chunk 0 also leaves sum_h theta_h = sum_h b_h + sum_o x_o sum_h W_ho (from the factor
-// table's sum_h W_ho, built by the launch before this one) and a.x.
+// q_h of walker `row` for the hidden units h0 .. h0 + kParentChunk - 1; a theta_h out of range stores `raised` in the flag word
 template <int LEN, bool CPLX>
-__global__ __launch_bounds__(kBlock) void rbm_children_parents_kernel(const uint64_t *__restrict__ onv, int64_t n, int sorb, int H,
-                                                                      const double *__restrict__ W, const double *__restrict__ hb,
-                                                                      const double *__restrict__ vb, const double *__restrict__ factors,
-                                                                      double *__restrict__ table) {
+__device__ __forceinline__ void children_parent_chunk(const uint64_t (&ket)[LEN], bool live, int h0, int sorb, int H, const double *__restrict__ W,
+                                                      const double *__restrict__ hb, double *__restrict__ flag, double raised,
+                                                      double *__restrict__ out) {
   constexpr int C = CPLX ? 2 : 1;
-  const int64_t i = (int64_t)blockIdx.x * kBlock + threadIdx.x;
-  const int64_t row = i < n ? i : n - 1;
-  const int h0 = (int)blockIdx.y * kParentChunk;
-  uint64_t ket[LEN];
-#pragma unroll
-  for (int w = 0; w < LEN; ++w) ket[w] = onv[row * LEN + w];
-  double *__restrict__ out = table + (size_t)row * (size_t)(H + 2) * C;
   double tr[kParentChunk], ti[kParentChunk];
 #pragma unroll
   for (int j = 0; j < kParentChunk; ++j) {
@@ -256,8 +264,8 @@ __global__ __launch_bounds__(kBlock) void rbm_children_parents_kernel(const uint
   }
 #pragma unroll
   for (int j = 0; j < kParentChunk; ++j) {
-    if (h0 + j < H && i < n) {
-      if (!(tr[j] > -340.0)) const_cast<double *>(factors)[(size_t)(2 * sorb + 1) * children_hp(H) * C] = 1.0;  // (also for nan)
+    if (h0 + j < H && live) {
+      if (!(tr[j] > -340.0)) *flag = raised;  // (also for nan)
       const double m = exp(-2.0 * tr[j]);
       if constexpr (CPLX) {
         double sn, cs;
@@ -269,8 +277,14 @@ __global__ __launch_bounds__(kBlock) void rbm_children_parents_kernel(const uint
       }
     }
   }
-  if (blockIdx.y != 0) return;
-  const int HP = children_hp(H);
+}
+
+// sum_h theta_h = sum_h b_h + sum_o x_o sum_h W_ho and a.x of walker `row`: f + o fstride holds (2 sum_h W_ho, 2 a_o) as C doubles each
+// (rows 2 o of the factor table from their entry H on, or a copy of just these)
+template <int LEN, bool CPLX>
+__device__ __forceinline__ void children_parent_sums(const uint64_t (&ket)[LEN], bool live, int sorb, int H, const double *__restrict__ hb,
+                                                     const double *__restrict__ f, size_t fstride, double *__restrict__ out) {
+  constexpr int C = CPLX ? 2 : 1;
   double sr = 0.0, si = 0.0, axr = 0.0, axi = 0.0;
   for (int h = 0; h < H; ++h) {
     sr += hb[(size_t)h * C];
@@ -278,17 +292,89 @@ __global__ __launch_bounds__(kBlock) void rbm_children_parents_kernel(const uint
   }
   for (int o = 0; o < sorb; ++o) {
     const double x = pm1_of<LEN>(ket, o);
-    // rows 2 o of the factor table: entry H = +2 sum_h W_ho, entry H + 1 = +2 a_o  (wave-uniform addresses)
-    const double *__restrict__ f = factors + ((size_t)(2 * o) * HP + H) * C;
-    sr = fma(0.5 * x, f[0], sr);
-    axr = fma(0.5 * x, f[C], axr);
-    if constexpr (CPLX) { si = fma(0.5 * x, f[1], si); axi = fma(0.5 * x, f[C + 1], axi); }
+    const double *__restrict__ fo = f + (size_t)o * fstride;  // (wave-uniform addresses)
+    sr = fma(0.5 * x, fo[0], sr);
+    axr = fma(0.5 * x, fo[C], axr);
+    if constexpr (CPLX) { si = fma(0.5 * x, fo[1], si); axi = fma(0.5 * x, fo[C + 1], axi); }
   }
-  if (i >= n) return;
+  if (!live) return;
   out[(size_t)H * C] = sr;
   out[(size_t)(H + 1) * C] = axr;
   if constexpr (CPLX) { out[(size_t)H * C + 1] = si; out[(size_t)(H + 1) * C + 1] = axi; }
 }
+
+// The two-launch form (pynqs_rbm_children_prepare): one lane per (walker, chunk of kParentChunk = 4 hidden units): blockIdx.y is the chunk, so
+// that W_ho stays wave-uniform and 8192 walkers are 10 x 128 waves, not 128 (80 -> 28 us with chunks of 8 -> 17 us for Fe2S2).  Chunk 0 also
+// leaves sum_h theta_h = sum_h b_h + sum_o x_o sum_h W_ho (from the factor table's sum_h W_ho, built by the launch before this one) and a.x.
+template <int LEN, bool CPLX>
+__global__ __launch_bounds__(kBlock) void rbm_children_parents_kernel(const uint64_t *__restrict__ onv, int64_t n, int sorb, int H,
+                                                                      const double *__restrict__ W, const double *__restrict__ hb,
+                                                                      const double *__restrict__ vb, const double *__restrict__ factors,
+                                                                      double *__restrict__ table) {
+  constexpr int C = CPLX ? 2 : 1;
+  const int64_t i = (int64_t)blockIdx.x * kBlock + threadIdx.x;
+  const int64_t row = i < n ? i : n - 1;
+  uint64_t ket[LEN];
+#pragma unroll
+  for (int w = 0; w < LEN; ++w) ket[w] = onv[row * LEN + w];
+  double *__restrict__ out = table + (size_t)row * (size_t)(H + 2) * C;
+  const int HP = children_hp(H);
+  children_parent_chunk<LEN, CPLX>(ket, i < n, (int)blockIdx.y * kParentChunk, sorb, H, W, hb,
+                                   const_cast<double *>(factors) + (size_t)(2 * sorb + 1) * HP * C, 1.0, out);
+  if (blockIdx.y != 0) return;
+  // rows 2 o of the factor table: entry H = +2 sum_h W_ho, entry H + 1 = +2 a_o
+  children_parent_sums<LEN, CPLX>(ket, i < n, sorb, H, hb, factors + (size_t)H * C, (size_t)2 * HP * C, out);
+}
+
+// The one-launch form (pynqs_rbm_children_prepare_stamped): the same table, bit for bit, from one grid with three kinds of block --
+//   blockIdx.y <  nchunks      parent chunks as above, without chunk 0's extra sums (they were the critical path of the launch)
+//   blockIdx.y == nchunks      sums blocks: sum_h theta_h and a.x per walker; what they need of the factor table -- 2 sum_h W_ho, 2 a_o --
+//                              they form in LDS themselves, in the factor kernel's order of additions (sorb x H loads from the L2 per block)
+//   blockIdx.y == nchunks + 1  factor blocks: the parameters' factor table
+// (blockIdx.x beyond a kind's count: nothing to do).  Nothing in the launch depends on anything else in it, so the flag cannot be "reset,
+// then maybe raised": a parent out of range stores this call's STAMP instead, and the children kernel compares the word with its own.
+template <int LEN, bool CPLX>
+__global__ __launch_bounds__(kBlock) void rbm_children_prepare_kernel(const uint64_t *__restrict__ onv, int64_t n, int sorb, int H,
+                                                                      const double *__restrict__ W, const double *__restrict__ hb,
+                                                                      const double *__restrict__ vb, double *__restrict__ factors,
+                                                                      double *__restrict__ table, int nchunks, double stamp) {
+  constexpr int C = CPLX ? 2 : 1;
+  __shared__ double fs[kMaxSorb][2][C];  // the sums blocks' (2 sum_h W_ho, 2 a_o)
+  if ((int)blockIdx.y == nchunks + 1) {
+    const int64_t idx = (int64_t)blockIdx.x * kBlock + threadIdx.x;
+    if (idx < (int64_t)(2 * sorb + 1) * children_hp(H)) children_factor_entry<CPLX>((int)idx, sorb, H, W, vb, factors);
+    return;
+  }
+  const int64_t i = (int64_t)blockIdx.x * kBlock + threadIdx.x;
+  if ((int64_t)blockIdx.x * kBlock >= n) return;  // (the whole block)
+  const int64_t row = i < n ? i : n - 1;
+  uint64_t ket[LEN];
+#pragma unroll
+  for (int w = 0; w < LEN; ++w) ket[w] = onv[row * LEN + w];
+  double *__restrict__ out = table + (size_t)row * (size_t)(H + 2) * C;
+  if ((int)blockIdx.y < nchunks) {
+    children_parent_chunk<LEN, CPLX>(ket, i < n, (int)blockIdx.y * kParentChunk, sorb, H, W, hb,
+                                     factors + (size_t)(2 * sorb + 1) * children_hp(H) * C, stamp, out);
+    return;
+  }
+  for (int o = threadIdx.x; o < sorb; o += kBlock) {
+    double re, im;
+    sum_w_column<CPLX>(W, sorb, H, o, re, im);
+    fs[o][0][0] = re * 2.0;  // (the table's row 2 o: sign +1)
+    fs[o][1][0] = vb ? 2.0 * vb[(size_t)o * C] : 0.0;
+    if constexpr (CPLX) {
+      fs[o][0][1] = im * 2.0;
+      fs[o][1][1] = vb ? 2.0 * vb[(size_t)o * C + 1] : 0.0;
+    }
+  }
+  __syncthreads();
+  children_parent_sums<LEN, CPLX>(ket, i < n, sorb, H, hb, &fs[0][0][0], (size_t)2 * C, out);
+}
+
+// what the children kernels make of the flag word: a stamped call (stamp != 0) takes the word for raised only if it holds its own stamp --
+// a stale stamp of an earlier call into the same buffer or the garbage of a fresh one is "not raised", and garbage that happens to equal
+// the stamp sends the call down the from-scratch path, which is correct for every input; the unstamped pair resets the word to 0 itself
+__device__ __forceinline__ bool children_flag_raised(double word, double stamp) { return stamp != 0.0 ? word == stamp : word != 0.0; }
 
 #ifndef PYNQS_CHILD_BLOCK
 #define PYNQS_CHILD_BLOCK 1024
@@ -301,14 +387,14 @@ __global__ __launch_bounds__(kChildBlock) void rbm_forward_children_kernel(const
                                                                       int64_t nwalkers, const double *__restrict__ table,
                                                                       const double *__restrict__ factors, int sorb, int H,
                                                                       const double *__restrict__ W, const double *__restrict__ hb,
-                                                                      const double *__restrict__ vb, double *__restrict__ psi) {
+                                                                      const double *__restrict__ vb, double *__restrict__ psi, double stamp) {
   constexpr bool CPLX = FLAVOUR == PYNQS_RBM_COMPLEX;
   constexpr int C = CPLX ? 2 : 1;
   extern __shared__ __attribute__((aligned(16))) double wl[];
   const int HP = children_hp(H);
   int64_t cnt = n;
   if (count_dev) cnt = min((int64_t)max(*count_dev, 0), n);
-  if (factors[(size_t)(2 * sorb + 1) * HP * C] != 0.0) {  // (grid-uniform) parents out of range: every row from scratch
+  if (children_flag_raised(factors[(size_t)(2 * sorb + 1) * HP * C], stamp)) {  // (grid-uniform) parents out of range: every row from scratch
     const int64_t rounds = (cnt + (int64_t)gridDim.x * kChildBlock - 1) / ((int64_t)gridDim.x * kChildBlock);
     for (int64_t r = 0; r < rounds; ++r) {  // (whole waves iterate together: the parameter loads are wave-uniform)
       const int64_t i = ((int64_t)r * gridDim.x + blockIdx.x) * kChildBlock + threadIdx.x;
@@ -425,13 +511,13 @@ __global__ __launch_bounds__(kBlock) void rbm_forward_children_wave_kernel(const
                                                                            int64_t nwalkers, const double *__restrict__ table,
                                                                            const double *__restrict__ factors, int sorb, int H,
                                                                            const double *__restrict__ W, const double *__restrict__ hb,
-                                                                           const double *__restrict__ vb, double *__restrict__ psi) {
+                                                                           const double *__restrict__ vb, double *__restrict__ psi, double stamp) {
   constexpr bool CPLX = FLAVOUR == PYNQS_RBM_COMPLEX;
   constexpr int C = CPLX ? 2 : 1;
   const int HP = children_hp(H);
   int64_t cnt = n;
   if (count_dev) cnt = min((int64_t)max(*count_dev, 0), n);
-  if (factors[(size_t)(2 * sorb + 1) * HP * C] != 0.0) {  // (grid-uniform) parents out of range: every row from scratch, a thread per row
+  if (children_flag_raised(factors[(size_t)(2 * sorb + 1) * HP * C], stamp)) {  // (grid-uniform) parents out of range: every row from scratch, a thread per row
     const int64_t rounds = (cnt + (int64_t)gridDim.x * kBlock - 1) / ((int64_t)gridDim.x * kBlock);
     for (int64_t r = 0; r < rounds; ++r) {
       const int64_t i = ((int64_t)r * gridDim.x + blockIdx.x) * kBlock + threadIdx.x;
@@ -622,12 +708,18 @@ extern "C" int64_t pynqs_rbm_children_table_bytes(int64_t nwalkers, int sorb, in
   return nwalkers * (nhidden + 2) * c + (int64_t)children_lds_bytes(sorb, nhidden, flavour) + 8;
 }
 
-extern "C" int pynqs_rbm_children_prepare(const uint64_t *walkers, int64_t nwalkers, int sorb, const double *weights, const double *hidden_bias,
-                                          const double *visible_bias, int nhidden, int flavour, void *table, void *stream) {
-  pynqs::DeviceScope device_scope_(table);
+static int children_prepare_check(const uint64_t *walkers, int64_t nwalkers, int sorb, const double *weights, const double *hidden_bias,
+                                  int nhidden, int flavour, void *table) {
   if (nwalkers < 0 || nwalkers > 0x7fffffffll * kBlock || sorb < 1 || sorb > kMaxSorb || nhidden < 1 || !children_flavour_ok(flavour))
     return set_error(PYNQS_EINVAL, "bad nwalkers/sorb/nhidden/flavour");
   if (!weights || !hidden_bias || !table || (nwalkers > 0 && !walkers)) return set_error(PYNQS_EINVAL, "null pointer");
+  return PYNQS_OK;
+}
+
+extern "C" int pynqs_rbm_children_prepare(const uint64_t *walkers, int64_t nwalkers, int sorb, const double *weights, const double *hidden_bias,
+                                          const double *visible_bias, int nhidden, int flavour, void *table, void *stream) {
+  pynqs::DeviceScope device_scope_(table);
+  if (const int rc = children_prepare_check(walkers, nwalkers, sorb, weights, hidden_bias, nhidden, flavour, table)) return rc;
   const bool cplx = flavour == PYNQS_RBM_COMPLEX;
   const int len = (sorb - 1) / 64 + 1;
   hipStream_t st = (hipStream_t)stream;
@@ -651,10 +743,37 @@ extern "C" int pynqs_rbm_children_prepare(const uint64_t *walkers, int64_t nwalk
   return check_launch("rbm_children_prepare");
 }
 
-extern "C" int pynqs_rbm_forward_children(const uint64_t *onv, int64_t n, const int32_t *count_dev, const int32_t *parent,
-                                          const uint64_t *walkers, int64_t nwalkers, const void *table, int sorb, const double *weights,
-                                          const double *hidden_bias, const double *visible_bias, int nhidden, int flavour, double *psi,
-                                          void *stream) {
+// a stamp is a call number in [1, 2^53): it travels as a double, the type of the flag word
+static bool children_stamp_ok(uint64_t stamp) { return stamp >= 1 && stamp < (1ull << 53); }
+
+extern "C" int pynqs_rbm_children_prepare_stamped(const uint64_t *walkers, int64_t nwalkers, int sorb, const double *weights,
+                                                  const double *hidden_bias, const double *visible_bias, int nhidden, int flavour,
+                                                  uint64_t stamp, void *table, void *stream) {
+  pynqs::DeviceScope device_scope_(table);
+  if (const int rc = children_prepare_check(walkers, nwalkers, sorb, weights, hidden_bias, nhidden, flavour, table)) return rc;
+  if (!children_stamp_ok(stamp)) return set_error(PYNQS_EINVAL, "rbm_children_prepare_stamped: stamp must be in [1, 2^53)");
+  const bool cplx = flavour == PYNQS_RBM_COMPLEX;
+  const int len = (sorb - 1) / 64 + 1;
+  double *parents = (double *)table;
+  double *factors = parents + (size_t)nwalkers * (size_t)(nhidden + 2) * (cplx ? 2 : 1);
+  const uint32_t gf = (uint32_t)(((2 * sorb + 1) * children_hp(nhidden) + kBlock - 1) / kBlock);
+  const uint32_t gw = (uint32_t)((nwalkers + kBlock - 1) / kBlock), nchunks = (uint32_t)((nhidden + kParentChunk - 1) / kParentChunk);
+  const dim3 grid(gw > gf ? gw : gf, nchunks + 2);
+  if (grid.y > 65535u) return set_error(PYNQS_EINVAL, "too many hidden units");
+  DISPATCH_LEN(len, {
+    if (cplx)
+      hipLaunchKernelGGL((rbm_children_prepare_kernel<LEN, true>), grid, dim3(kBlock), 0, (hipStream_t)stream, walkers, nwalkers, sorb, nhidden,
+                         weights, hidden_bias, visible_bias, factors, parents, (int)nchunks, (double)stamp);
+    else
+      hipLaunchKernelGGL((rbm_children_prepare_kernel<LEN, false>), grid, dim3(kBlock), 0, (hipStream_t)stream, walkers, nwalkers, sorb, nhidden,
+                         weights, hidden_bias, visible_bias, factors, parents, (int)nchunks, (double)stamp);
+  });
+  return check_launch("rbm_children_prepare_stamped");
+}
+
+static int forward_children_launch(const uint64_t *onv, int64_t n, const int32_t *count_dev, const int32_t *parent, const uint64_t *walkers,
+                                   int64_t nwalkers, const void *table, int sorb, const double *weights, const double *hidden_bias,
+                                   const double *visible_bias, int nhidden, int flavour, double stamp, double *psi, void *stream) {
   pynqs::DeviceScope device_scope_(onv);
   if (n < 0 || n > 0x7fffffffll * kBlock || nwalkers < 0 || sorb < 1 || sorb > kMaxSorb || nhidden < 1) return set_error(PYNQS_EINVAL, "bad n/sorb/nhidden");
   if (!pynqs_rbm_forward_children_supported(sorb, nhidden, flavour))
@@ -676,10 +795,10 @@ extern "C" int pynqs_rbm_forward_children(const uint64_t *onv, int64_t n, const 
   do {                                                                                                                                       \
     if (in_lds)                                                                                                                              \
       hipLaunchKernelGGL((rbm_forward_children_kernel<LEN, F>), dim3(grid), dim3(kChildBlock), lds, st, onv, n, count_dev, parent, walkers,  \
-                         nwalkers, parents, factors, sorb, nhidden, weights, hidden_bias, visible_bias, psi);                                \
+                         nwalkers, parents, factors, sorb, nhidden, weights, hidden_bias, visible_bias, psi, stamp);                         \
     else                                                                                                                                     \
       hipLaunchKernelGGL((rbm_forward_children_wave_kernel<LEN, F>), dim3((uint32_t)wblocks), dim3(kBlock), 0, st, onv, n, count_dev,        \
-                         parent, walkers, nwalkers, parents, factors, sorb, nhidden, weights, hidden_bias, visible_bias, psi);               \
+                         parent, walkers, nwalkers, parents, factors, sorb, nhidden, weights, hidden_bias, visible_bias, psi, stamp);        \
   } while (0)
   DISPATCH_LEN(len, {
     switch (flavour) {
@@ -691,4 +810,21 @@ extern "C" int pynqs_rbm_forward_children(const uint64_t *onv, int64_t n, const 
   });
 #undef PYNQS_RC
   return check_launch("rbm_forward_children");
+}
+
+extern "C" int pynqs_rbm_forward_children(const uint64_t *onv, int64_t n, const int32_t *count_dev, const int32_t *parent,
+                                          const uint64_t *walkers, int64_t nwalkers, const void *table, int sorb, const double *weights,
+                                          const double *hidden_bias, const double *visible_bias, int nhidden, int flavour, double *psi,
+                                          void *stream) {
+  return forward_children_launch(onv, n, count_dev, parent, walkers, nwalkers, table, sorb, weights, hidden_bias, visible_bias, nhidden, flavour,
+                                 0.0, psi, stream);
+}
+
+extern "C" int pynqs_rbm_forward_children_stamped(const uint64_t *onv, int64_t n, const int32_t *count_dev, const int32_t *parent,
+                                                  const uint64_t *walkers, int64_t nwalkers, const void *table, int sorb, const double *weights,
+                                                  const double *hidden_bias, const double *visible_bias, int nhidden, int flavour,
+                                                  uint64_t stamp, double *psi, void *stream) {
+  if (!children_stamp_ok(stamp)) return set_error(PYNQS_EINVAL, "rbm_forward_children_stamped: stamp must be in [1, 2^53)");
+  return forward_children_launch(onv, n, count_dev, parent, walkers, nwalkers, table, sorb, weights, hidden_bias, visible_bias, nhidden, flavour,
+                                 (double)stamp, psi, stream);
 }

@@ -11,6 +11,10 @@
 //             and each sums its output over the 32 walkers (LDS broadcasts, +- from the walker's bit).  Partial sums per workgroup go
 //             to the workspace; the loss' share of the 32 walkers too.  (64 walkers per workgroup, 8 hidden units per thread: 58 us
 //             instead of 30 for 8192 Fe2S2 walkers -- 512 waves, each alone on its SIMD with twice the chain.)
+//             The workgroup size B is a template parameter: with B = 512 a walker has 16 threads of 2 hidden units each, i.e. two
+//             waves per SIMD with half the chain for the same 256 workgroups.  The outputs are summed over the same 32 walkers in the
+//             same order whatever B is (the gradient is the same bit for bit; the loss adds its B / 32 shares per walker in another
+//             grouping), and the workspace keeps its size.
 //   kernel 2: one thread per parameter adds the workgroups' partial sums in their fixed order: the gradient is bit-reproducible.
 #include "detcore.h"
 #include "launch.h"
@@ -21,8 +25,8 @@ namespace pynqs {
 constexpr int kGradWalkers = 32;  // per workgroup
 constexpr int kGradHidden = 32;   // per pass: 4 per thread, 8 threads per walker
 
-template <int LEN, bool CPLX>
-__global__ __launch_bounds__(kBlock) void rbm_grad_partial_kernel(const uint64_t *__restrict__ onv, int64_t n, int sorb, int H,
+template <int LEN, bool CPLX, int B>
+__global__ __launch_bounds__(B) void rbm_grad_partial_kernel(const uint64_t *__restrict__ onv, int64_t n, int sorb, int H,
                                                                   const double *__restrict__ W, const double *__restrict__ hb,
                                                                   const double *__restrict__ vb, const double *__restrict__ prob,
                                                                   const double *__restrict__ eloc, bool eloc_cplx,
@@ -32,7 +36,7 @@ __global__ __launch_bounds__(kBlock) void rbm_grad_partial_kernel(const uint64_t
   __shared__ uint64_t xs[kGradWalkers][LEN];
   __shared__ double tc[kGradWalkers][kGradHidden + 1][C];  // tanh(theta_h) conj(f_w) (real parameters: tanh(theta_h) Re f_w); +1: bank spread
   __shared__ double cf[kGradWalkers][C];                   // conj(f_w)
-  constexpr int NQ = kBlock / kGradWalkers;  // threads per walker
+  constexpr int NQ = B / kGradWalkers;  // threads per walker
   const int tid = threadIdx.x, w = tid % kGradWalkers, q = tid / kGradWalkers;
   const int64_t i = (int64_t)blockIdx.x * kGradWalkers + w;
   const bool valid = i < n;
@@ -60,7 +64,7 @@ __global__ __launch_bounds__(kBlock) void rbm_grad_partial_kernel(const uint64_t
   double lre = 0.0, lim = 0.0;
   const int SP = sorb + 1;  // outputs per hidden unit: W[h][0..sorb-1], b[h]
   for (int h0 = 0; h0 < H; h0 += kGradHidden) {
-    // ---- theta, tanh for hidden units h0 + 8 q .. + 8 of walker w
+    // ---- theta, tanh for hidden units h0 + HC q .. + HC of walker w
     constexpr int HC = kGradHidden / NQ;
     double tr[HC], ti[HC];
 #pragma unroll
@@ -113,7 +117,7 @@ __global__ __launch_bounds__(kBlock) void rbm_grad_partial_kernel(const uint64_t
     __syncthreads();
     // ---- this pass' outputs: (hh, o), o = sorb: the hidden bias
     const int nout = min(kGradHidden, H - h0) * SP;
-    for (int k = tid; k < nout; k += kBlock) {
+    for (int k = tid; k < nout; k += B) {
       const int hh = k / SP, o = k - hh * SP;
       double ar = 0.0, ai = 0.0;
       if (o < sorb) {
@@ -139,10 +143,11 @@ __global__ __launch_bounds__(kBlock) void rbm_grad_partial_kernel(const uint64_t
   }
   // ---- visible bias: sum_w conj(f_w) x_wo, and a.x for the loss
   const int64_t off_vb = (int64_t)H * SP;
-  for (int o = tid; o < sorb; o += kBlock) {
+  for (int o = tid; o < sorb; o += B) {
     const int word = o >> 6, bit = o & 63;
     double ar = 0.0, ai = 0.0;
-    for (int v = 0; v < kGradWalkers; ++v) {
+#pragma unroll 4
+    for (int v = 0; v < kGradWalkers; ++v) {  // (unrolled in full, the 32 conj(f) loaded at once cost 128 registers)
       const bool up = (xs[v][word] >> bit) & 1ull;
       ar += up ? cf[v][0] : -cf[v][0];
       if constexpr (CPLX) ai += up ? cf[v][1] : -cf[v][1];
@@ -159,6 +164,7 @@ __global__ __launch_bounds__(kBlock) void rbm_grad_partial_kernel(const uint64_t
     }
   }
   __syncthreads();
+  static_assert(NQ * kGradWalkers * 2 <= kGradWalkers * (kGradHidden + 1) * C && kGradHidden % NQ == 0, "B: 256 or 512");
   double *lr = &tc[0][0][0];  // (tc is free now) [NQ][walkers][2]
   lr[(q * kGradWalkers + w) * 2] = lre;
   lr[(q * kGradWalkers + w) * 2 + 1] = lim;
@@ -183,7 +189,7 @@ __global__ __launch_bounds__(kBlock) void rbm_grad_partial_kernel(const uint64_t
 template <bool CPLX>
 __global__ __launch_bounds__(kBlock) void rbm_grad_reduce_kernel(const double *__restrict__ partial, int64_t stride, int ngroups, int sorb, int H,
                                                                  double *__restrict__ gw, double *__restrict__ ghb, double *__restrict__ gvb,
-                                                                 double *__restrict__ loss) {
+                                                                 double *__restrict__ loss, double *__restrict__ loss_copy) {
   constexpr int C = CPLX ? 2 : 1;
   constexpr int NS = kBlock / 64;  // a block owns 64 outputs; its NS waves take contiguous slices of the workgroups' partial sums
   __shared__ double part[NS][64][2];
@@ -216,6 +222,7 @@ __global__ __launch_bounds__(kBlock) void rbm_grad_reduce_kernel(const double *_
   for (int sl = 0; sl < NS; ++sl) { re += part[sl][lane][0]; im += part[sl][lane][1]; }  // fixed order: reproducible
   if (k == nout - 1) {
     if (loss) loss[0] = re;
+    if (loss_copy) loss_copy[0] = re;  // (a second home for the caller to hand out: saves it a copy launch)
     return;
   }
   double *dst;
@@ -247,10 +254,16 @@ extern "C" int64_t pynqs_rbm_grad_workspace(int64_t n, int sorb, int nhidden, in
   return groups * grad_stride(sorb, nhidden, flavour == PYNQS_RBM_COMPLEX) * 8;
 }
 
-extern "C" int pynqs_rbm_grad(const uint64_t *onv, int64_t n, int sorb, const double *weights, const double *hidden_bias,
-                              const double *visible_bias, int nhidden, int flavour, const double *prob, const double *eloc,
-                              int eloc_is_complex, const double *e_total, const double *pow, double *grad_weights, double *grad_hidden_bias,
-                              double *grad_visible_bias, double *loss, void *workspace, void *stream) {
+// threads per workgroup of kernel 1 (see the file's head): 512 unless PYNQS_RBM_GRAD_BLOCK=256 asks for the earlier shape
+static int grad_block() {
+  static const int b = getenv("PYNQS_RBM_GRAD_BLOCK") ? atoi(getenv("PYNQS_RBM_GRAD_BLOCK")) : 512;
+  return b == 256 ? 256 : 512;
+}
+
+extern "C" int pynqs_rbm_grad_loss(const uint64_t *onv, int64_t n, int sorb, const double *weights, const double *hidden_bias,
+                                   const double *visible_bias, int nhidden, int flavour, const double *prob, const double *eloc,
+                                   int eloc_is_complex, const double *e_total, const double *pow, double *grad_weights, double *grad_hidden_bias,
+                                   double *grad_visible_bias, double *loss, double *loss_copy, void *workspace, void *stream) {
   pynqs::DeviceScope device_scope_(onv);
   if (n < 0 || n > 0x7fffffffll * kGradWalkers || sorb < 1 || sorb > kMaxSorb || nhidden < 1) return set_error(PYNQS_EINVAL, "bad n/sorb/nhidden");
   if (flavour != PYNQS_RBM_REAL && flavour != PYNQS_RBM_COMPLEX) return set_error(PYNQS_EINVAL, "rbm_grad: flavour must be PYNQS_RBM_REAL or PYNQS_RBM_COMPLEX");
@@ -262,12 +275,13 @@ extern "C" int pynqs_rbm_grad(const uint64_t *onv, int64_t n, int sorb, const do
   hipStream_t st = (hipStream_t)stream;
   double *partial = (double *)workspace;
   if (groups > 0) {
-#define PYNQS_RG(C)                                                                                                                          \
-  hipLaunchKernelGGL((rbm_grad_partial_kernel<LEN, C>), dim3((uint32_t)groups), dim3(kBlock), 0, st, onv, n, sorb, nhidden, weights, hidden_bias, \
+    const bool wide = grad_block() == 512;
+#define PYNQS_RG(C, B)                                                                                                                         \
+  hipLaunchKernelGGL((rbm_grad_partial_kernel<LEN, C, B>), dim3((uint32_t)groups), dim3(B), 0, st, onv, n, sorb, nhidden, weights, hidden_bias, \
                      visible_bias, prob, eloc, eloc_is_complex != 0, e_total, pow, partial, stride)
     DISPATCH_LEN(len, {
-      if (cplx) PYNQS_RG(true);
-      else PYNQS_RG(false);
+      if (cplx) { if (wide) PYNQS_RG(true, 512); else PYNQS_RG(true, 256); }
+      else { if (wide) PYNQS_RG(false, 512); else PYNQS_RG(false, 256); }
     });
 #undef PYNQS_RG
   }
@@ -275,9 +289,17 @@ extern "C" int pynqs_rbm_grad(const uint64_t *onv, int64_t n, int sorb, const do
   const uint32_t g2 = (uint32_t)((nout + 63) / 64);
   if (cplx)
     hipLaunchKernelGGL((rbm_grad_reduce_kernel<true>), dim3(g2), dim3(kBlock), 0, st, partial, stride, (int)groups, sorb, nhidden, grad_weights,
-                       grad_hidden_bias, grad_visible_bias, loss);
+                       grad_hidden_bias, grad_visible_bias, loss, loss_copy);
   else
     hipLaunchKernelGGL((rbm_grad_reduce_kernel<false>), dim3(g2), dim3(kBlock), 0, st, partial, stride, (int)groups, sorb, nhidden, grad_weights,
-                       grad_hidden_bias, grad_visible_bias, loss);
+                       grad_hidden_bias, grad_visible_bias, loss, loss_copy);
   return check_launch("rbm_grad");
+}
+
+extern "C" int pynqs_rbm_grad(const uint64_t *onv, int64_t n, int sorb, const double *weights, const double *hidden_bias,
+                              const double *visible_bias, int nhidden, int flavour, const double *prob, const double *eloc,
+                              int eloc_is_complex, const double *e_total, const double *pow, double *grad_weights, double *grad_hidden_bias,
+                              double *grad_visible_bias, double *loss, void *workspace, void *stream) {
+  return pynqs_rbm_grad_loss(onv, n, sorb, weights, hidden_bias, visible_bias, nhidden, flavour, prob, eloc, eloc_is_complex, e_total, pow,
+                             grad_weights, grad_hidden_bias, grad_visible_bias, loss, nullptr, workspace, stream);
 }

@@ -591,6 +591,14 @@ __global__ __launch_bounds__(kBlock) void reduce_contract_kernel(int64_t nbatch,
   }
 }
 
+// the prologue of pynqs_reduce_onepass as ONE launch: the de-duplication table to "empty" (all bits set: n16 16-byte stores, grid-stride) and
+// the four counter words to 0 -- instead of two memsets
+__global__ __launch_bounds__(kBlock) void reduce_clear_kernel(uint4 *__restrict__ table, size_t n16, uint32_t *__restrict__ counters) {
+  const uint4 ones = make_uint4(0xffffffffu, 0xffffffffu, 0xffffffffu, 0xffffffffu);
+  for (size_t i = (size_t)blockIdx.x * kBlock + threadIdx.x; i < n16; i += (size_t)gridDim.x * kBlock) table[i] = ones;
+  if (blockIdx.x == 0 && threadIdx.x < 4) counters[threadIdx.x] = 0u;
+}
+
 }  // namespace pynqs
 
 using namespace pynqs;
@@ -804,9 +812,19 @@ extern "C" int pynqs_reduce_onepass(const uint64_t *bra, int64_t nbatch, int sor
   if (io->lut_table && io->lut_nkeys < 0) return set_error(PYNQS_EINVAL, "bad lut_nkeys");
   hipStream_t st = (hipStream_t)stream;
   const int len = (sorb - 1) / 64 + 1;
-  if (hipMemsetAsync(io->counters, 0, 16, st) != hipSuccess) return check_launch("memset");
-  if (io->dedup_table &&
-      hipMemsetAsync(io->dedup_table, 0xFF, (size_t)io->dedup_slots * dedup_slot_words(len) * 8, st) != hipSuccess) return check_launch("memset");
+  // one clear kernel instead of two memsets (Fe2S2, 64 MB table: no slower than the runtime's fill of the table alone, and one launch
+  // less); PYNQS_REDUCE_CLEAR_KERNEL=0 brings the memsets back
+  static const bool clear_kernel = !(getenv("PYNQS_REDUCE_CLEAR_KERNEL") && atoi(getenv("PYNQS_REDUCE_CLEAR_KERNEL")) == 0);
+  const size_t table_bytes = io->dedup_table ? (size_t)io->dedup_slots * dedup_slot_words(len) * 8 : 0;
+  if (clear_kernel && table_bytes && table_bytes % 16 == 0 && ((uintptr_t)io->dedup_table & 15) == 0 && ((uintptr_t)io->counters & 3) == 0) {
+    const size_t n16 = table_bytes / 16;
+    size_t blocks = (n16 + (size_t)kBlock * 8 - 1) / ((size_t)kBlock * 8);  // 8 stores per thread, up to 8 workgroups per CU
+    if (blocks > 2048) blocks = 2048;
+    hipLaunchKernelGGL(reduce_clear_kernel, dim3((uint32_t)blocks), dim3(kBlock), 0, st, (uint4 *)io->dedup_table, n16, (uint32_t *)io->counters);
+  } else {
+    if (hipMemsetAsync(io->counters, 0, 16, st) != hipSuccess) return check_launch("memset");
+    if (table_bytes && hipMemsetAsync(io->dedup_table, 0xFF, table_bytes, st) != hipSuccess) return check_launch("memset");
+  }
   if (nbatch == 0) return PYNQS_OK;
   if (!bra || !plan) return set_error(PYNQS_EINVAL, "null pointer");
   uint32_t nchunks, chunk_len, max_tiles, fixed;

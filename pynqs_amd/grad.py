@@ -228,11 +228,15 @@ class FusedRbmGrad:
         params = self.params
         W, hb, vb = (p.detach().contiguous() for p in params)
         gw, ghb, gvb = self.views
-        N.check(N.lib().pynqs_rbm_grad(onv.contiguous().data_ptr(), n, self.sorb, W.data_ptr(), hb.data_ptr(), vb.data_ptr(), self.H, self.flavour,
-                                       prob.data_ptr(), el.data_ptr(), int(cplx), et.data_ptr(), pw.data_ptr() if pw is not None else None,
-                                       gw.data_ptr(), ghb.data_ptr(), gvb.data_ptr(), self.loss.data_ptr(), self.work.data_ptr(),
-                                       torch.cuda.current_stream(dev).cuda_stream), "pynqs_rbm_grad")
         ws = get_world_size()
+        # one rank: the kernel leaves the loss a second time in a fresh tensor for the caller (torch.empty launches nothing; a clone of
+        # self.loss would be a copy launch)
+        loss_out = torch.empty(1, dtype=torch.float64, device=dev) if ws == 1 else None
+        N.check(N.lib().pynqs_rbm_grad_loss(onv.contiguous().data_ptr(), n, self.sorb, W.data_ptr(), hb.data_ptr(), vb.data_ptr(), self.H,
+                                            self.flavour, prob.data_ptr(), el.data_ptr(), int(cplx), et.data_ptr(),
+                                            pw.data_ptr() if pw is not None else None, gw.data_ptr(), ghb.data_ptr(), gvb.data_ptr(),
+                                            self.loss.data_ptr(), loss_out.data_ptr() if loss_out is not None else None, self.work.data_ptr(),
+                                            torch.cuda.current_stream(dev).cuda_stream), "pynqs_rbm_grad_loss")
         ev = None
         if self.events is not None:
             ev = [torch.cuda.Event(enable_timing=True) for _ in range(2)]
@@ -247,7 +251,7 @@ class FusedRbmGrad:
             self.events.append(ev)
         for p, v in zip(params, self.views):
             p.grad = v
-        return self.loss * ws if ws > 1 else self.loss.clone()
+        return self.loss * ws if ws > 1 else loss_out
 
 
 class FusedJastrowRbmGrad:

@@ -45,16 +45,27 @@ def dist_stats(x: Tensor, prob: Tensor, counts: Optional[int] = None, world_size
 _WS: dict = {}  # device -> zero-initialised workspace of pynqs_weighted_moments
 
 
+def _on_kernel(x: Tensor, prob: Tensor) -> bool:
+    return x.is_cuda and prob.is_cuda and prob.dtype == torch.float64 and x.dtype in (torch.float64, torch.complex128) and x.dim() == 1
+
+
+def _workspace(dev) -> Tensor:
+    from . import _native as N
+
+    ws = _WS.get(dev)
+    if ws is None:
+        ws = _WS[dev] = torch.zeros(N.lib().pynqs_moments_workspace() // 8, dtype=torch.float64, device=dev)
+    return ws
+
+
 def _moments(x: Tensor, prob: Tensor) -> Tensor:
     """[sum p Re x, sum p Im x, sum p |x|^2, sum p] as one float64 tensor: one HIP kernel for float64 / complex128 on
     the GPU (pynqs_weighted_moments), torch ops otherwise."""
-    if x.is_cuda and prob.is_cuda and prob.dtype == torch.float64 and x.dtype in (torch.float64, torch.complex128) and x.dim() == 1:
+    if _on_kernel(x, prob):
         from . import _native as N
 
         dev = x.device
-        ws = _WS.get(dev)
-        if ws is None:
-            ws = _WS[dev] = torch.zeros(N.lib().pynqs_moments_workspace() // 8, dtype=torch.float64, device=dev)
+        ws = _workspace(dev)
         xc, pc = x.contiguous(), prob.contiguous()
         N.check(N.lib().pynqs_weighted_moments(xc.data_ptr(), int(x.is_complex()), pc.data_ptr(), x.numel(), ws.data_ptr(),
                                                torch.cuda.current_stream(dev).cuda_stream), "pynqs_weighted_moments")
@@ -69,7 +80,19 @@ def _moments(x: Tensor, prob: Tensor) -> Tensor:
 
 def dist_stats_moments(x: Tensor, prob: Tensor, counts: Optional[int] = None, world_size: int = 1):
     """dist_stats_onepass on the fused moments kernel: 1 kernel + 1 all-reduce of 4 doubles + the closing arithmetic.
-    counts defaults to len(x) * world_size (equal shards), so no device-to-host copy is needed."""
+    counts defaults to len(x) * world_size (equal shards), so no device-to-host copy is needed.  With ONE rank nothing happens between the
+    moments and the closing arithmetic: one launch does both (pynqs_weighted_moments_finish, bit for bit the two launches' result)."""
+    if get_world_size() == 1 and _on_kernel(x, prob):
+        from . import _native as N
+
+        dev = x.device
+        out = torch.empty(6, dtype=torch.float64, device=dev)
+        xc, pc = x.contiguous(), prob.contiguous()
+        N.check(N.lib().pynqs_weighted_moments_finish(xc.data_ptr(), int(x.is_complex()), pc.data_ptr(), x.numel(), _workspace(dev).data_ptr(),
+                                                      1.0 / world_size, float(counts if counts is not None else x.size(0)), out.data_ptr(),
+                                                      torch.cuda.current_stream(dev).cuda_stream), "pynqs_weighted_moments_finish")
+        mean = torch.view_as_complex(out[0:2]).reshape(()) if torch.is_complex(x) else out[0]
+        return mean, out[2], out[3], out[4]
     m = _moments(x, prob)
     if counts is None:
         counts = x.size(0) * get_world_size()
