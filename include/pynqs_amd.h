@@ -639,6 +639,17 @@ int pynqs_rbm_sr_cg_step(int mode, int64_t np, double *y, const double *rhs, dou
  *        states (pRBM: 0; every pRBM proposal is accepted, |psi| = 1).  Each chain's hidden-unit state is recomputed from the parameters
  *        at the start of the launch; keep launches short (the Python layer bounds the steps per launch).
  *   pynqs_mcmc_rbm_supported : 1 if (sorb, nhidden, flavour) has a fused kernel (nhidden <= 512, a valid table layout), else 0.
+ *   pynqs_mcmc_jrbm : pynqs_mcmc_rbm for the real RBM times a two-body Jastrow factor, psi(x) = exp(a.x + x^T M x) prod_h 2cosh(theta_h)
+ *        (pynqs_eloc_jrbm's amplitude).  rbm_table: pynqs_rbm_table_build; jastrow_table: pynqs_jastrow_table_build, of which the block
+ *        S = M + M^T (zero diagonal) and tr M are read.  Every other argument, the random streams, records, n_accept and lnpsi as for
+ *        pynqs_mcmc_rbm with PYNQS_RBM_REAL.  With F the 2 or 4 flipped orbitals and x the state before the move,
+ *            ln|psi_J(x')| - ln|psi_J(x)| = -2 sum_{i in F} x_i r_i + 4 sum_{i<j in F} S_ij x_i x_j,    r_i = sum_j S_ij x_j,
+ *        r_i summed anew at every step (at most 4 ceil(sorb / G) loads and fma per lane, G = the lanes of a chain), nothing of the
+ *        Jastrow factor kept between steps; at the start of a launch ln|psi| takes tr M + sum_{i<j} S_ij x_i x_j.  With M = 0 the
+ *        decisions and lnpsi are pynqs_mcmc_rbm's bit for bit.
+ *   pynqs_mcmc_jrbm_supported : 1 where pynqs_mcmc_rbm_supported with PYNQS_RBM_REAL holds and sorb has a Jastrow table, else 0.
+ *   pynqs_mcmc_jrbm_form : host only, the shape alone decides: bit 0 = the RBM table is copied to LDS (it is at most 64 KiB, as in
+ *        pynqs_mcmc_rbm), bit 1 = S (sorb^2 doubles) too (both together within the 64 KiB); so 3, 1 or 0, and -1 where unsupported.
  *   pynqs_mcmc_accept : step t of any ansatz, after pynqs_spin_flip_rand(states, ..., seed, (t << 32) + chain_base, proposals).
  *        psi / psi_proposals: double[nchains] or, with is_complex, (re, im) pairs; states and psi take the proposals' values where the
  *        move is accepted; n_accept (may be NULL) is bumped there; record_row (may be NULL): uint64[nchains][len] <- the states after
@@ -648,6 +659,11 @@ int pynqs_mcmc_rbm_supported(int sorb, int nhidden, int flavour);
 int pynqs_mcmc_rbm(uint64_t *states, int64_t nchains, int sorb, int noA, int noB, const void *table, int nhidden, int flavour,
                    uint64_t seed, uint64_t chain_base, uint64_t t0, int nsteps, int every, uint64_t *records, int64_t *n_accept,
                    double *lnpsi, void *stream);
+int pynqs_mcmc_jrbm_supported(int sorb, int nhidden);
+int pynqs_mcmc_jrbm_form(int sorb, int nhidden);
+int pynqs_mcmc_jrbm(uint64_t *states, int64_t nchains, int sorb, int noA, int noB, const void *rbm_table, const void *jastrow_table,
+                    int nhidden, uint64_t seed, uint64_t chain_base, uint64_t t0, int nsteps, int every, uint64_t *records,
+                    int64_t *n_accept, double *lnpsi, void *stream);
 int pynqs_mcmc_accept(uint64_t *states, double *psi, const uint64_t *proposals, const double *psi_proposals, int64_t nchains,
                       int sorb, int is_complex, uint64_t seed, uint64_t chain_base, uint64_t t, uint64_t *record_row,
                       int64_t *n_accept, void *stream);

@@ -124,6 +124,9 @@ SIGNATURES.update({
     "pynqs_eloc_jrbm": (_int, [_vp, _i64, _int, _int, _int, _int, _vp, _vp, _vp, _int, _vp, _vp, _vp]),
     "pynqs_jrbm_forward": (_int, [_vp, _i64, _int, _vp, _vp, _vp, _vp, _int, _vp, _vp]),
     "pynqs_jastrow_grad_workspace": (_i64, [_i64, _int]),
+    "pynqs_mcmc_jrbm_supported": (_int, [_int, _int]),
+    "pynqs_mcmc_jrbm_form": (_int, [_int, _int]),
+    "pynqs_mcmc_jrbm": (_int, [_vp, _i64, _int, _int, _int, _vp, _vp, _int, C.c_uint64, C.c_uint64, C.c_uint64, _int, _int, _vp, _vp, _vp, _vp]),
     "pynqs_jastrow_grad": (_int, [_vp, _i64, _int, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp]),
 })
 

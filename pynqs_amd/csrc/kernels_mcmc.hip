@@ -1,7 +1,8 @@
 // kernels_mcmc.hip -- many-chain Metropolis sampling (PyNQS' Sampler.MCMC, vmc/sample.py:480-569, one chain in a Python loop there):
 //   pynqs_mcmc_rbm    : the fused kernel for RBM amplitudes; every chain runs `nsteps` steps inside one launch
+//   pynqs_mcmc_jrbm   : the same for the real RBM times the Jastrow factor exp(x^T M x) (pynqs_amd.rbm.JastrowRBM; JAS of mcmc_rbm_kernel)
 //   pynqs_mcmc_accept : one accept / reject step of any ansatz, from proposals of pynqs_spin_flip_rand and their psi
-// Both follow the rule written out in include/pynqs_amd.h; with equal psi they make the same decisions (the fused kernel's ratio is
+// All follow the rule written out in include/pynqs_amd.h; with equal psi they make the same decisions (the fused kernel's ratio is
 // exp(2 (ln|psi'| - ln|psi|)), the generic one |psi'|^2 / |psi|^2: equal to rounding).
 //
 // The fused kernel.  G lanes (a power of two, G * kMcmcSlots >= H) own one chain; lane g holds the hidden units h = g + G j, j < 8, as
@@ -76,14 +77,29 @@ struct McmcTable {
   int H, stride;                              // row stride in elements (real: doubles, complex: (re, im) pairs)
   int64_t offWt, offE4p, offE4m, offHb, offVb;  // in elements
   int64_t total;                              // table size in doubles
+  const double *jas;                          // the Jastrow table (pynqs_mcmc_jrbm only)
 };
 
 constexpr int64_t kMcmcLdsBytes = 64 * 1024;
 
-template <int LEN, int FLAVOUR, bool IN_LDS>
+// where the chain kernel reads S, the first block of the Jastrow table (rbm.h): no Jastrow factor; from the table in the L2; from LDS,
+// behind the RBM table (both within kMcmcLdsBytes)
+constexpr int kJasNone = 0, kJasL2 = 1, kJasLds = 2;
+
+// JAS != kJasNone: the real flavour times the Jastrow factor exp(x^T M x) (pynqs_mcmc_jrbm; T.jas = the Jastrow table).  Every Jastrow
+// statement is under if constexpr, so the instantiations without it compile to what they were.  With S = M + M^T without its diagonal,
+//   ln|psi_J(x)| = tr M + sum_{i<j} S_ij x_i x_j   (at the start of a launch: lane g sums the rows i = g (mod G), the butterfly that
+//                                                   sums the hidden units' ln 2cosh sums these shares too)
+//   ln|psi_J(x')| - ln|psi_J(x)| = -2 sum_{i in F} x_i r_i + 4 sum_{i<j in F} S_ij x_i x_j,   r_i = sum_j S_ij x_j,
+// r_i formed at every step from the state before the move: lane g sums the orbitals j = g (mod G) of the <= 4 rows and adds its share
+// to the value it hands the hidden units' butterfly (no second butterfly; every lane ends with the same bits); the pair term (<= 6
+// products) is added by every lane after it.  Nothing of the Jastrow factor is carried from step to step but ln|psi| itself.
+template <int LEN, int FLAVOUR, bool IN_LDS, int JAS = kJasNone>
 __global__ __launch_bounds__(kBlock) void mcmc_rbm_kernel(uint64_t *__restrict__ states, int64_t nchains, SDParams p, McmcTable T, int G,
                                                           uint64_t seed, uint64_t chain_base, uint64_t t0, int nsteps, int every,
                                                           uint64_t *__restrict__ rec, int64_t *__restrict__ nacc, double *__restrict__ lnpsi_out) {
+  static_assert(JAS == kJasNone || FLAVOUR == PYNQS_RBM_REAL, "the Jastrow factor multiplies the real flavour only");
+  static_assert(JAS != kJasLds || IN_LDS, "S joins the RBM table in LDS, never alone");
   constexpr bool CPLX = FLAVOUR == PYNQS_RBM_COMPLEX;
   constexpr bool HIDDEN = FLAVOUR != PYNQS_RBM_PHASE;  // (pRBM: |psi| = 1, every proposal is accepted)
   constexpr int C = CPLX ? 2 : 1;
@@ -91,9 +107,12 @@ __global__ __launch_bounds__(kBlock) void mcmc_rbm_kernel(uint64_t *__restrict__
   extern __shared__ __attribute__((aligned(16))) double lds_tab[];
   if constexpr (IN_LDS) {
     for (int64_t k = threadIdx.x; k < T.total; k += kBlock) lds_tab[k] = T.tab[k];
+    if constexpr (JAS == kJasLds)
+      for (int64_t k = threadIdx.x; k < jastrow_pairs(p.sorb); k += kBlock) lds_tab[T.total + k] = T.jas[k];
     __syncthreads();
   }
   const double *__restrict__ tab = IN_LDS ? lds_tab : T.tab;
+  const double *__restrict__ S = JAS == kJasLds ? lds_tab + T.total : T.jas;  // [sorb][sorb] (JAS != kJasNone)
   const int64_t gt = (int64_t)blockIdx.x * kBlock + threadIdx.x;
   const int64_t i = gt / G;
   const int g = (int)(gt - i * G);
@@ -127,8 +146,16 @@ __global__ __launch_bounds__(kBlock) void mcmc_rbm_kernel(uint64_t *__restrict__
       }
     }
     for (int o = 0; o < sorb; ++o) ax = fma(pm1_of<LEN>(x, o), tab[(T.offVb + o) * C], ax);
+    if constexpr (JAS != kJasNone) {
+      for (int a = g; a < sorb; a += G) {
+        double r = 0.0;
+        for (int b = a + 1; b < sorb; ++b) r = fma(S[a * sorb + b], pm1_of<LEN>(x, b), r);
+        part = fma(pm1_of<LEN>(x, a), r, part);
+      }
+    }
     lnh = group_sum(part, G);
     lnpsi = lnh + (FLAVOUR == PYNQS_RBM_TANH ? log(fabs(tanh(ax))) : ax);
+    if constexpr (JAS != kJasNone) lnpsi += T.jas[3 * jastrow_pairs(sorb)];  // tr M (JastrowLayout::offTr)
   }
 
   int64_t accepted = 0;
@@ -215,14 +242,40 @@ __global__ __launch_bounds__(kBlock) void mcmc_rbm_kernel(uint64_t *__restrict__
           nthr[j] = tr; nthi[j] = ti; nqr[j] = ur; nqi[j] = ui;
         }
       }
-      const double dh = group_sum(fma(CPLX ? 0.5 : 1.0, log(pn / po), lsum), G);
+      double share = fma(CPLX ? 0.5 : 1.0, log(pn / po), lsum);
+      if constexpr (JAS != kJasNone) {
+        // -2 sum_{i in F} x_i r_i = sum_f 2 fs[f] r_f (fs is the NEW value -x_i), this lane's orbitals of r_f
+        double r[4] = {0.0, 0.0, 0.0, 0.0};
+        for (int b = g; b < sorb; b += G) {
+          const double xb = pm1_of<LEN>(x, b);
+#pragma unroll
+          for (int f = 0; f < 4; ++f)
+            if (f < nf) r[f] = fma(S[fo[f] * sorb + b], xb, r[f]);
+        }
+        double jl = 0.0;
+#pragma unroll
+        for (int f = 0; f < 4; ++f) jl = fma(2.0 * fs[f], r[f], jl);
+        share += jl;
+      }
+      const double dh = group_sum(share, G);
       double dax = 0.0;
 #pragma unroll
       for (int f = 0; f < 4; ++f)
         if (f < nf) dax = fma(2.0 * fs[f], tab[(T.offVb + fo[f]) * C], dax);
       const double axn = ax + dax;
       const double lvn = FLAVOUR == PYNQS_RBM_TANH ? log(fabs(tanh(axn))) : 0.0;  // (-inf: x' has amplitude zero)
-      const double dl = dh + (FLAVOUR == PYNQS_RBM_TANH ? lvn - log(fabs(tanh(ax))) : dax);
+      double dl = dh + (FLAVOUR == PYNQS_RBM_TANH ? lvn - log(fabs(tanh(ax))) : dax);
+      if constexpr (JAS != kJasNone) {
+        // + 4 sum_{i<j in F} S_ij x_i x_j (x_i x_j = fs_i fs_j); the same loads and products in every lane of the group
+        double pr = 0.0;
+#pragma unroll
+        for (int f = 0; f < 4; ++f) {
+#pragma unroll
+          for (int f2 = f + 1; f2 < 4; ++f2)
+            if (f2 < nf) pr = fma(fs[f] * fs[f2], S[fo[f] * sorb + fo[f2]], pr);
+        }
+        dl = fma(4.0, pr, dl);
+      }
       // u <= |psi'|^2 / |psi|^2, and every proposal from a state of amplitude zero (then dl is +inf or nan)
       accept = !(lnpsi > -INFINITY) || mcmc_uniform(seed, t, c) <= exp(2.0 * dl);
       if (accept) {
@@ -332,6 +385,7 @@ extern "C" int pynqs_mcmc_rbm(uint64_t *states, int64_t nchains, int sorb, int n
   if (!states || !table) return set_error(PYNQS_EINVAL, "null pointer");
   McmcTable T;
   T.tab = (const double *)table;
+  T.jas = nullptr;
   T.H = nhidden;
   if (flavour == PYNQS_RBM_COMPLEX) {
     CrbmLayout cl;
@@ -370,6 +424,62 @@ extern "C" int pynqs_mcmc_rbm(uint64_t *states, int64_t nchains, int sorb, int n
   });
 #undef PYNQS_MC
   return check_launch("mcmc_rbm");
+}
+
+// bit 0: the RBM table in LDS, bit 1: S too (both within kMcmcLdsBytes); the shape alone decides
+static int mcmc_jrbm_form(int sorb, const RbmLayout &rl) {
+  if (rl.total * 8 > kMcmcLdsBytes) return 0;
+  return (rl.total + jastrow_pairs(sorb)) * 8 <= kMcmcLdsBytes ? 3 : 1;
+}
+
+extern "C" int pynqs_mcmc_jrbm_supported(int sorb, int nhidden) {
+  JastrowLayout jl;
+  return pynqs_mcmc_rbm_supported(sorb, nhidden, PYNQS_RBM_REAL) && make_jastrow_layout(sorb, &jl) ? 1 : 0;
+}
+
+extern "C" int pynqs_mcmc_jrbm_form(int sorb, int nhidden) {
+  if (!pynqs_mcmc_jrbm_supported(sorb, nhidden)) return -1;
+  RbmLayout rl;
+  make_rbm_layout(sorb, nhidden, &rl);
+  return mcmc_jrbm_form(sorb, rl);
+}
+
+extern "C" int pynqs_mcmc_jrbm(uint64_t *states, int64_t nchains, int sorb, int noA, int noB, const void *rbm_table,
+                               const void *jastrow_table, int nhidden, uint64_t seed, uint64_t chain_base, uint64_t t0, int nsteps,
+                               int every, uint64_t *records, int64_t *n_accept, double *lnpsi, void *stream) {
+  pynqs::DeviceScope device_scope_(states);
+  SDParams p;
+  if (!make_sd_params(sorb, noA + noB, noA, noB, &p)) return set_error(PYNQS_EINVAL, "mcmc_jrbm: bad sorb/noA/noB");
+  if (!pynqs_mcmc_jrbm_supported(sorb, nhidden)) return set_error(PYNQS_EINVAL, "mcmc_jrbm: unsupported nhidden / sorb");
+  if (nchains < 0 || nsteps < 0 || every < 1) return set_error(PYNQS_EINVAL, "mcmc_jrbm: bad nchains/nsteps/every");
+  if (chain_base + (uint64_t)nchains > (1ull << 32)) return set_error(PYNQS_EINVAL, "mcmc_jrbm: chain indices must stay below 2^32");
+  if (nchains == 0) return PYNQS_OK;
+  if (!states || !rbm_table || !jastrow_table) return set_error(PYNQS_EINVAL, "null pointer");
+  RbmLayout rl;
+  make_rbm_layout(sorb, nhidden, &rl);
+  McmcTable T;
+  T.tab = (const double *)rbm_table;
+  T.jas = (const double *)jastrow_table;
+  T.H = nhidden;
+  T.stride = rl.Hq; T.offWt = rl.offWt; T.offE4p = rl.offE4p; T.offE4m = rl.offE4m; T.offHb = rl.offHb; T.offVb = rl.offVb;
+  T.total = rl.total;
+  const int G = mcmc_group(nhidden);
+  const uint64_t grid = ((uint64_t)nchains * G + kBlock - 1) / kBlock;
+  if (grid > 0x7fffffffull) return set_error(PYNQS_EINVAL, "nchains too large for one launch");
+  const int len = (sorb - 1) / 64 + 1;
+  hipStream_t st = (hipStream_t)stream;
+  const int form = mcmc_jrbm_form(sorb, rl);
+  const size_t lds = form == 3 ? (size_t)(T.total + jastrow_pairs(sorb)) * 8 : form == 1 ? (size_t)T.total * 8 : 0;
+#define PYNQS_MCJ(JAS, IN_LDS)                                                                                                          \
+  hipLaunchKernelGGL((mcmc_rbm_kernel<LEN, PYNQS_RBM_REAL, IN_LDS, JAS>), dim3((uint32_t)grid), dim3(kBlock), lds, st, states, nchains, \
+                     p, T, G, seed, chain_base, t0, nsteps, every, records, n_accept, lnpsi)
+  DISPATCH_LEN(len, {
+    if (form == 3) PYNQS_MCJ(kJasLds, true);
+    else if (form == 1) PYNQS_MCJ(kJasL2, true);
+    else PYNQS_MCJ(kJasL2, false);
+  });
+#undef PYNQS_MCJ
+  return check_launch("mcmc_jrbm");
 }
 
 extern "C" int pynqs_mcmc_accept(uint64_t *states, double *psi, const uint64_t *proposals, const double *psi_proposals, int64_t nchains,

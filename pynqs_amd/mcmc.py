@@ -7,6 +7,8 @@ world_size > 1.  Here `nchains` chains advance together, with the rule and the r
 - an RBM (pynqs_amd.rbm.RealRBM "real" / "tanh" / "pRBM" / "cos", ComplexRBM, or PyNQS' RBMWavefunction: whatever
   energy._real_rbm_params / _complex_rbm_params recognise) runs in the fused kernel pynqs_mcmc_rbm: every chain keeps its hidden-unit
   state on chip and a step costs a few multiplications per hidden unit, many steps per launch;
+- a Jastrow-RBM (pynqs_amd.rbm.JastrowRBM, float64 parameters on the GPU: energy._jastrow_rbm_params) runs in the same kernel with the
+  Jastrow factor's ln-ratio added to the hidden units' (pynqs_mcmc_jrbm);
 - any other ansatz takes the generic path, one step at a time: pynqs_spin_flip_rand -> the module's forward on the proposals (as
   +-1 rows, onv_to_tensor) -> pynqs_mcmc_accept.
 
@@ -26,7 +28,7 @@ from . import _native as N
 from . import public_function as pf
 from .distributed import get_rank, get_world_size, shard_bounds
 
-__all__ = ["MCMCSampler", "mcmc_rbm_supported"]
+__all__ = ["MCMCSampler", "mcmc_rbm_supported", "mcmc_jrbm_supported"]
 
 # chain-steps x hidden units of one fused launch at most: ~1 ms of kernel time at the Fe2S2 size, a few ms at sorb 192
 _LAUNCH_WORK = 1 << 28
@@ -38,6 +40,25 @@ def mcmc_rbm_supported(sorb: int, num_hidden: int, rbm_type: str = "real") -> bo
     return flav is not None and bool(N.lib().pynqs_mcmc_rbm_supported(sorb, num_hidden, flav))
 
 
+def mcmc_jrbm_supported(sorb: int, num_hidden: int) -> bool:
+    """Whether a JastrowRBM of this size has the fused chain kernel (pynqs_mcmc_jrbm)."""
+    return bool(N.lib().pynqs_mcmc_jrbm_supported(sorb, num_hidden))
+
+
+def _jastrow_params(ansatz):
+    """energy._jastrow_rbm_params where every parameter is float64 (float32 parameters take the generic path, whose forward runs in
+    float32: the float64 kernel would decide otherwise), else None."""
+    from .energy import _jastrow_rbm_params
+
+    prm = _jastrow_rbm_params(ansatz)
+    if prm is None:
+        return None
+    m = getattr(ansatz, "module", ansatz)
+    if any(t.dtype != torch.float64 or not t.is_cuda for t in (m.weights, m.hidden_bias, m.visible_bias, m.jastrow)):
+        return None
+    return prm
+
+
 def _electrons(onv_words: Tensor) -> Tuple[Tensor, Tensor]:
     """(alpha count, beta count) per row of uint64 words (viewed as int64)."""
     bits = onv_words.view(torch.uint8).view(onv_words.size(0), -1)
@@ -46,14 +67,22 @@ def _electrons(onv_words: Tensor) -> Tuple[Tensor, Tensor]:
 
 
 class _Fused:
-    """The parameters of an RBM laid out for pynqs_mcmc_rbm (rebuilt on every run: the parameters change between runs)."""
+    """The parameters of an RBM laid out for pynqs_mcmc_rbm, or of a Jastrow-RBM for pynqs_mcmc_jrbm (rebuilt on every run: the
+    parameters change between runs)."""
 
     def __init__(self, ansatz, sorb: int) -> None:
         from .energy import _complex_rbm_params, _real_rbm_params
 
-        self.log_scale, self.real_valued = 0.0, True
+        self.log_scale, self.real_valued, self.jastrow_table = 0.0, True, None
         real = _real_rbm_params(ansatz)
-        if real is not None:
+        jas = _jastrow_params(ansatz) if real is None else None
+        if jas is not None:
+            W, hb, vb, M = jas
+            self.kind, self.params = "real", (W, hb, vb, M)
+            if W.size(1) != sorb:
+                raise RuntimeError(f"RBM weights have {W.size(1)} visible units, the sampler sorb = {sorb}")
+            self.table, self.jastrow_table = CX.RBMTable(W, hb, vb), CX.JastrowTable(M)
+        elif real is not None:
             W, hb, vb, kind = real
             self.kind, self.params = kind, (W, hb, vb)
             if W.size(1) != sorb:
@@ -75,11 +104,16 @@ class _Fused:
         real = _real_rbm_params(ansatz)
         if real is not None:
             return mcmc_rbm_supported(sorb, real[0].size(0), real[3]) and real[0].size(1) == sorb
+        jas = _jastrow_params(ansatz)
+        if jas is not None:
+            return mcmc_jrbm_supported(sorb, jas[0].size(0)) and jas[0].size(1) == sorb
         cplx = _complex_rbm_params(ansatz)
         return cplx is not None and mcmc_rbm_supported(sorb, cplx[0].size(0), "complex") and cplx[0].size(1) == sorb
 
     def psi(self, onv: Tensor, sorb: int) -> Tensor:
         """psi of the rows (the module's values: cos -> the complex kernel's value times 2^-H, real-valued)."""
+        if self.jastrow_table is not None:
+            return CX.jrbm_forward(onv, *self.params, sorb)
         W, hb, vb = self.params
         if self.kind == "complex":
             psi = CX.rbm_forward(onv, W, hb, vb, sorb, "complex")
@@ -145,10 +179,16 @@ class MCMCSampler:
     def _fused_launch(self, f: _Fused, nsteps: int, every: int, record: bool) -> Optional[Tensor]:
         rec = torch.empty((nsteps // every, self.nchains, self.len), dtype=torch.int64, device=self.device) if record else None
         self.lnpsi = torch.empty(self.nchains, dtype=torch.float64, device=self.device)
-        N.check(N.lib().pynqs_mcmc_rbm(self._x.data_ptr(), self.nchains, self.sorb, self.noA, self.noB, f.table.data_ptr(), f.nhidden,
-                                       f.flavour, self.seed, self.chain_base, self.step, nsteps, every,
-                                       rec.data_ptr() if record else None, self.n_accept.data_ptr() if record else None,
-                                       self.lnpsi.data_ptr(), self._stream()), "pynqs_mcmc_rbm")
+        if f.jastrow_table is not None:
+            N.check(N.lib().pynqs_mcmc_jrbm(self._x.data_ptr(), self.nchains, self.sorb, self.noA, self.noB, f.table.data_ptr(),
+                                            f.jastrow_table.data_ptr(), f.nhidden, self.seed, self.chain_base, self.step, nsteps, every,
+                                            rec.data_ptr() if record else None, self.n_accept.data_ptr() if record else None,
+                                            self.lnpsi.data_ptr(), self._stream()), "pynqs_mcmc_jrbm")
+        else:
+            N.check(N.lib().pynqs_mcmc_rbm(self._x.data_ptr(), self.nchains, self.sorb, self.noA, self.noB, f.table.data_ptr(), f.nhidden,
+                                           f.flavour, self.seed, self.chain_base, self.step, nsteps, every,
+                                           rec.data_ptr() if record else None, self.n_accept.data_ptr() if record else None,
+                                           self.lnpsi.data_ptr(), self._stream()), "pynqs_mcmc_rbm")
         self.step += nsteps
         return rec
 

@@ -75,7 +75,8 @@ class JastrowRBM(nn.Module):
     (vmc/ansatz/hybrid/multi.py) of the reference's RBMWavefunction, rbm_type "real", and its Jastrow (vmc/ansatz/rbm/rbm_other.py:
     exp(sum_ij M_ij x_i x_j), prod_dim = 1).  jastrow: M [sorb, sorb], any real matrix -- not symmetric, diagonal allowed (it scales psi).
     forward() is plain torch, so every generic route of the package works with it; the fused routes are its own: SIMPLE local energies
-    (pynqs_amd.energy, pynqs_eloc_jrbm) and pynqs_amd.grad.FusedJastrowRbmGrad.  On purpose NOT a RealRBM and without an `rbm_type`: the
+    (pynqs_amd.energy, pynqs_eloc_jrbm), pynqs_amd.grad.FusedJastrowRbmGrad and the many-chain sampler (pynqs_amd.mcmc,
+    pynqs_mcmc_jrbm).  On purpose NOT a RealRBM and without an `rbm_type`: the
     fused routes of the plain RBMs recognise their modules by those two and would drop M."""
 
     def __init__(self, weights: Tensor, hidden_bias: Tensor, visible_bias: Tensor, jastrow: Tensor) -> None:
