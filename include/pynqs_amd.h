@@ -608,6 +608,27 @@ int pynqs_rbm_sr_matvec(const uint64_t *onv, int64_t n, int sorb, int nhidden, i
                         const double *obar, const double *v, double *y, void *stream);
 int pynqs_rbm_sr_cg_step(int mode, int64_t np, double *y, const double *rhs, double *d, double *r, double *p, double *scalars,
                          double inv_world, double diag_shift, double tol, void *stream);
+/* The same for the Jastrow-RBM, psi(x) = exp(a.x + x^T M x) prod_h 2cosh(theta_h) (pynqs_jrbm_forward; all parameters real).  The parameter
+ * vector gains the jastrow block: weights [nhidden][sorb], hidden_bias, visible_bias, jastrow [sorb][sorb]; P = nhidden sorb + nhidden +
+ * sorb + sorb^2, and obar, v, y (and the vectors of pynqs_rbm_sr_cg_step, which serves this solve unchanged with np = P) are flat
+ * double[P] of this layout.  O_n = (tanh theta_nh x_no, tanh theta_nh, x_no, x_ni x_nj); with Z the jastrow block of v,
+ *      c_n = x_n . z_a + sum_h tanh theta_nh (z_b,h + sum_o z_W,ho x_no) + x_n^T Z x_n - Obar . z,      y_k = sum_n p_n O_nk c_n;
+ * the first three blocks of y are those of pynqs_rbm_sr_matvec with this c_n, and y_M[i][j] = sum_n p_n c_n x_ni x_nj.
+ *  - S does not depend on M.  It is singular on the jastrow block by construction: O_ii = 1 (row and column ii of S are zero, so
+ *    d_ii = F_ii / diag_shift), O_ij = O_ji, and with fixed particle numbers sum_j x_i x_j is proportional to x_i; diag_shift
+ *    regularises all of it and conjugate gradients from zero stay in the range of S.
+ *  - Only the symmetric part of Z reaches c_n: the kernel evaluates x^T Z x = sum_i Z_ii + sum_{i<j} (Z_ij + Z_ji) x_i x_j.
+ *  - The jastrow block of y (and of obar) is bit-symmetric, y_M[i][j] == y_M[j][i]: one sum is formed for i <= j and written twice.
+ *   pynqs_jrbm_sr_workspace : [host] bytes (-1 on bad arguments): the tanh table double[nhidden][n], the workgroups' partial sums
+ *        (ceil(n / 32) x (nhidden (sorb + 1) + sorb + ceil(sorb / 2) (sorb + 1)) doubles: the jastrow block as its triangle), Obar . z.
+ *   pynqs_jrbm_sr_prepare   : as pynqs_rbm_sr_prepare (the table does not depend on M); obar gains sum_n p_n x_ni x_nj.  n = 0: obar = 0.
+ *   pynqs_jrbm_sr_matvec    : as pynqs_rbm_sr_matvec.  Z is staged in LDS (symmetrised) for sorb <= 128 and read from global memory
+ *        above.  v and y must not overlap.  n = 0: y = 0.                                                                            */
+int64_t pynqs_jrbm_sr_workspace(int64_t n, int sorb, int nhidden);
+int pynqs_jrbm_sr_prepare(const uint64_t *onv, int64_t n, int sorb, const double *weights, const double *hidden_bias, int nhidden,
+                          const double *prob, void *workspace, double *obar, void *stream);
+int pynqs_jrbm_sr_matvec(const uint64_t *onv, int64_t n, int sorb, int nhidden, const double *prob, const void *workspace,
+                         const double *obar, const double *v, double *y, void *stream);
 
 /* ---- many-chain Metropolis sampling (vmc/sample.py:480-569, Sampler.MCMC; the reference runs one chain in a Python loop) -------------
  * Semantics shared by both entry points (and by pynqs_amd/mcmc.py, which drives them):

@@ -112,6 +112,9 @@ SIGNATURES.update({
     "pynqs_rbm_sr_prepare": (_int, [_vp, _i64, _int, _vp, _vp, _int, _int, _vp, _vp, _vp, _vp]),
     "pynqs_rbm_sr_matvec": (_int, [_vp, _i64, _int, _int, _int, _vp, _vp, _vp, _vp, _vp, _vp]),
     "pynqs_rbm_sr_cg_step": (_int, [_int, _i64, _vp, _vp, _vp, _vp, _vp, _vp, _dbl, _dbl, _dbl, _vp]),
+    "pynqs_jrbm_sr_workspace": (_i64, [_i64, _int, _int]),
+    "pynqs_jrbm_sr_prepare": (_int, [_vp, _i64, _int, _vp, _vp, _int, _vp, _vp, _vp, _vp]),
+    "pynqs_jrbm_sr_matvec": (_int, [_vp, _i64, _int, _int, _vp, _vp, _vp, _vp, _vp, _vp]),
     "pynqs_mcmc_accept": (_int, [_vp, _vp, _vp, _vp, _i64, _int, _int, C.c_uint64, C.c_uint64, C.c_uint64, _vp, _vp, _vp]),
     "pynqs_rdm_scatter": (_int, [_vp, _i64, _int, _int, _int, _int, _vp, _vp, _int, _vp, _vp, _vp]),
     "pynqs_rdm_rbm_supported": (_int, [_int, _int, _int, _int, _int]),

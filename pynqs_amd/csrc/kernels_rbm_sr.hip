@@ -15,6 +15,15 @@
 //   cg_step : the vector part of an iteration in ONE workgroup (P_real <= 2 x 29 160 at the largest size served), the scalars in device
 //             memory, dot products in a fixed order; a `done` flag turns later steps into no-ops so that the host enqueues several
 //             iterations between read-backs.
+//   Jastrow-RBM (JAS; psi = exp(a.x + x^T M x) prod_h 2cosh theta_h, real parameters): O gains the block x_i x_j, P = H sorb + H + sorb +
+//             sorb^2, and c_n the term x_n^T Z x_n with Z the jastrow block of z.  Only the symmetric part of Z reaches it:
+//             x^T Z x = sum_i Z_ii + sum_{i<j} (Z_ij + Z_ji) x_i x_j.  The 8 threads of a walker share the rows (row i: thread i mod 8) and
+//             add the entries S_ij = Z_ij + Z_ji with the sign of x_j, then the row with the sign of x_i: no multiply.  S is staged in LDS
+//             when it leaves room for two workgroups per CU (sorb <= 128), else read from Z in the L2 (the addresses are the same for the
+//             32 walkers of a half-wave).  The thread of a walker adds the eight shares AFTER the RBM sum, so Z = 0 leaves the RBM blocks'
+//             bits.  The outputs sum_w g_w x_wi x_wj are formed for i <= j only, the sign from two bits, and kept behind the visible-bias
+//             block in the paired-rows order of jas_pair_at; the reduce kernel writes (i, j) and (j, i) from the same sum: the Jastrow
+//             block of y is bit-symmetric.
 // Everything is float64 and bit-reproducible.
 #include "detcore.h"
 #include "launch.h"
@@ -29,14 +38,32 @@ constexpr int kSrCgBlock = 1024;
 __host__ __device__ static inline int64_t sr_nout(int sorb, int H) { return (int64_t)H * (sorb + 1) + sorb; }  // per workgroup: (W[h][:], b[h]) rows, then a
 static inline int64_t sr_table_doubles(int64_t n, int H, bool cplx) { return n * H * (cplx ? 2 : 1); }
 
+// The upper triangle i <= j of an [sorb][sorb] matrix as ceil(sorb / 2) rows of sorb + 1: rows r and sorb - 1 - r of the triangle
+// (sorb - r and r + 1 entries) share one.  Odd sorb: the middle row pairs with itself and its second half stays empty.
+__host__ __device__ static inline int jas_pair_count(int sorb) { return ((sorb + 1) / 2) * (sorb + 1); }
+__device__ __forceinline__ int jas_pair_at(int sorb, int i, int j) {  // i <= j
+  return i < (sorb + 1) / 2 ? i * (sorb + 1) + (j - i) : (sorb - 1 - i) * (sorb + 1) + j + 1;
+}
+__device__ __forceinline__ bool jas_pair_decode(int sorb, int k, int &i, int &j) {
+  const int r = k / (sorb + 1), c = k - r * (sorb + 1);
+  if (c < sorb - r) { i = r; j = r + c; return true; }
+  i = sorb - 1 - r; j = c - 1;
+  return i != r;
+}
+constexpr int kSrJasLdsBytes = 66 * 1024;  // S in LDS up to here: sorb <= 128 (66 048 bytes beside 13 KiB of static LDS, two workgroups per CU)
+static inline bool sr_jas_in_lds(int sorb) { return (int64_t)jas_pair_count(sorb) * 8 <= kSrJasLdsBytes; }
+
 // PREP: A = weights, B = hidden bias; writes the table and the partial sums of Obar.  Otherwise: A, B, VA = z_W, z_b, z_a (the vector's
 // blocks in the parameters' layout), dot = Obar . z; reads the table and writes the partial sums of y.
-template <int LEN, bool CPLX, bool PREP>
+// JAS (0: none; 1: S from Z in global memory; 2: S staged in the dynamic LDS): Z = the jastrow block of z (unused by PREP).
+template <int LEN, bool CPLX, bool PREP, int JAS = 0>
 __global__ __launch_bounds__(kBlock) void rbm_sr_partial_kernel(const uint64_t *__restrict__ onv, int64_t n, int sorb, int H,
                                                                 const double *__restrict__ A, const double *__restrict__ B,
                                                                 const double *__restrict__ VA, const double *__restrict__ prob,
                                                                 double *__restrict__ table, const double *__restrict__ dot,
-                                                                double *__restrict__ partial, int64_t stride) {
+                                                                double *__restrict__ partial, int64_t stride,
+                                                                const double *__restrict__ Z = nullptr) {
+  static_assert(!JAS || !CPLX, "the Jastrow-RBM has real parameters");
   constexpr int C = CPLX ? 2 : 1;
   constexpr int NQ = kBlock / kSrWalkers;  // threads per walker
   constexpr int HC = kSrHidden / NQ;
@@ -44,6 +71,7 @@ __global__ __launch_bounds__(kBlock) void rbm_sr_partial_kernel(const uint64_t *
   __shared__ double tc[kSrWalkers][kSrHidden + 1][C];  // PREP: tanh(theta_h) p_w; else conj(tanh(theta_h)) g_w; +1: bank spread
   __shared__ double cf[kSrWalkers][C];                 // PREP: p_w; else g_w = p_w c_w
   __shared__ double cq[NQ][kSrWalkers][C];             // the threads' shares of c_w
+  __shared__ double cjq[JAS != 0 && !PREP ? NQ : 1][kSrWalkers];  // JAS: their shares of x_w^T Z x_w
   const int tid = threadIdx.x, w = tid % kSrWalkers, q = tid / kSrWalkers;
   const int64_t i = (int64_t)blockIdx.x * kSrWalkers + w;
   const bool valid = i < n;
@@ -58,6 +86,36 @@ __global__ __launch_bounds__(kBlock) void rbm_sr_partial_kernel(const uint64_t *
   }
   double gr = pr, gi = 0.0;  // the walker's weight in the sums
   if constexpr (!PREP) {
+    double cj = 0.0;  // this thread's rows of x^T Z x
+    if constexpr (JAS != 0) {
+      extern __shared__ __attribute__((aligned(16))) double ssym[];  // JAS 2: S (diagonal: Z_ii) in the order of jas_pair_at
+      if constexpr (JAS == 2) {
+        const int np2 = jas_pair_count(sorb);
+        for (int k = tid; k < np2; k += kBlock) {
+          int a, b;
+          if (jas_pair_decode(sorb, k, a, b)) ssym[k] = a == b ? Z[(size_t)a * sorb + a] : Z[(size_t)a * sorb + b] + Z[(size_t)b * sorb + a];
+        }
+        __syncthreads();
+      }
+      for (int a = q; a < sorb; a += NQ) {
+        const int at = jas_pair_at(sorb, a, a) - a;  // + b: (a, b)
+        double r = 0.0;
+#pragma unroll
+        for (int wd = 0; wd < LEN; ++wd) {
+          const int b0 = max(a + 1, 64 * wd), b1 = min(sorb, 64 * wd + 64);
+          if (b0 >= b1) continue;
+          uint64_t bits = ket[wd] >> (b0 & 63);
+#pragma unroll 4
+          for (int b = b0; b < b1; ++b) {
+            const double sv = JAS == 2 ? ssym[at + b] : Z[(size_t)a * sorb + b] + Z[(size_t)b * sorb + a];
+            r += (bits & 1ull) ? sv : -sv;
+            bits >>= 1;
+          }
+        }
+        cj += pm1_of<LEN>(ket, a) > 0.0 ? r : -r;
+        cj += JAS == 2 ? ssym[at + a] : Z[(size_t)a * sorb + a];
+      }
+    }
     // ---- c_w: this thread's hidden units
     double cr = 0.0, ci = 0.0;
     for (int h0 = 0; h0 < H; h0 += kSrHidden) {
@@ -98,6 +156,7 @@ __global__ __launch_bounds__(kBlock) void rbm_sr_partial_kernel(const uint64_t *
     }
     cq[q][w][0] = cr;
     if constexpr (CPLX) cq[q][w][1] = ci;
+    if constexpr (JAS != 0) cjq[q][w] = cj;
     __syncthreads();
     if (q == 0) {
       double ar = 0.0, ai = 0.0;  // x . z_a
@@ -110,6 +169,12 @@ __global__ __launch_bounds__(kBlock) void rbm_sr_partial_kernel(const uint64_t *
       for (int k = 0; k < NQ; ++k) {
         ar += cq[k][w][0];
         if constexpr (CPLX) ai += cq[k][w][1];
+      }
+      if constexpr (JAS != 0) {  // after the RBM sum: Z = 0 leaves its bits
+        double jr = 0.0;
+#pragma unroll
+        for (int k = 0; k < NQ; ++k) jr += cjq[k][w];
+        ar += jr;
       }
       ar -= dot[0];
       if constexpr (CPLX) ai -= dot[1];
@@ -231,18 +296,39 @@ __global__ __launch_bounds__(kBlock) void rbm_sr_partial_kernel(const uint64_t *
     out[C * (off_vb + o)] = ar;
     if constexpr (CPLX) out[C * (off_vb + o) + 1] = ai;
   }
+  if constexpr (JAS != 0) {
+    // ---- jastrow, i <= j: sum_w g_w x_wi x_wj
+    const int64_t off_j = off_vb + sorb;
+    const int np2 = jas_pair_count(sorb);
+    for (int k = tid; k < np2; k += kBlock) {
+      int a, b;
+      double ar = 0.0;
+      if (jas_pair_decode(sorb, k, a, b)) {
+        const int wa = a >> 6, ba = a & 63, wb = b >> 6, bb = b & 63;
+#pragma unroll 8
+        for (int v = 0; v < kSrWalkers; ++v) {
+          const bool same = ((xs[v][wa] >> ba) & 1ull) == ((xs[v][wb] >> bb) & 1ull);
+          const double g = cf[v][0];
+          ar += same ? g : -g;
+        }
+      }
+      out[off_j + k] = ar;
+    }
+  }
 }
 
 // out (flat, the parameters' layout: weights [H][sorb], hidden_bias [H], visible_bias [sorb], x2 for pairs) = the workgroups' partial
 // sums in a fixed order
-template <bool CPLX>
+// JAS: the jastrow block [sorb][sorb] follows; its partial sums hold i <= j (jas_pair_at), written to (i, j) and (j, i)
+template <bool CPLX, bool JAS = false>
 __global__ __launch_bounds__(kBlock) void rbm_sr_reduce_kernel(const double *__restrict__ partial, int64_t stride, int ngroups, int sorb, int H,
                                                                double *__restrict__ flat) {
+  static_assert(!JAS || !CPLX, "the Jastrow-RBM has real parameters");
   constexpr int C = CPLX ? 2 : 1;
   constexpr int NS = kBlock / 64;  // a block owns 64 outputs; its NS waves take contiguous slices of the workgroups' partial sums
   __shared__ double part[NS][64][2];
   const int SP = sorb + 1;
-  const int64_t nout = sr_nout(sorb, H);
+  const int64_t nrbm = sr_nout(sorb, H), nout = nrbm + (JAS ? jas_pair_count(sorb) : 0);
   const int lane = threadIdx.x & 63, slice = threadIdx.x >> 6;
   const int64_t k = (int64_t)blockIdx.x * 64 + lane;
   const int per = (ngroups + NS - 1) / NS, g_lo = min(slice * per, ngroups), g_hi = min(g_lo + per, ngroups);
@@ -268,6 +354,17 @@ __global__ __launch_bounds__(kBlock) void rbm_sr_reduce_kernel(const double *__r
   re = 0.0; im = 0.0;
 #pragma unroll
   for (int sl = 0; sl < NS; ++sl) { re += part[sl][lane][0]; im += part[sl][lane][1]; }  // fixed order: reproducible
+  if constexpr (JAS) {
+    if (k >= nrbm) {
+      int a, b;
+      if (jas_pair_decode(sorb, (int)(k - nrbm), a, b)) {
+        double *__restrict__ m = flat + (int64_t)H * sorb + H + sorb;
+        m[(size_t)a * sorb + b] = re;
+        m[(size_t)b * sorb + a] = re;
+      }
+      return;
+    }
+  }
   int64_t at;
   if (k < (int64_t)H * SP) {
     const int64_t h = k / SP;
@@ -410,33 +507,56 @@ extern "C" int64_t pynqs_rbm_sr_workspace(int64_t n, int sorb, int nhidden, int 
   return (sr_table_doubles(n, nhidden, cplx) + groups * sr_nout(sorb, nhidden) * (cplx ? 2 : 1) + 2) * 8;
 }
 
-template <bool PREP>
+// JAS: the Jastrow-RBM (flavour real): VA + sorb = Z for the product, the jastrow block behind every vector
+template <bool PREP, bool JAS = false>
 static int sr_launch(const uint64_t *onv, int64_t n, int sorb, int H, int flavour, const double *A, const double *B, const double *VA,
                      const double *prob, void *workspace, const double *obar, double *flat, hipStream_t st, const char *what) {
   const bool cplx = flavour == PYNQS_RBM_COMPLEX;
   const int C = cplx ? 2 : 1;
   const int len = (sorb - 1) / 64 + 1;
-  const int64_t groups = (n + kSrWalkers - 1) / kSrWalkers, stride = sr_nout(sorb, H) * C;
+  const int64_t nout = sr_nout(sorb, H) + (JAS ? jas_pair_count(sorb) : 0);
+  const int64_t groups = (n + kSrWalkers - 1) / kSrWalkers, stride = nout * C;
   double *table = (double *)workspace;
   double *partial = table + sr_table_doubles(n, H, cplx);
   double *dot = partial + groups * stride;
   if (groups > 0) {
     if constexpr (!PREP) {
-      const int64_t np = (int64_t)H * sorb + H + sorb;
+      const int64_t np = (int64_t)H * sorb + H + sorb + (JAS ? (int64_t)sorb * sorb : 0);
       if (cplx) hipLaunchKernelGGL((rbm_sr_dot_kernel<true>), dim3(1), dim3(kBlock), 0, st, obar, A, np, dot);  // (A = the whole flat z)
       else hipLaunchKernelGGL((rbm_sr_dot_kernel<false>), dim3(1), dim3(kBlock), 0, st, obar, A, np, dot);
     }
+    if constexpr (JAS) {
+      const double *Z = PREP ? nullptr : VA + sorb;
+      const bool lds = !PREP && sr_jas_in_lds(sorb);
+      const size_t dyn = lds ? (size_t)jas_pair_count(sorb) * 8 : 0;
+#define PYNQS_SR(J)                                                                                                                       \
+  do {                                                                                                                                    \
+    auto kern = rbm_sr_partial_kernel<LEN, false, PREP, J>;                                                                               \
+    /* above 64 KiB of LDS a kernel has to be told; the static arrays take 11 KiB of that */                                              \
+    if (dyn > 48 * 1024 && hipFuncSetAttribute(reinterpret_cast<const void *>(kern), hipFuncAttributeMaxDynamicSharedMemorySize, (int)dyn) != hipSuccess) \
+      return check_launch("hipFuncSetAttribute");                                                                                         \
+    hipLaunchKernelGGL(kern, dim3((uint32_t)groups), dim3(kBlock), dyn, st, onv, n, sorb, H, A, B, VA, prob, table, dot, partial, stride, Z); \
+  } while (0)
+      DISPATCH_LEN(len, {
+        if constexpr (PREP) PYNQS_SR(1);  // (no Z: only the jastrow block of Obar)
+        else if (lds) PYNQS_SR(2);
+        else PYNQS_SR(1);
+      });
+#undef PYNQS_SR
+    } else {
 #define PYNQS_SR(CP)                                                                                                                      \
   hipLaunchKernelGGL((rbm_sr_partial_kernel<LEN, CP, PREP>), dim3((uint32_t)groups), dim3(kBlock), 0, st, onv, n, sorb, H, A, B, VA, prob, table, \
-                     dot, partial, stride)
-    DISPATCH_LEN(len, {
-      if (cplx) PYNQS_SR(true);
-      else PYNQS_SR(false);
-    });
+                     dot, partial, stride, (const double *)nullptr)
+      DISPATCH_LEN(len, {
+        if (cplx) PYNQS_SR(true);
+        else PYNQS_SR(false);
+      });
 #undef PYNQS_SR
+    }
   }
-  const uint32_t g2 = (uint32_t)((sr_nout(sorb, H) + 63) / 64);
-  if (cplx) hipLaunchKernelGGL((rbm_sr_reduce_kernel<true>), dim3(g2), dim3(kBlock), 0, st, partial, stride, (int)groups, sorb, H, flat);
+  const uint32_t g2 = (uint32_t)((nout + 63) / 64);
+  if constexpr (JAS) hipLaunchKernelGGL((rbm_sr_reduce_kernel<false, true>), dim3(g2), dim3(kBlock), 0, st, partial, stride, (int)groups, sorb, H, flat);
+  else if (cplx) hipLaunchKernelGGL((rbm_sr_reduce_kernel<true>), dim3(g2), dim3(kBlock), 0, st, partial, stride, (int)groups, sorb, H, flat);
   else hipLaunchKernelGGL((rbm_sr_reduce_kernel<false>), dim3(g2), dim3(kBlock), 0, st, partial, stride, (int)groups, sorb, H, flat);
   return check_launch(what);
 }
@@ -468,4 +588,30 @@ extern "C" int pynqs_rbm_sr_cg_step(int mode, int64_t np, double *y, const doubl
   hipLaunchKernelGGL(rbm_sr_cg_kernel, dim3(1), dim3(kSrCgBlock), 0, (hipStream_t)stream, mode, np, y, rhs, d, r, p, scalars, inv_world,
                      diag_shift, tol);
   return check_launch("rbm_sr_cg_step");
+}
+
+// ---- the Jastrow-RBM: the same kernels with JAS, the jastrow block [sorb][sorb] behind every vector
+extern "C" int64_t pynqs_jrbm_sr_workspace(int64_t n, int sorb, int nhidden) {
+  if (!sr_args_ok(n, sorb, nhidden, PYNQS_RBM_REAL)) return -1;
+  const int64_t groups = (n + kSrWalkers - 1) / kSrWalkers;
+  return (sr_table_doubles(n, nhidden, false) + groups * (sr_nout(sorb, nhidden) + jas_pair_count(sorb)) + 2) * 8;
+}
+
+extern "C" int pynqs_jrbm_sr_prepare(const uint64_t *onv, int64_t n, int sorb, const double *weights, const double *hidden_bias, int nhidden,
+                                     const double *prob, void *workspace, double *obar, void *stream) {
+  pynqs::DeviceScope device_scope_(obar);
+  if (!sr_args_ok(n, sorb, nhidden, PYNQS_RBM_REAL)) return set_error(PYNQS_EINVAL, "jrbm_sr_prepare: bad n/sorb/nhidden");
+  if (!weights || !hidden_bias || !obar || !workspace || (n > 0 && (!onv || !prob))) return set_error(PYNQS_EINVAL, "null pointer");
+  return sr_launch<true, true>(onv, n, sorb, nhidden, PYNQS_RBM_REAL, weights, hidden_bias, nullptr, prob, workspace, nullptr, obar,
+                               (hipStream_t)stream, "jrbm_sr_prepare");
+}
+
+extern "C" int pynqs_jrbm_sr_matvec(const uint64_t *onv, int64_t n, int sorb, int nhidden, const double *prob, const void *workspace,
+                                    const double *obar, const double *v, double *y, void *stream) {
+  pynqs::DeviceScope device_scope_(y);
+  if (!sr_args_ok(n, sorb, nhidden, PYNQS_RBM_REAL)) return set_error(PYNQS_EINVAL, "jrbm_sr_matvec: bad n/sorb/nhidden");
+  if (!obar || !v || !y || !workspace || (n > 0 && (!onv || !prob))) return set_error(PYNQS_EINVAL, "null pointer");
+  const int64_t nw = (int64_t)nhidden * sorb, nb = nhidden;
+  return sr_launch<false, true>(onv, n, sorb, nhidden, PYNQS_RBM_REAL, v, v + nw, v + nw + nb, prob, (void *)workspace, obar, y,
+                                (hipStream_t)stream, "jrbm_sr_matvec");
 }

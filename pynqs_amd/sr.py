@@ -8,7 +8,11 @@ of size n x P or P x P exists, where the reference materialises O[n, P], builds 
     F = the energy gradient exactly as FusedRbmGrad returns it,        theta <- theta - lr d   with torch.optim.SGD(lr).
 
 Under torch.distributed every rank holds its shard of the walkers (probabilities pre-scaled by the world size, as everywhere in this
-package): one all-reduce of Obar per solve and one of the product per iteration; the decision to stop is rank 0's, broadcast."""
+package): one all-reduce of Obar per solve and one of the product per iteration; the decision to stop is rank 0's, broadcast.
+
+FusedRbmSR serves RealRBM / ComplexRBM, FusedJastrowRbmSR the JastrowRBM (the parameter vector gains the block jastrow [sorb, sorb] and
+the product the term x^T Z x; pynqs_jrbm_sr_*).  Both are the private _FusedSR (buffers, conjugate gradients, all-reduces, status
+broadcast) with their own gradient object and their own two native calls."""
 from __future__ import annotations
 
 import warnings
@@ -17,34 +21,25 @@ import torch
 from torch import Tensor, nn
 
 from .distributed import get_world_size
-from .grad import FusedRbmGrad
+from .grad import FusedJastrowRbmGrad, FusedRbmGrad
 
 # slots of the solver's device scalars (include/pynqs_amd.h: PYNQS_SR_*)
 _RHO, _RHS2, _DONE, _ITER, _TRUE2, _PAP, _CONVERGED, _BREAKDOWN, _NSC = range(9)
 _INIT, _STEP, _RESIDUAL = 0, 1, 2
 
 
-class FusedRbmSR:
-    """SR direction for pynqs_amd.rbm.RealRBM (rbm_type "real") and ComplexRBM with float64 parameters on the GPU (what FusedRbmGrad
-    accepts; anything else: ValueError).  Calling convention of FusedRbmGrad:
+class _FusedSR:
+    """What FusedRbmSR and FusedJastrowRbmSR share: the flat buffers, the conjugate-gradient driver on pynqs_rbm_sr_cg_step, the
+    all-reduces and the status broadcast.  A subclass sets `_who`, builds its
+    gradient object, calls _setup() and provides _workspace_bytes(n), _native_prepare(n) and _native_matvec(v, y)."""
 
-        loss = sr(onv, state_prob, eloc, e_total, extra_psi_pow=1.0)
+    _who = "_FusedSR"
 
-    After the call every p.grad is a view of the direction d (so torch.optim.SGD(lr) performs theta <- theta - lr d), `energy_grad` holds
-    F per parameter, `iterations` the CG iterations, `converged` whether the TRUE residual met `tol`, `residual` the true relative
-    residual |F - (S + diag_shift) d| / |F| from one product after the loop (0 when F = 0).  CG starts from zero; when the recurrence's
-    residual meets the tolerance the true residual is formed, and if that does not meet it the iteration goes on from the current
-    iterate with the true residual, inside the same max_iter.  When max_iter is reached the last iterate is installed, `converged` is
-    False and a warning is issued.  Every sum runs in a fixed order: two calls give the same bits.
-    prepare(onv, state_prob), matvec(v_flat) -> S v (all-reduced) and solve(rhs_flat) -> d_flat serve users with their own right-hand
-    side; flat vectors have the layout weights, hidden_bias, visible_bias (each as stored, (re, im) interleaved)."""
-
-    def __init__(self, nqs: nn.Module, sorb: int, diag_shift: float = 0.02, tol: float = 1e-6, max_iter: int = 1000, check_every: int = 8) -> None:
-        self.grad = FusedRbmGrad(nqs, sorb)  # (refuses other modules)
+    def _setup(self, grad, sorb: int, diag_shift: float, tol: float, max_iter: int, check_every: int) -> None:
         if not (diag_shift >= 0.0) or not (tol > 0.0) or max_iter < 1 or check_every < 1:
-            raise ValueError("FusedRbmSR: diag_shift >= 0, tol > 0, max_iter >= 1, check_every >= 1")
-        g = self.grad
-        self.N, self.module, self.sorb, self.H, self.flavour = g.N, g.module, sorb, g.H, g.flavour
+            raise ValueError(f"{self._who}: diag_shift >= 0, tol > 0, max_iter >= 1, check_every >= 1")
+        g = self.grad = grad
+        self.N, self.module, self.sorb, self.H = g.N, g.module, sorb, g.H
         self.diag_shift, self.tol, self.max_iter, self.check_every = float(diag_shift), float(tol), int(max_iter), int(check_every)
         dev = g.flat.device
         self.np = g.flat.numel() - 1  # P_real
@@ -72,30 +67,21 @@ class FusedRbmSR:
 
     def prepare(self, onv: Tensor, state_prob: Tensor) -> None:
         """tanh theta of the walkers -> the table, Obar (all-reduced) -> self.obar; the walkers and probabilities are kept for matvec."""
-        N, dev = self.N, self.d.device
+        dev = self.d.device
         n = onv.size(0)
         if onv.dtype != torch.uint8 or onv.dim() != 2 or onv.size(1) != 8 * ((self.sorb - 1) // 64 + 1) or onv.device != dev:
-            raise ValueError("FusedRbmSR: walkers as packed onv uint8[n, 8 len] on the parameters' device")
+            raise ValueError(f"{self._who}: walkers as packed onv uint8[n, 8 len] on the parameters' device")
         prob = (state_prob.real if state_prob.is_complex() else state_prob).to(device=dev, dtype=torch.float64).contiguous()
         if prob.numel() != n:
-            raise ValueError("FusedRbmSR: one probability per walker")
-        need = N.lib().pynqs_rbm_sr_workspace(n, self.sorb, self.H, self.flavour)
+            raise ValueError(f"{self._who}: one probability per walker")
+        need = self._workspace_bytes(n)
         if need < 0:
-            raise ValueError("FusedRbmSR: bad sizes")
+            raise ValueError(f"{self._who}: bad sizes")
         if self.work is None or self.work.numel() * 8 < need:
             self.work = torch.empty(max(need // 8, 1), dtype=torch.float64, device=dev)
-        W, hb, _ = (p.detach().contiguous() for p in self.params)
         self._onv, self._prob = onv.contiguous(), prob
-        N.check(N.lib().pynqs_rbm_sr_prepare(self._onv.data_ptr(), n, self.sorb, W.data_ptr(), hb.data_ptr(), self.H, self.flavour, prob.data_ptr(),
-                                             self.work.data_ptr(), self.obar.data_ptr(), self._stream()), "pynqs_rbm_sr_prepare")
+        self._native_prepare(n)
         self._all_reduce(self.obar, divide=True)
-
-    def tanh_table(self) -> Tensor:
-        """tanh theta of the prepared walkers, [n, H] (complex128 for a ComplexRBM): a copy of the kernels' table, for tests"""
-        n, H = self._onv.size(0), self.H
-        if self.flavour == self.N.RBM_COMPLEX:
-            return torch.view_as_complex(self.work[:2 * n * H].view(H, n, 2)).t().contiguous()
-        return self.work[:n * H].view(H, n).t().contiguous()
 
     def _all_reduce(self, t: Tensor, divide: bool) -> None:
         ws = get_world_size()
@@ -116,16 +102,13 @@ class FusedRbmSR:
     def _product(self, v: Tensor, y: Tensor, divide: bool) -> None:
         """y <- the all-reduced SUM of the ranks' products (divided by the world size if `divide`)"""
         if self._onv is None:
-            raise RuntimeError("FusedRbmSR: prepare(onv, state_prob) first")
-        N = self.N
-        N.check(N.lib().pynqs_rbm_sr_matvec(self._onv.data_ptr(), self._onv.size(0), self.sorb, self.H, self.flavour, self._prob.data_ptr(),
-                                            self.work.data_ptr(), self.obar.data_ptr(), v.data_ptr(), y.data_ptr(), self._stream()),
-                "pynqs_rbm_sr_matvec")
+            raise RuntimeError(f"{self._who}: prepare(onv, state_prob) first")
+        self._native_matvec(v, y)
         self._all_reduce(y, divide)
 
     def _flat_arg(self, v: Tensor) -> Tensor:
         if v.numel() != self.np or v.device != self.d.device:
-            raise ValueError(f"FusedRbmSR: a flat vector of {self.np} doubles on the parameters' device")
+            raise ValueError(f"{self._who}: a flat vector of {self.np} doubles on the parameters' device")
         return v.detach().to(torch.float64).reshape(-1).contiguous()
 
     def matvec(self, v_flat: Tensor) -> Tensor:
@@ -181,7 +164,7 @@ class FusedRbmSR:
         self.converged = bool(st[_CONVERGED])
         self.residual = (st[_TRUE2] / st[_RHS2]) ** 0.5 if st[_RHS2] > 0 else 0.0
         if not self.converged:
-            warnings.warn(f"FusedRbmSR: conjugate gradients stopped after {self.iterations} iterations at a relative residual of "
+            warnings.warn(f"{self._who}: conjugate gradients stopped after {self.iterations} iterations at a relative residual of "
                           f"{self.residual:.3e} (tol {self.tol:.1e}, max_iter {self.max_iter}); the last iterate is used", RuntimeWarning, stacklevel=2)
         return self.d
 
@@ -194,3 +177,93 @@ class FusedRbmSR:
         for p, v in zip(self.params, self.views):
             p.grad = v
         return loss
+
+
+class FusedRbmSR(_FusedSR):
+    """SR direction for pynqs_amd.rbm.RealRBM (rbm_type "real") and ComplexRBM with float64 parameters on the GPU (what FusedRbmGrad
+    accepts; anything else: ValueError).  Calling convention of FusedRbmGrad:
+
+        loss = sr(onv, state_prob, eloc, e_total, extra_psi_pow=1.0)
+
+    After the call every p.grad is a view of the direction d (so torch.optim.SGD(lr) performs theta <- theta - lr d), `energy_grad` holds
+    F per parameter, `iterations` the CG iterations, `converged` whether the TRUE residual met `tol`, `residual` the true relative
+    residual |F - (S + diag_shift) d| / |F| from one product after the loop (0 when F = 0).  CG starts from zero; when the recurrence's
+    residual meets the tolerance the true residual is formed, and if that does not meet it the iteration goes on from the current
+    iterate with the true residual, inside the same max_iter.  When max_iter is reached the last iterate is installed, `converged` is
+    False and a warning is issued.  Every sum runs in a fixed order: two calls give the same bits.
+    prepare(onv, state_prob), matvec(v_flat) -> S v (all-reduced) and solve(rhs_flat) -> d_flat serve users with their own right-hand
+    side; flat vectors have the layout weights, hidden_bias, visible_bias (each as stored, (re, im) interleaved)."""
+
+    _who = "FusedRbmSR"
+
+    def __init__(self, nqs: nn.Module, sorb: int, diag_shift: float = 0.02, tol: float = 1e-6, max_iter: int = 1000, check_every: int = 8) -> None:
+        g = FusedRbmGrad(nqs, sorb)  # (refuses other modules)
+        self.flavour = g.flavour
+        self._setup(g, sorb, diag_shift, tol, max_iter, check_every)
+
+    def _workspace_bytes(self, n: int) -> int:
+        return self.N.lib().pynqs_rbm_sr_workspace(n, self.sorb, self.H, self.flavour)
+
+    def _native_prepare(self, n: int) -> None:
+        N = self.N
+        W, hb, _ = (p.detach().contiguous() for p in self.params)
+        N.check(N.lib().pynqs_rbm_sr_prepare(self._onv.data_ptr(), n, self.sorb, W.data_ptr(), hb.data_ptr(), self.H, self.flavour,
+                                             self._prob.data_ptr(), self.work.data_ptr(), self.obar.data_ptr(), self._stream()), "pynqs_rbm_sr_prepare")
+
+    def _native_matvec(self, v: Tensor, y: Tensor) -> None:
+        N = self.N
+        N.check(N.lib().pynqs_rbm_sr_matvec(self._onv.data_ptr(), self._onv.size(0), self.sorb, self.H, self.flavour, self._prob.data_ptr(),
+                                            self.work.data_ptr(), self.obar.data_ptr(), v.data_ptr(), y.data_ptr(), self._stream()),
+                "pynqs_rbm_sr_matvec")
+
+    def tanh_table(self) -> Tensor:
+        """tanh theta of the prepared walkers, [n, H] (complex128 for a ComplexRBM): a copy of the kernels' table, for tests"""
+        n, H = self._onv.size(0), self.H
+        if self.flavour == self.N.RBM_COMPLEX:
+            return torch.view_as_complex(self.work[:2 * n * H].view(H, n, 2)).t().contiguous()
+        return self.work[:n * H].view(H, n).t().contiguous()
+
+
+class FusedJastrowRbmSR(_FusedSR):
+    """SR direction for pynqs_amd.rbm.JastrowRBM, psi(x) = exp(a.x + x^T M x) prod_h 2cosh(theta_h), with float64 parameters on the GPU
+    (what FusedJastrowRbmGrad accepts; anything else, and a complex local energy: ValueError).  Calling convention, attributes and
+    methods of FusedRbmSR; the flat layout is weights, hidden_bias, visible_bias, jastrow [sorb, sorb], P = H sorb + H + sorb + sorb^2:
+
+        O_n = (tanh theta_nh x_no, tanh theta_nh, x_no, x_ni x_nj),
+        c_n = x_n.z_a + sum_h tanh theta_nh (z_b,h + sum_o z_W,ho x_no) + x_n^T Z x_n - Obar.z,      (S v)_k = sum_n p_n O_nk c_n,
+
+    Z the jastrow block of v (pynqs_jrbm_sr_matvec).  S does not depend on M; F is what FusedJastrowRbmGrad returns.  Three facts:
+      - S is singular on the jastrow block by construction.  O_ii = 1, so row and column ii of S vanish and d_ii = F_ii / diag_shift
+        (F_ii = 2 sum_n f_n: rounding-level when e_total is the weighted mean of eloc); O_ij = O_ji; and with fixed particle numbers
+        sum_j x_i x_j is proportional to x_i.  diag_shift regularises all of this and conjugate gradients from zero stay in the range
+        of S; diag_shift = 0 is accepted, as by FusedRbmSR, and then relies on that alone.
+      - The jastrow block is bit-symmetric: the product forms one sum for i <= j and writes it to (i, j) and (j, i), F_M from
+        pynqs_jastrow_grad has the property too, and the vector updates of conjugate gradients act entry by entry: after a call
+        jastrow.grad[i, j] == jastrow.grad[j, i] bit for bit.
+      - Only the symmetric part of Z reaches c_n (x^T Z x = tr Z + sum_{i<j} (Z_ij + Z_ji) x_i x_j, the form the kernel evaluates): an
+        antisymmetric Z with zero RBM blocks is in the null space of S."""
+
+    _who = "FusedJastrowRbmSR"
+
+    def __init__(self, nqs: nn.Module, sorb: int, diag_shift: float = 0.02, tol: float = 1e-6, max_iter: int = 1000, check_every: int = 8) -> None:
+        self._setup(FusedJastrowRbmGrad(nqs, sorb), sorb, diag_shift, tol, max_iter, check_every)  # (refuses other modules)
+
+    def _workspace_bytes(self, n: int) -> int:
+        return self.N.lib().pynqs_jrbm_sr_workspace(n, self.sorb, self.H)
+
+    def _native_prepare(self, n: int) -> None:
+        N = self.N
+        W, hb, _, _ = (p.detach().contiguous() for p in self.params)
+        N.check(N.lib().pynqs_jrbm_sr_prepare(self._onv.data_ptr(), n, self.sorb, W.data_ptr(), hb.data_ptr(), self.H, self._prob.data_ptr(),
+                                              self.work.data_ptr(), self.obar.data_ptr(), self._stream()), "pynqs_jrbm_sr_prepare")
+
+    def _native_matvec(self, v: Tensor, y: Tensor) -> None:
+        N = self.N
+        N.check(N.lib().pynqs_jrbm_sr_matvec(self._onv.data_ptr(), self._onv.size(0), self.sorb, self.H, self._prob.data_ptr(),
+                                             self.work.data_ptr(), self.obar.data_ptr(), v.data_ptr(), y.data_ptr(), self._stream()),
+                "pynqs_jrbm_sr_matvec")
+
+    def tanh_table(self) -> Tensor:
+        """tanh theta of the prepared walkers, [n, H]: a copy of the kernels' table, for tests"""
+        n, H = self._onv.size(0), self.H
+        return self.work[:n * H].view(H, n).t().contiguous()
