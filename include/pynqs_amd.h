@@ -319,6 +319,17 @@ int pynqs_green_rbm(const uint64_t *bra, int64_t nbatch, int sorb, int nele, int
                     uint8_t *clamped, void *stream);
 int pynqs_gfmc_sample_rank(const double *green, int64_t n, const double *rand_num, const uint64_t *bra, int sorb, int nele,
                            int noA, int noB, int64_t *index, double *beta, uint64_t *x_new, void *stream);
+/* The same row for a trial function that is a real RBM times a two-body Jastrow factor, psi(x) = exp(a.x + x^T M x) prod_h 2cosh(theta_h)
+ * (pynqs_eloc_jrbm's amplitude: rbm_table from pynqs_rbm_table_build, jastrow_table from pynqs_jastrow_table_build), in ONE kernel
+ * (kernels_rbm.hip, GREEN and JASTROW together).  Row layout, column order, v_sf, the clamping of green[0], clamped, eloc and psi (may be
+ * NULL; includes exp(tr M)) are those of pynqs_green_rbm with flavour PYNQS_RBM_REAL; pynqs_gfmc_sample_rank moves by such a row.
+ * Serves what pynqs_eloc_jrbm serves: PYNQS_EINVAL where pynqs_eloc_jrbm_supported is 0 (nothing is launched) or where jastrow_table,
+ * green or clamped is NULL.  The form is always "resident, one workgroup per walker" (the row finishes its diagonal in the kernel);
+ * the pair factors are read from the walker's triangle in LDS or from the table in L2 exactly where bit 2 of pynqs_eloc_jrbm_form says
+ * so (PYNQS_JRBM_PAIRS=lds / l2 honoured). */
+int pynqs_green_jrbm(const uint64_t *bra, int64_t nbatch, int sorb, int nele, int noA, int noB, const void *plan,
+                     const void *rbm_table, const void *jastrow_table, int nhidden, double lambda, double *eloc, double *psi,
+                     double *green, uint8_t *clamped, void *stream);
 
 /* ---- statistics: utils/stats/dist_stats.py:18-79 needs sum p O, sum p |O|^2 (and sum p) before its all-reduce -----
  *   pynqs_moments_workspace : [host] bytes of the workspace (device memory, ZERO it once before the first call)

@@ -34,7 +34,7 @@ USE_PLAN = True  # route get_comb_hij_fused through the cached integral plan (Fa
 
 __all__ = [
     "tensor_to_onv", "onv_to_tensor", "get_comb_tensor", "get_hij_torch", "get_comb_hij_fused",
-    "wavefunction_lut", "hash_build", "hash_lookup", "HashTable", "RBMTable", "eloc_rbm", "JastrowTable", "eloc_jrbm", "jrbm_forward", "eloc_jrbm_supported", "merge_rank_sample", "spin_flip_rand", "check_sorb", "compress_h1e_h2e", "decompress_h1e_h2e", "get_Num_SinglesDoubles",
+    "wavefunction_lut", "hash_build", "hash_lookup", "HashTable", "RBMTable", "eloc_rbm", "JastrowTable", "eloc_jrbm", "green_jrbm", "jrbm_forward", "eloc_jrbm_supported", "merge_rank_sample", "spin_flip_rand", "check_sorb", "compress_h1e_h2e", "decompress_h1e_h2e", "get_Num_SinglesDoubles",
     "MAX_SORB", "MAX_SORB_LEN", "MAX_NELE",
 ]
 
@@ -650,6 +650,34 @@ def eloc_jrbm(bra: Tensor, h1e: Tensor, h2e: Tensor, rbm_table: RBMTable, jastro
     return _eloc_fused(bra, h1e, h2e, rbm_table, sorb, want_psi, torch.float64, lambda x, n, plan, eloc, psi, st: N.check(
         N.lib().pynqs_eloc_jrbm(x.data_ptr(), n, sorb, nele, noA, noB, plan.data_ptr(), rbm_table.data_ptr(), jastrow_table.data_ptr(),
                                 rbm_table.nhidden, eloc.data_ptr(), psi, st), "pynqs_eloc_jrbm"))
+
+
+def green_jrbm(bra: Tensor, h1e: Tensor, h2e: Tensor, rbm_table: RBMTable, jastrow_table: JastrowTable, sorb: int, nele: int, noA: int, noB: int,
+               Lambda: float, want_psi: bool = False) -> Tuple[Tensor, Tensor, Tensor, "Tensor | None"]:
+    """The fixed-node Green's row of every walker for the trial function of eloc_jrbm, one kernel (pynqs_green_jrbm):
+    (eloc float64[n], green float64[n, ncomb] in the reference's column order, clamped uint8[n], psi(x) float64[n] or None).
+    Walkers, integrals and tables on one GPU; float64."""
+    _check_onv(bra, "bra", sorb, (2,))
+    if jastrow_table.sorb != sorb or rbm_table.sorb != sorb or jastrow_table.device != rbm_table.device:
+        raise RuntimeError(f"Jastrow table: sorb = {jastrow_table.sorb} on {jastrow_table.device}, RBM table: sorb = {rbm_table.sorb} on {rbm_table.device}")
+    if _fdtype(h1e, h2e) != N.PYNQS_F64:
+        raise RuntimeError("the fused Green's row is float64 only")
+    plan = plan_for(h1e, h2e, sorb, bra.device)
+    if plan is None:
+        raise RuntimeError("the fused Green's row needs an even sorb")
+    dev = bra.device
+    if dev.type != "cuda" or plan.device != dev or rbm_table.device != dev:
+        raise RuntimeError("bra, integrals and tables must be on the same GPU")
+    n = bra.size(0)
+    eloc = torch.empty(n, dtype=torch.float64, device=dev)
+    gk = torch.empty((n, get_Num_SinglesDoubles(sorb, noA, noB) + 1), dtype=torch.float64, device=dev)
+    neg = torch.empty(n, dtype=torch.uint8, device=dev)
+    psi = torch.empty(n, dtype=torch.float64, device=dev) if want_psi else None
+    if n:
+        N.check(N.lib().pynqs_green_jrbm(bra.data_ptr(), n, sorb, nele, noA, noB, plan.data_ptr(), rbm_table.data_ptr(), jastrow_table.data_ptr(),
+                                         rbm_table.nhidden, float(Lambda), eloc.data_ptr(), psi.data_ptr() if want_psi else None, gk.data_ptr(),
+                                         neg.data_ptr(), _stream(dev)), "pynqs_green_jrbm")
+    return eloc, gk, neg, psi
 
 
 def jrbm_forward(onv: Tensor, weights: Tensor, hidden_bias: Tensor, visible_bias: "Tensor | None", jastrow: Tensor, sorb: int) -> Tensor:

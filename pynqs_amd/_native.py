@@ -125,6 +125,7 @@ SIGNATURES.update({
     "pynqs_eloc_jrbm_supported": (_int, [_int, _int, _int, _int, _int]),
     "pynqs_eloc_jrbm_form": (_int, [_i64, _int, _int, _int, _int, _int]),
     "pynqs_eloc_jrbm": (_int, [_vp, _i64, _int, _int, _int, _int, _vp, _vp, _vp, _int, _vp, _vp, _vp]),
+    "pynqs_green_jrbm": (_int, [_vp, _i64, _int, _int, _int, _int, _vp, _vp, _vp, _int, _dbl, _vp, _vp, _vp, _vp, _vp]),
     "pynqs_jrbm_forward": (_int, [_vp, _i64, _int, _vp, _vp, _vp, _vp, _int, _vp, _vp]),
     "pynqs_jastrow_grad_workspace": (_i64, [_i64, _int]),
     "pynqs_mcmc_jrbm_supported": (_int, [_int, _int]),

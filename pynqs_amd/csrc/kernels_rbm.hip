@@ -47,8 +47,14 @@
 //   from a per-walker triangle P[i > j] = exp(4 S_ij x_i x_j) in LDS behind the trailer (4 sorb (sorb - 1) bytes, built from the table
 //   next to C(o); `lambda` != 0) where three workgroups still fit a CU with it, else from the table itself (L2-resident, 16 sorb^2
 //   bytes).  Fe2S2, 8192 walkers: 0.97-1.13 ms from LDS, 1.00-1.17 ms from L2, pynqs_eloc_rbm 0.77 ms in the same run.
-// tr M scales psi(x) only.  Every statement of it stands under `if constexpr (JASTROW)`; the table comes in the slot of `green`, which
-// this form does not use, so that the kernel's arguments -- and the other instantiations -- are what they were.
+// tr M scales psi(x) only.  Every statement of it stands under `if constexpr (JASTROW)`; without GREEN the table comes in the slot of
+// `green`, which that form does not use, and `lambda` != 0 says that the pair factors are in LDS.
+//
+// GREEN and JASTROW together (pynqs_green_jrbm): the pair factors join the running products in the tile epilogue BEFORE add_column, so
+// the row, v_sf and the diagonal see the full ratio.  `green`, `lambda` and `clamped` keep their meaning; the table comes in the trailing
+// argument `jastrow` (nullptr in every other form) and the LDS flag in bit 1 of the chunk count, which is 1 in this form by construction
+// (one workgroup per walker: the row finishes its diagonal in the kernel).  The other instantiations' registers are what they were
+// (DESIGN 4.8).
 #include <string.h>
 
 #include "rbm.h"
@@ -112,12 +118,25 @@ enum : int { kRbmReal = 0, kRbmTanh = 1, kRbmPhase = 2 };
 
 template <int LEN, bool WINDOWED, int FLAVOUR, bool GREEN, bool JASTROW = false>
 __global__ __launch_bounds__(1024, 4) void eloc_rbm_kernel(const uint64_t *__restrict__ bra, SDParams p, PlanLayout pl, RbmLayout rl,
-                                                          RbmBlocks<kRbmFB> B, uint32_t nchunks, uint32_t hw, const double *__restrict__ plan,
+                                                          RbmBlocks<kRbmFB> B, uint32_t nchunks_arg, uint32_t hw, const double *__restrict__ plan,
                                                           const double *__restrict__ rbm, double *__restrict__ eloc,
                                                           double *__restrict__ psi, double lambda, double *__restrict__ green,
-                                                          uint8_t *__restrict__ clamped) {
+                                                          uint8_t *__restrict__ clamped, const double *__restrict__ jastrow) {
   static_assert(!GREEN || FLAVOUR != kRbmPhase, "the fixed-node row needs a real-valued amplitude");
-  static_assert(!JASTROW || (FLAVOUR == kRbmReal && !GREEN && !WINDOWED), "the Jastrow factor: real flavour, resident form, no Green's row");
+  static_assert(!JASTROW || (FLAVOUR == kRbmReal && !WINDOWED), "the Jastrow factor: real flavour, resident form");
+  // GREEN and JASTROW together (pynqs_green_jrbm): `green`, `lambda` and `clamped` are the row's, so the Jastrow table comes in `jastrow`
+  // and the "pair factors in LDS" flag in bit 1 of `nchunks_arg` -- the row is launched with one workgroup per walker, so the chunk
+  // count is the constant 1 in that form.  Every other instantiation reads what it read before.
+  constexpr bool kGreenJastrow = GREEN && JASTROW;
+  const uint32_t nchunks = kGreenJastrow ? 1u : nchunks_arg;
+  [[maybe_unused]] auto jas_table = [&]() -> const double * {
+    if constexpr (kGreenJastrow) return jastrow;
+    else return green;
+  };
+  [[maybe_unused]] auto jas_pairs_in_lds = [&]() -> bool {
+    if constexpr (kGreenJastrow) return (nchunks_arg & 2u) != 0u;
+    else return lambda != 0.0;
+  };
   // no static __shared__ here: with the dynamic region at LDS address 0 the row offsets below are the addresses and
   // the ds_read immediates carry the rest (a static in front costs one v_add per read)
   extern __shared__ __attribute__((aligned(16))) unsigned char smem[];
@@ -277,7 +296,7 @@ __global__ __launch_bounds__(1024, 4) void eloc_rbm_kernel(const uint64_t *__res
         da = exp(-4.0 * x * a);
       } else if constexpr (JASTROW) {
         // r_o = sum_j S_jo x_j (S is symmetric: column o, so that consecutive lanes read consecutive words; S_oo = 0), 16 loads in flight
-        const double *__restrict__ S = green;
+        const double *__restrict__ S = jas_table();
         double r = 0.0;
 #pragma unroll 16
         for (int j = 0; j < sorb; ++j) {
@@ -296,17 +315,17 @@ __global__ __launch_bounds__(1024, 4) void eloc_rbm_kernel(const uint64_t *__res
     if constexpr (FLAVOUR == kRbmTanh) R.Aq[o] = da;
   }
   if constexpr (JASTROW) {
-    // the walker's pair factors in LDS (lambda != 0), behind the kernel's own layout (where they are is worked out again at each use:
+    // the walker's pair factors in LDS (jas_pairs_in_lds), behind the kernel's own layout (where they are is worked out again at each use:
     // nothing of it lives across the hidden-unit loop)
     // (one and two words only: at three the triangle is 66 KiB and more and never chosen, and the branch alone costs that
     // instantiation a spill inside the hidden-unit loop)
     double *jP = reinterpret_cast<double *>(smem + lds_bytes_rbm(p, rl, hw));
-    if (LEN < 3 && lambda != 0.0) {  // P[a (a - 1) / 2 + b] = exp(4 S_ab x_a x_b), b < a: a wave per row, consecutive lanes read consecutive words
+    if (LEN < 3 && jas_pairs_in_lds()) {  // P[a (a - 1) / 2 + b] = exp(4 S_ab x_a x_b), b < a: a wave per row, consecutive lanes read consecutive words
       const uint32_t n2 = (uint32_t)jastrow_pairs(sorb);
       for (int a = 1 + wave; a < sorb; a += nwaves) {
         const uint32_t xa = bit_of<LEN>(wk.w, a);
         for (int b = lane; b < a; b += 64)
-          jP[(uint32_t)(a * (a - 1) / 2 + b)] = green[(bit_of<LEN>(wk.w, b) == xa ? n2 : 2u * n2) + (uint32_t)a * (uint32_t)sorb + (uint32_t)b];
+          jP[(uint32_t)(a * (a - 1) / 2 + b)] = jas_table()[(bit_of<LEN>(wk.w, b) == xa ? n2 : 2u * n2) + (uint32_t)a * (uint32_t)sorb + (uint32_t)b];
       }
     }
   }
@@ -486,7 +505,7 @@ __global__ __launch_bounds__(1024, 4) void eloc_rbm_kernel(const uint64_t *__res
             }
           }
         };
-        if (LEN < 3 && lambda != 0.0) {  // (workgroup-uniform)
+        if (LEN < 3 && jas_pairs_in_lds()) {  // (workgroup-uniform)
           const double *jP = reinterpret_cast<const double *>(smem + lds_bytes_rbm(p, rl, hw));
           join_pairs([&](uint32_t a, uint32_t b, int, int) {
             const uint32_t hi = max(a, b), lo = min(a, b);
@@ -501,7 +520,7 @@ __global__ __launch_bounds__(1024, 4) void eloc_rbm_kernel(const uint64_t *__res
           }
           const uint32_t n2 = (uint32_t)jastrow_pairs(sorb);
           join_pairs([&](uint32_t a, uint32_t b, int ka, int kb) {
-            return green[((((occ >> ka) ^ (occ >> kb)) & 1u) ? 2u * n2 : n2) + a * (uint32_t)sorb + b];
+            return jas_table()[((((occ >> ka) ^ (occ >> kb)) & 1u) ? 2u * n2 : n2) + a * (uint32_t)sorb + b];
           });
         }
       }
@@ -598,7 +617,7 @@ __global__ __launch_bounds__(1024, 4) void eloc_rbm_kernel(const uint64_t *__res
     if constexpr (JASTROW) {  // x^T M x = tr M + sum_{i<j} S_ij x_i x_j, the sum apart from lnpsi: at most sorb - 1 of its additions round
 #pragma unroll
       for (int o = 32; o > 0; o >>= 1) xsx += __shfl_xor(xsx, o);
-      xmx = rbm_over_waves(xsx, T.red, tid, nwaves) + green[3 * jastrow_pairs(sorb)];
+      xmx = rbm_over_waves(xsx, T.red, tid, nwaves) + jas_table()[3 * jastrow_pairs(sorb)];
     }
     if (tid == 0) {
       if constexpr (JASTROW) psi[walker] = exp(s + xmx);
@@ -721,7 +740,7 @@ static int eloc_rbm_impl(const uint64_t *bra, int64_t nbatch, int sorb, int nele
   int rc = PYNQS_OK;
 #define PYNQS_RBM_LAUNCH(W, F, G)                                                                                                            \
   rc = rbm_launch("eloc_rbm", eloc_rbm_kernel<LEN, W, F, G>, grid, threads, lds, st, bra, p, pl, rl, B, nchunks, hw, (const double *)plan, \
-                  (const double *)rbm_table, eloc, psi, lambda, green, clamped)
+                  (const double *)rbm_table, eloc, psi, lambda, green, clamped, (const double *)nullptr)
 #define PYNQS_RBM_FLAVOURS(W)                                                \
   do {                                                                       \
     if (green && flavour == PYNQS_RBM_REAL) PYNQS_RBM_LAUNCH(W, kRbmReal, true);  \
@@ -809,8 +828,40 @@ extern "C" int pynqs_eloc_jrbm(const uint64_t *bra, int64_t nbatch, int sorb, in
   int rc = PYNQS_OK;
 #define PYNQS_JRBM_LAUNCH                                                                                                                  \
   rc = rbm_launch("eloc_jrbm", eloc_rbm_kernel<LEN, false, kRbmReal, false, true>, grid, threads, lds, st, bra, p, pl, rl, B, nchunks, hw, \
-                  (const double *)plan, (const double *)rbm_table, eloc, psi, pairs_in_lds ? 1.0 : 0.0, jas, (uint8_t *)nullptr)
+                  (const double *)plan, (const double *)rbm_table, eloc, psi, pairs_in_lds ? 1.0 : 0.0, jas, (uint8_t *)nullptr, (const double *)nullptr)
   DISPATCH_LEN(len, { PYNQS_JRBM_LAUNCH; });
 #undef PYNQS_JRBM_LAUNCH
+  return rc;
+}
+
+// ---- the fixed-node Green's row with the Jastrow factor (GREEN and JASTROW): pynqs_green_rbm's row for pynqs_eloc_jrbm's amplitude.
+// Resident form, one workgroup per walker; the LDS is the kernel's own layout plus, where jrbm_pairs_in_lds says so, the walker's triangle.
+extern "C" int pynqs_green_jrbm(const uint64_t *bra, int64_t nbatch, int sorb, int nele, int noA, int noB, const void *plan,
+                                const void *rbm_table, const void *jastrow_table, int nhidden, double lambda, double *eloc, double *psi,
+                                double *green, uint8_t *clamped, void *stream) {
+  pynqs::DeviceScope device_scope_(bra);
+  if (!jastrow_table || !green || !clamped) return set_error(PYNQS_EINVAL, "null pointer");
+  RbmSystem<RbmLayout> sys;
+  if (const char *bad = rbm_system(sorb, nele, noA, noB, nhidden, make_rbm_layout, &sys)) return set_error(PYNQS_EINVAL, bad);
+  if (const int rc = rbm_batch(nbatch, 0x7fffffffll, bra, plan, rbm_table, eloc)) return rc;
+  if (!jrbm_resident(sys)) return set_error(PYNQS_EINVAL, "green_jrbm: sorb x nhidden beyond the LDS (pynqs_eloc_jrbm_supported)");
+  if (nbatch == 0) return PYNQS_OK;
+  const auto &[p, pl, rl] = sys;
+  const RbmBlocks<kRbmFB> B = make_rbm_blocks<kRbmFB>(p);
+  const uint32_t hw = (uint32_t)rl.Hloop;
+  const bool pairs_in_lds = jrbm_pairs_in_lds(sys);
+  const size_t lds = lds_bytes_rbm(p, rl, hw) + (pairs_in_lds ? jrbm_pairs_bytes(p) : 0);
+  hipStream_t st = (hipStream_t)stream;
+  uint32_t grid;
+  if (const int rc = rbm_grid(nbatch, 1u, eloc, 8, st, &grid)) return rc;
+  const int len = (sorb - 1) / 64 + 1;
+  const uint32_t threads = rbm_resident_threads(lds, B.ntiles, 1024, rbm_block_env());
+  const uint32_t chunks_and_flag = 1u | (pairs_in_lds ? 2u : 0u);  // (eloc_rbm_kernel: bit 1 = pair factors in LDS; the chunk count is 1)
+  int rc = PYNQS_OK;
+#define PYNQS_GJRBM_LAUNCH                                                                                                                      \
+  rc = rbm_launch("green_jrbm", eloc_rbm_kernel<LEN, false, kRbmReal, true, true>, grid, threads, lds, st, bra, p, pl, rl, B, chunks_and_flag, \
+                  hw, (const double *)plan, (const double *)rbm_table, eloc, psi, lambda, green, clamped, (const double *)jastrow_table)
+  DISPATCH_LEN(len, { PYNQS_GJRBM_LAUNCH; });
+#undef PYNQS_GJRBM_LAUNCH
   return rc;
 }

@@ -17,10 +17,11 @@ from . import C_extension as CX
 from . import _native as N
 from .C_extension import get_comb_hij_fused
 from .distributed import all_gather_varlen, get_rank, get_world_size
-from .energy import Func, _rbm_lds_ok, _real_rbm_params
+from .energy import Func, _jastrow_rbm_params, _rbm_lds_ok, _real_rbm_params
 from .public_function import WavefunctionLUT, get_Num_SinglesDoubles
 
-FUSED_GREEN = True  # trial function = RBM with real parameters ("real" / "tanh"): the whole row in one kernel (pynqs_green_rbm)
+# trial function = RBM with real parameters ("real" / "tanh"), or a JastrowRBM: the whole row in one kernel (pynqs_green_rbm / pynqs_green_jrbm)
+FUSED_GREEN = True
 
 
 class CombRows:
@@ -45,8 +46,10 @@ def green_kernel(x: Tensor, Lambda: float, h1e: Tensor, h2e: Tensor, ansatz, ans
         assert x.dim() == 2
         batch = x.shape[0]
         device = h1e.device
-        prm = _real_rbm_params(ansatz) if (FUSED_GREEN and WF_LUT is None and dtype == torch.double and x.is_cuda and sorb % 2 == 0
-                                           and h1e.dtype in (torch.float64, torch.float32)) else None
+        fused = (FUSED_GREEN and WF_LUT is None and dtype == torch.double and x.is_cuda and sorb % 2 == 0
+                 and h1e.dtype in (torch.float64, torch.float32))
+        prm = _real_rbm_params(ansatz) if fused else None
+        jprm = _jastrow_rbm_params(ansatz) if fused and prm is None else None
         if prm is not None and prm[3] in ("real", "tanh") and _rbm_lds_ok(sorb, nele, noa, nob, prm[0].size(0)):
             # enumeration, matrix elements, amplitude ratios, fixed-node construction and E_loc in one kernel
             plan = CX.plan_for(*CX.integrals_f64(h1e, h2e), sorb, x.device)
@@ -61,6 +64,12 @@ def green_kernel(x: Tensor, Lambda: float, h1e: Tensor, h2e: Tensor, ansatz, ans
                                                 CX.RBM_FLAVOURS[prm[3]], float(Lambda), eloc.data_ptr(), None, gk.data_ptr(), neg.data_ptr(),
                                                 torch.cuda.current_stream(x.device).cuda_stream), "pynqs_green_rbm")
             return eloc, gk, rows, False, neg.bool()
+        if jprm is not None and CX.eloc_jrbm_supported(sorb, nele, noa, nob, jprm[0].size(0)):
+            # the same with the two-body Jastrow factor on the real RBM (pynqs_green_jrbm)
+            xc = x.contiguous()
+            eloc, gk, neg, _ = CX.green_jrbm(xc, *CX.integrals_f64(h1e, h2e), CX.RBMTable(*jprm[:3]), CX.JastrowTable(jprm[3]), sorb, nele, noa, nob,
+                                             float(Lambda))
+            return eloc, gk, CombRows(xc, sorb, nele, noa, nob), False, neg.bool()
         f = partial(ansatz_batch, func=ansatz)
         comb_x, comb_hij = get_comb_hij_fused(x, h1e, h2e, sorb, nele, noa, nob)
         bra_len = comb_x.shape[2]
