@@ -487,6 +487,39 @@ int pynqs_reduce_onepass(const uint64_t *bra, int64_t nbatch, int sorb, int nele
 int pynqs_reduce_contract(int64_t nbatch, int sorb, int nele, int noA, int noB, int dtype, int eps_sample,
                           const pynqs_reduce_io *io, const double *psi_unique, const double *psi_table, int psi_is_complex,
                           int divide, double *eloc, double *psi_x, void *stream);
+/* ---- the draw law of the short-row form (pynqs_reduce_onepass where pynqs_reduce_onepass_wants_row_f32 says 1 and io->row_f32 is given:
+ * rows of at most 8192 columns, at most 16383 draws, the kept records within the list; pynqs_amd/csrc/reduce_draw.h).  This form's random
+ * STREAM is part of the contract: which columns walker i draws, and how often, is a pure function of (seed, *io->seed_dev, i, the row).
+ * tests/reduce_replay.py replays it on the host; tests/test_gpu_reduce_replay.py compares every record.
+ *  - Hash: mix64 = the splitmix64 finaliser (pynqs_amd/csrc/mix64.h), all arithmetic modulo 2^64.
+ *  - Key of walker i (its index in the call, from 0):  key = mix64((seed + seed_dev) ^ mix64(i)),  seed_dev = *io->seed_dev as the launch
+ *    reads it from device memory (0 when io->seed_dev is NULL).  A caller that replays the launch from a HIP graph bumps that word between
+ *    replays (reduce_front.ReduceStep: +1 per replay, inside the graph), so that replay m draws with seed + seed_dev_m.
+ *  - Draw k = 0 .. N - 1 (N = eps_sample) of the walker:  r_k = mix64(key ^ ((k + 1) * 0x9e3779b97f4a7c15)),  u_k = (r_k >> 11) * 2^-53 in
+ *    [0, 1): a 53-bit uniform, exact in double.
+ *  - Widths, in the reference's column order (column 0 the diagonal, then get_comb_tensor's singles and doubles): w32_j = float32(|H_j|),
+ *    round to nearest, for the sub-eps columns -- |H_j| < eps compared in the integral dtype; with eps <= 0 nothing is kept and every
+ *    column is sub-eps -- and 0 for the kept ones.  With float32 integrals the widths are the elements' magnitudes themselves.
+ *    C_j = w32_0 + ... + w32_j,  S' = C_last.  A float64 element below the float32 range has width 0 and is never drawn.
+ *  - Boundary rule: draw k chooses the column j with  C_{j-1} <= u_k S' < C_j  (C_{-1} = 0): the first column whose running sum exceeds
+ *    the target.  A column of width zero (kept, or an exact zero) is never chosen.  P(column j) = w32_j / S', which is the reference's
+ *    |H_j| / S (torch.multinomial(prob, N, replacement=True), vmc/energy/eloc.py:263-296) to 6e-8 relative.
+ *  - Rounding: the kernel forms S', the starting sum of a segment of 16 columns and the running sum inside the segment in float64, each a
+ *    sum of at most ncomb non-negative terms in a fixed order, so its choice is the rule's whenever the target is farther than
+ *    2^-51 (ncomb + 64) S' from both ends of the column's interval; nearer than that it may be the neighbouring column of positive width,
+ *    nothing else.  Fallbacks when rounding takes the target past the last positive width of its segment: that last column; when the
+ *    segment has no width at all: the nearest column of positive width after it, else before it.  A row without any width (S' = 0) draws
+ *    nothing and leaves all N slots at -1; its kept records and row_sum = 0 are written as usual.
+ *  - Records: one per distinct drawn column, in the first slots of the walker's N, ascending columns (the reference's
+ *    unique(sorted=True)); a column drawn c times carries  (c / N) sign(H_j) S  in the integral dtype,  S = io->row_sum = the float64 sum of
+ *    the exact sub-eps |H_j| (within ncomb 2^-52 relative of the exact sum; the weight within (ncomb + 2) 2^-52 relative).
+ *  - Limits: ncomb <= 8192 columns and N <= 16383 draws (a record waits as count << 16 | sign << 15 | column); beyond either the call
+ *    takes one of the forms below.
+ * The other semi-stochastic forms -- the flushing and look-back forms of this entry point (wants_row_f32 = 2 or 0), the LIST form with
+ * io->row_cache or io->tile_scratch, and the multi-pass pynqs_reduce_count_sums / pynqs_reduce_sample -- draw HIERARCHICALLY: first the tile
+ * (in proportion to the tiles' sums of sub-eps |H|), then the column inside the tile in the tile's enumeration order, with streams keyed by (seed, walker
+ * or slot, tile, k).  Only their LAW is contractual -- P(column j) = |H_j| / S, N draws per walker with replacement, the same records and
+ * weights --, not their stream: it may change with the tiling. */
 
 /* ---- the RBM amplitudes themselves on a LIST of determinants (kernels_rbm_forward.hip): psi(x) of vmc/ansatz/rbm/rbm.py:186-211 from the
  * packed bits, one lane per determinant, nothing but the result written.  The amplitude forward of the REDUCE local energy (`Func` on the
