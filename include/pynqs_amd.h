@@ -753,13 +753,27 @@ int pynqs_mcmc_accept(uint64_t *states, double *psi, const uint64_t *proposals, 
  *        (kernels_rdm.hip); the lane constant is exp(+-2 sum_o (sum_h W_ho - a_o)) over the two orbitals of the lane side, which must
  *        stay a finite double (|sum_h W_ho| below ~170 per orbital).
  *   pynqs_rdm_rbm_supported : 1 if the fused kernel serves (sorb even, (sorb / 2)^2 <= 2048, nhidden <= 512, its tables within 64 KiB of
- *        LDS), else 0: callers then use pynqs_rdm_scatter.                                                                              */
+ *        LDS), else 0: callers then use pynqs_rdm_scatter.
+ *   pynqs_rdm_jrbm : Jastrow-RBM, psi(x) = exp(a.x + x^T M x) prod_h 2 cosh theta_h: pynqs_rdm_rbm's kernel in its Jastrow flavour, with
+ *        pynqs_rdm_rbm's conventions (OVERWRITES, nbatch = 0 gives zeros, walkers with other electron counts are skipped, fixed order:
+ *        two calls give the same bits).  rbm_table from pynqs_rbm_table_build, jastrow_table from pynqs_jastrow_table_build; workspace:
+ *        pynqs_rdm_jrbm_workspace bytes = pynqs_rdm_rbm_workspace's + r [nbatch][sorb] doubles, r_o = sum_j S_oj x_j (S = M + M^T, zero
+ *        diagonal).  The ratio gains exp(-2 sum_{i in F} x_i r_i + 4 sum_{i<j in F} S_ij x_i x_j) over the flipped orbitals F: the pair
+ *        terms are constants of a workgroup and join the exponents that exist, exp(-+2 r_o) per orbital is staged once per walker; it
+ *        must stay a finite double (2 sum_j |S_oj| below ~700).  tr M and the diagonal of M do not enter.  With M = 0 the result has the
+ *        bits of pynqs_rdm_rbm.
+ *   pynqs_rdm_jrbm_supported : pynqs_rdm_rbm_supported with 16 sorb more bytes of LDS.
+ *   PYNQS_EINVAL, nothing launched, where _supported answers 0 or a pointer is null.                                                    */
 int pynqs_rdm_scatter(const uint64_t *bra, int64_t nbatch, int sorb, int nele, int noA, int noB, const double *w, const double *ratio,
                       int is_complex, double *rdm1, double *rdm2, void *stream);
 int pynqs_rdm_rbm_supported(int sorb, int nele, int noA, int noB, int nhidden);
 int64_t pynqs_rdm_rbm_workspace(int64_t nbatch, int sorb, int nhidden);
 int pynqs_rdm_rbm(const uint64_t *bra, int64_t nbatch, int sorb, int nele, int noA, int noB, const double *w, const void *rbm_table,
                   int nhidden, void *workspace, double *rdm1, double *rdm2, void *stream);
+int pynqs_rdm_jrbm_supported(int sorb, int nele, int noA, int noB, int nhidden);
+int64_t pynqs_rdm_jrbm_workspace(int64_t nbatch, int sorb, int nhidden);
+int pynqs_rdm_jrbm(const uint64_t *bra, int64_t nbatch, int sorb, int nele, int noA, int noB, const double *w, const void *rbm_table,
+                   const void *jastrow_table, int nhidden, void *workspace, double *rdm1, double *rdm2, void *stream);
 
 #ifdef __cplusplus
 }

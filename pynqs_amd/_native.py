@@ -120,6 +120,9 @@ SIGNATURES.update({
     "pynqs_rdm_rbm_supported": (_int, [_int, _int, _int, _int, _int]),
     "pynqs_rdm_rbm_workspace": (_i64, [_i64, _int, _int]),
     "pynqs_rdm_rbm": (_int, [_vp, _i64, _int, _int, _int, _int, _vp, _vp, _int, _vp, _vp, _vp, _vp]),
+    "pynqs_rdm_jrbm_supported": (_int, [_int, _int, _int, _int, _int]),
+    "pynqs_rdm_jrbm_workspace": (_i64, [_i64, _int, _int]),
+    "pynqs_rdm_jrbm": (_int, [_vp, _i64, _int, _int, _int, _int, _vp, _vp, _vp, _int, _vp, _vp, _vp, _vp]),
     "pynqs_jastrow_table_bytes": (_i64, [_int]),
     "pynqs_jastrow_table_build": (_int, [_vp, _int, _vp, _vp]),
     "pynqs_eloc_jrbm_supported": (_int, [_int, _int, _int, _int, _int]),

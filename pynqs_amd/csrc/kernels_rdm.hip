@@ -19,6 +19,14 @@
 //       the results go to directed tables [particle side][hole side] in the workspace, and a last kernel forms every packed slot from
 //       them (slot (ij, kl) = table[ij][kl] + table[kl][ij]): no float atomics, every sum in a fixed order, two calls give the same bits.
 //       The singles' spectator terms (rdm2[(h,k),(q,k)] for every occupied k) are added by the item that owns (h, q) into its own LDS row.
+//   pynqs_rdm_jrbm    : Jastrow-RBM, the same kernel (JASTROW).  With S = M + M^T (zero diagonal, the Jastrow table) and r_o = sum_j S_oj x_j
+//       the ratio gains exp(Delta), Delta = -2 sum_{i in F} x_i r_i + 4 sum_{i<j in F} S_ij x_i x_j over the flipped orbitals F.  In a
+//       qualifying walker every owner orbital has x = xo and every live item orbital x = xl = -xo, so every pair term is a constant of
+//       the workgroup: + 4 S_o0o1 joins the owner's visible term, 4 S_l0l1 - 4 (S_o0l0 + S_o0l1 + S_o1l0 + S_o1l1) (singles: - 4 S_ol) the
+//       exponent of the lane constant.  Per walker -2 xo (r_o0 + r_o1) joins the owner's exponent and e_o = exp(-2 xl r_o) is staged for
+//       every orbital next to a_h, b_h (published by the same barrier); an item multiplies by e_l0 e_l1.  r [n][sorb] comes from
+//       rdm_r_kernel (one fma chain per walker and orbital) in the workspace.  M = 0: every added term is +-0 and every added factor 1,
+//       the bits of pynqs_rdm_rbm.
 #include "detcore.h"
 #include "launch.h"
 #include "rbm.h"
@@ -99,6 +107,7 @@ __global__ __launch_bounds__(kBlock) void rdm_scatter_kernel(const uint64_t *__r
 // its time on -- without slices Fe2S2 x 8192 walkers has 780 + 40 such chains of 500 to 2000 walkers.  Every slice has tables of its
 // own; the last kernel adds them in slice order.
 // workspace (doubles): theta [n][H] | Dg [nslS][sorb][sorb] | T [nslS][sorb][sorb][sorb + 1] | Daa, Dbb [nslD][npS][npS] | Dab [nslD][K K][K K]
+// (pynqs_rdm_jrbm: | r [n][sorb] behind them, RdmJastrow::offR)
 struct RdmLayout {
   int sorb, K, H, Hq, npS, owner_empty, noA, noB;
   int nslD, nslS;      // slices of the pair kernel / of the singles and diagonal kernels
@@ -143,10 +152,18 @@ static inline bool make_rdm_layout(int64_t n, int sorb, int noA, int noB, int H,
   return true;
 }
 
-__host__ __device__ inline size_t rdm_lds_bytes(const RdmLayout &r, bool singles) {
+__host__ __device__ inline size_t rdm_lds_bytes(const RdmLayout &r, bool singles, bool jastrow = false) {
   // G [sorb][Hq] | ab [2 buffers][2][H] | red [2 buffers][kBlock / 64] | cs [sorb] | (singles) Ts [K][sorb] | list [kBlock] u32 | wcnt [kBlock / 64] u32
-  return 8 * ((size_t)r.sorb * r.Hq + 4 * (size_t)r.H + 2 * (kBlock / 64) + r.sorb + (singles ? (size_t)r.K * r.sorb : 0)) + 4 * (kBlock + kBlock / 64);
+  // | (jastrow) ev [2 buffers][sorb]
+  return 8 * ((size_t)r.sorb * r.Hq + 4 * (size_t)r.H + 2 * (kBlock / 64) + r.sorb + (singles ? (size_t)r.K * r.sorb : 0)) + 4 * (kBlock + kBlock / 64) +
+         (jastrow ? 16 * (size_t)r.sorb : 0);
 }
+
+// what the JASTROW flavour of rdm_rbm_kernel reads beside the RBM table: the Jastrow table (rbm.h) and where r [n][sorb] lies in the workspace
+struct RdmJastrow {
+  const double *tab;
+  int64_t offS, offR;  // doubles: S in the table, r in the workspace
+};
 
 // theta[i][h] = b_h + sum_o W_ho x_o: one fma chain over the orbitals in ascending order
 template <int LEN>
@@ -162,6 +179,22 @@ __global__ __launch_bounds__(kBlock) void rdm_theta_kernel(const uint64_t *__res
   double th = rbm[offHb + h];
   for (int o = 0; o < r.sorb; ++o) th = fma(bit_of<LEN>(x, o) ? 1.0 : -1.0, rbm[r.offWt + (int64_t)o * r.Hq + h], th);
   ws[r.offTheta + g] = th;
+}
+
+// r[i][o] = sum_j S_oj x_j: one fma chain over the orbitals in ascending order from 0 (S_oo = 0)
+template <int LEN>
+__global__ __launch_bounds__(kBlock) void rdm_r_kernel(const uint64_t *__restrict__ bra, int64_t n, int sorb, RdmJastrow jz, double *__restrict__ ws) {
+  const int64_t g = (int64_t)blockIdx.x * kBlock + threadIdx.x;
+  if (g >= n * sorb) return;
+  const int64_t i = g / sorb;
+  const int o = (int)(g - i * sorb);
+  uint64_t x[LEN];
+#pragma unroll
+  for (int k = 0; k < LEN; ++k) x[k] = bra[i * LEN + k];
+  const double *__restrict__ row = jz.tab + jz.offS + (int64_t)o * sorb;
+  double acc = 0.0;
+  for (int j = 0; j < sorb; ++j) acc = fma(bit_of<LEN>(x, j) ? 1.0 : -1.0, row[j], acc);
+  ws[jz.offR + g] = acc;
 }
 
 // Dg[slice][p][q] = sum_x w_x n_p(x) n_q(x), the slice's walkers in order: one workgroup per (p, slice), one thread per q
@@ -197,10 +230,11 @@ __device__ __forceinline__ void rdm_make_walker(const uint64_t (&x)[LEN], Walker
   }
 }
 
-// class 0 / 1: alpha-alpha / beta-beta pairs, 2: alpha-beta pairs (block = owner pair); SINGLES: block = owner orbital
-template <int LEN, bool SINGLES>
+// class 0 / 1: alpha-alpha / beta-beta pairs, 2: alpha-beta pairs (block = owner pair); SINGLES: block = owner orbital; JASTROW: the
+// Jastrow-RBM (jz is not read otherwise)
+template <int LEN, bool SINGLES, bool JASTROW>
 __global__ __launch_bounds__(kBlock) void rdm_rbm_kernel(const uint64_t *__restrict__ bra, int64_t n, const double *__restrict__ w,
-                                                         RdmLayout r, const double *__restrict__ rbm, double *__restrict__ ws) {
+                                                         RdmLayout r, const double *__restrict__ rbm, double *__restrict__ ws, RdmJastrow jz) {
   extern __shared__ __attribute__((aligned(16))) unsigned char smem[];
   double *G = reinterpret_cast<double *>(smem);
   double *ab = G + (size_t)r.sorb * r.Hq;   // [2][2][H]: a_h, b_h, double-buffered over the walkers
@@ -209,6 +243,7 @@ __global__ __launch_bounds__(kBlock) void rdm_rbm_kernel(const uint64_t *__restr
   double *Ts = cs + r.sorb;
   uint32_t *list = reinterpret_cast<uint32_t *>(Ts + (SINGLES ? (size_t)r.K * r.sorb : 0));
   uint32_t *wcnt = list + kBlock;
+  double *ev = reinterpret_cast<double *>(wcnt + kBlock / 64);  // (JASTROW) [2][sorb]: e_o = exp(-2 xl r_o), double-buffered as ab
   const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
   const int sorb = r.sorb, K = r.K, H = r.H, Hq = r.Hq;
   const bool oe = r.owner_empty != 0;
@@ -261,7 +296,11 @@ __global__ __launch_bounds__(kBlock) void rdm_rbm_kernel(const uint64_t *__restr
       dth[s] = -2.0 * xo * wsum;
     }
   }
-  const double vis_owner = -2.0 * xo * (SINGLES ? rbm[r.offVb + o0] : rbm[r.offVb + o0] + rbm[r.offVb + o1]);
+  double vis_owner = -2.0 * xo * (SINGLES ? rbm[r.offVb + o0] : rbm[r.offVb + o0] + rbm[r.offVb + o1]);
+  const double *__restrict__ Sj = jz.tab + jz.offS;  // (JASTROW) S [sorb][sorb]
+  // the orbital whose e_o this thread stages: from the last thread down, the waves that stage no hidden unit when H is small
+  const int oj = kBlock - 1 - tid;
+  if constexpr (JASTROW && !SINGLES) vis_owner += 4.0 * Sj[(int64_t)o0 * sorb + o1];  // the owner pair: x_o0 x_o1 = 1
   __syncthreads();
   // ---- this thread's items: orbitals l0 (> l1 within a same-spin pair; alpha, beta in class 2), constant c_Q, running sum
   int l0[kRdmMaxItems], l1[kRdmMaxItems];
@@ -274,7 +313,10 @@ __global__ __launch_bounds__(kBlock) void rdm_rbm_kernel(const uint64_t *__restr
     if (it < nitems) {
       if constexpr (SINGLES) {
         l0[j] = l1[j] = 2 * it + cls;
-        lc[j] = exp(2.0 * xl * (cs[l0[j]] - rbm[r.offVb + l0[j]]));
+        double lnc = 2.0 * xl * (cs[l0[j]] - rbm[r.offVb + l0[j]]);
+        // the pair terms of the flip formula that involve the item are constants of the workgroup: x_o x_l = -1
+        if constexpr (JASTROW) lnc += -4.0 * Sj[(int64_t)o0 * sorb + l0[j]];
+        lc[j] = exp(lnc);
       } else {
         if (cls < 2) {
           int hi, lo;
@@ -283,7 +325,13 @@ __global__ __launch_bounds__(kBlock) void rdm_rbm_kernel(const uint64_t *__restr
         } else {
           l0[j] = 2 * (it / K); l1[j] = 2 * (it % K) + 1;
         }
-        lc[j] = exp(2.0 * xl * ((cs[l0[j]] + cs[l1[j]]) - (rbm[r.offVb + l0[j]] + rbm[r.offVb + l1[j]])));
+        double lnc = 2.0 * xl * ((cs[l0[j]] + cs[l1[j]]) - (rbm[r.offVb + l0[j]] + rbm[r.offVb + l1[j]]));
+        if constexpr (JASTROW) {
+          // + 4 S within the item pair, - 4 S for each of the four crossed owner-item pairs
+          const int64_t r0 = (int64_t)o0 * sorb, r1 = (int64_t)o1 * sorb;
+          lnc += 4.0 * Sj[(int64_t)l0[j] * sorb + l1[j]] - 4.0 * (((Sj[r0 + l0[j]] + Sj[r0 + l1[j]]) + Sj[r1 + l0[j]]) + Sj[r1 + l1[j]]);
+        }
+        lc[j] = exp(lnc);
       }
     }
   }
@@ -317,6 +365,7 @@ __global__ __launch_bounds__(kBlock) void rdm_rbm_kernel(const uint64_t *__restr
     // the next walker's words, weight and theta are requested while the current one is worked on
     uint64_t xn[LEN];
     double thn[2], wn = 0.0;
+    [[maybe_unused]] double ron = 0.0, rln = 0.0;  // (JASTROW) r of the owner's orbitals (summed), r of this thread's orbital oj
     auto request = [&](uint32_t t) {
       const int64_t i = base + list[t];
 #pragma unroll
@@ -327,15 +376,22 @@ __global__ __launch_bounds__(kBlock) void rdm_rbm_kernel(const uint64_t *__restr
         const int h = tid + s * kBlock;
         thn[s] = h < H ? ws[r.offTheta + i * H + h] : 0.0;
       }
+      if constexpr (JASTROW) {
+        const double *__restrict__ ri = ws + jz.offR + i * sorb;
+        ron = SINGLES ? ri[o0] : ri[o0] + ri[o1];
+        rln = oj < sorb ? ri[oj] : 0.0;
+      }
     };
     if (cnt) request(0);
     for (uint32_t t = 0; t < cnt; ++t) {
       Walker<LEN> wk;
       rdm_make_walker<LEN>(xn, wk);
       const double wi = wn, th0 = thn[0], th1 = thn[1];
+      [[maybe_unused]] const double ro = ron, rl = rln;
       if (t + 1 < cnt) request(t + 1);
       double *__restrict__ abp = ab + (size_t)parity * 2 * H;
       double *__restrict__ redp = red + parity * (kBlock / 64);
+      [[maybe_unused]] double *__restrict__ evp = ev + (size_t)parity * sorb;
       parity ^= 1u;
       // stage a_h, b_h of theta' and the owner's factor  prod_h cosh theta'_h / cosh theta_h
       double lnf = 0.0;
@@ -351,6 +407,8 @@ __global__ __launch_bounds__(kBlock) void rdm_rbm_kernel(const uint64_t *__restr
           lnf += fma(sg, d, log1p(exp(-2.0 * sg * tp)) - log1p(exp(-2.0 * fabs(th))));
         }
       }
+      if constexpr (JASTROW)
+        if (oj < sorb) evp[oj] = exp(-2.0 * xl * rl);  // (an orbital that is not on the lane side in this walker: any value, read by no live item)
       // fixed order: a butterfly over the lanes (the same bits in every lane), then the waves in turn
 #pragma unroll
       for (int d = 32; d > 0; d >>= 1) lnf += __shfl_xor(lnf, d);
@@ -361,7 +419,9 @@ __global__ __launch_bounds__(kBlock) void rdm_rbm_kernel(const uint64_t *__restr
       double lnsum = 0.0;
 #pragma unroll
       for (int v = 0; v < kBlock / 64; ++v) lnsum += redp[v];
-      const double cw = wi * exp(lnsum + vis_owner);
+      double lnown = lnsum + vis_owner;
+      if constexpr (JASTROW) lnown += -2.0 * xo * ro;
+      const double cw = wi * exp(lnown);
       const uint32_t lane_occ = oe ? 1u : 0u;
 #pragma unroll
       for (int j = 0; j < kRdmMaxItems; ++j) {
@@ -377,6 +437,7 @@ __global__ __launch_bounds__(kBlock) void rdm_rbm_kernel(const uint64_t *__restr
           prod *= fma(abp[h], g, abp[H + h]);
         }
         double v = (cw * lc[j]) * prod;
+        if constexpr (JASTROW) v *= SINGLES ? evp[a0] : evp[a0] * evp[a1];
         uint32_t par;
         if constexpr (SINGLES) {
           const int hh = oe ? a0 : o0, qq = oe ? o0 : a0;
@@ -513,37 +574,80 @@ extern "C" int64_t pynqs_rdm_rbm_workspace(int64_t nbatch, int sorb, int nhidden
   return r.total * 8;
 }
 
-extern "C" int pynqs_rdm_rbm(const uint64_t *bra, int64_t nbatch, int sorb, int nele, int noA, int noB, const double *w,
-                             const void *rbm_table, int nhidden, void *workspace, double *rdm1, double *rdm2, void *stream) {
-  pynqs::DeviceScope device_scope_(rdm1);
-  if (!pynqs_rdm_rbm_supported(sorb, nele, noA, noB, nhidden)) return set_error(PYNQS_EINVAL, "rdm_rbm: sizes not served by the fused kernel");
-  if (nbatch < 0 || nbatch > 0x7fffffffll) return set_error(PYNQS_EINVAL, "rdm_rbm: bad nbatch");
-  if (!rbm_table || !workspace || !rdm1 || !rdm2 || (nbatch > 0 && (!bra || !w))) return set_error(PYNQS_EINVAL, "null pointer");
+// pynqs_rdm_rbm (jastrow_table null) and pynqs_rdm_jrbm: the same launches, the JASTROW flavour of the owner kernel and rdm_r_kernel before it
+static int rdm_fused_launch(const char *what, const uint64_t *bra, int64_t nbatch, int sorb, int nele, int noA, int noB, const double *w,
+                            const void *rbm_table, const void *jastrow_table, int nhidden, void *workspace, double *rdm1, double *rdm2,
+                            void *stream) {
+  const bool jastrow = jastrow_table != nullptr;
+  if (nbatch < 0 || nbatch > 0x7fffffffll) return set_error(PYNQS_EINVAL, jastrow ? "rdm_jrbm: bad nbatch" : "rdm_rbm: bad nbatch");
   RdmLayout r;
   RbmLayout rl;
   make_rdm_layout(nbatch, sorb, noA, noB, nhidden, &r);
   make_rbm_layout(sorb, nhidden, &rl);
+  RdmJastrow jz = {nullptr, 0, 0};
+  if (jastrow) {
+    JastrowLayout jl;
+    make_jastrow_layout(sorb, &jl);
+    jz.tab = (const double *)jastrow_table; jz.offS = jl.offS; jz.offR = r.total;
+  }
   hipStream_t st = (hipStream_t)stream;
   double *ws = (double *)workspace;
   const double *rbm = (const double *)rbm_table;
   // (the last kernel reads only entries that some workgroup has written -- every (owner, item, slice) writes its sum, zero included --
   // so the tables need no clearing; without walkers nothing is launched to write them)
-  if (nbatch == 0 && hipMemsetAsync(ws, 0, (size_t)r.total * 8, st) != hipSuccess) return check_launch("rdm_rbm memset");
+  if (nbatch == 0 && hipMemsetAsync(ws, 0, (size_t)r.total * 8, st) != hipSuccess) return check_launch(what);
   const int len = (sorb - 1) / 64 + 1;
-  const int64_t nth = nbatch * nhidden;
-  if ((nth + kBlock - 1) / kBlock > 0x7fffffffll) return set_error(PYNQS_EINVAL, "rdm_rbm: too many walkers for one call");
+  const int64_t nth = nbatch * nhidden, nr = nbatch * sorb;
+  if ((nth + kBlock - 1) / kBlock > 0x7fffffffll) return set_error(PYNQS_EINVAL, jastrow ? "rdm_jrbm: too many walkers for one call" : "rdm_rbm: too many walkers for one call");
   const uint32_t nowners = 2u * (uint32_t)r.npS + (uint32_t)(r.K * r.K);
-  const size_t ldsD = rdm_lds_bytes(r, false), ldsS = rdm_lds_bytes(r, true);
+  const size_t ldsD = rdm_lds_bytes(r, false, jastrow), ldsS = rdm_lds_bytes(r, true, jastrow);
   DISPATCH_LEN(len, {
     if (nth > 0) {
       hipLaunchKernelGGL((rdm_theta_kernel<LEN>), dim3((uint32_t)((nth + kBlock - 1) / kBlock)), dim3(kBlock), 0, st, bra, nbatch, r, rbm, rl.offHb, ws);
       hipLaunchKernelGGL((rdm_diag_kernel<LEN>), dim3((uint32_t)(sorb * r.nslS)), dim3(kBlock), 0, st, bra, nbatch, w, r, ws);
-      hipLaunchKernelGGL((rdm_rbm_kernel<LEN, false>), dim3(nowners * (uint32_t)r.nslD), dim3(kBlock), ldsD, st, bra, nbatch, w, r, rbm, ws);
-      hipLaunchKernelGGL((rdm_rbm_kernel<LEN, true>), dim3((uint32_t)(sorb * r.nslS)), dim3(kBlock), ldsS, st, bra, nbatch, w, r, rbm, ws);
+      if (jastrow) {
+        hipLaunchKernelGGL((rdm_r_kernel<LEN>), dim3((uint32_t)((nr + kBlock - 1) / kBlock)), dim3(kBlock), 0, st, bra, nbatch, sorb, jz, ws);
+        hipLaunchKernelGGL((rdm_rbm_kernel<LEN, false, true>), dim3(nowners * (uint32_t)r.nslD), dim3(kBlock), ldsD, st, bra, nbatch, w, r, rbm, ws, jz);
+        hipLaunchKernelGGL((rdm_rbm_kernel<LEN, true, true>), dim3((uint32_t)(sorb * r.nslS)), dim3(kBlock), ldsS, st, bra, nbatch, w, r, rbm, ws, jz);
+      } else {
+        hipLaunchKernelGGL((rdm_rbm_kernel<LEN, false, false>), dim3(nowners * (uint32_t)r.nslD), dim3(kBlock), ldsD, st, bra, nbatch, w, r, rbm, ws, jz);
+        hipLaunchKernelGGL((rdm_rbm_kernel<LEN, true, false>), dim3((uint32_t)(sorb * r.nslS)), dim3(kBlock), ldsS, st, bra, nbatch, w, r, rbm, ws, jz);
+      }
     }
   });
   const int64_t pair = (int64_t)sorb * (sorb - 1) / 2, nslots = pair * (pair + 1) / 2;
   const int64_t nfold = nslots > (int64_t)sorb * sorb ? nslots : (int64_t)sorb * sorb;
   hipLaunchKernelGGL(rdm_fold_kernel, dim3((uint32_t)((nfold + kBlock - 1) / kBlock)), dim3(kBlock), 0, st, r, ws, rdm1, rdm2, nslots);
-  return check_launch("rdm_rbm");
+  return check_launch(what);
+}
+
+extern "C" int pynqs_rdm_rbm(const uint64_t *bra, int64_t nbatch, int sorb, int nele, int noA, int noB, const double *w,
+                             const void *rbm_table, int nhidden, void *workspace, double *rdm1, double *rdm2, void *stream) {
+  pynqs::DeviceScope device_scope_(rdm1);
+  if (!pynqs_rdm_rbm_supported(sorb, nele, noA, noB, nhidden)) return set_error(PYNQS_EINVAL, "rdm_rbm: sizes not served by the fused kernel");
+  if (!rbm_table || !workspace || !rdm1 || !rdm2 || (nbatch > 0 && (!bra || !w))) return set_error(PYNQS_EINVAL, "null pointer");
+  return rdm_fused_launch("rdm_rbm", bra, nbatch, sorb, nele, noA, noB, w, rbm_table, nullptr, nhidden, workspace, rdm1, rdm2, stream);
+}
+
+extern "C" int pynqs_rdm_jrbm_supported(int sorb, int nele, int noA, int noB, int nhidden) {
+  RdmLayout r;
+  JastrowLayout jl;
+  if (!pynqs_rdm_rbm_supported(sorb, nele, noA, noB, nhidden) || !make_jastrow_layout(sorb, &jl)) return 0;
+  make_rdm_layout(0, sorb, noA, noB, nhidden, &r);
+  return rdm_lds_bytes(r, true, true) <= kRdmMaxLds ? 1 : 0;
+}
+
+extern "C" int64_t pynqs_rdm_jrbm_workspace(int64_t nbatch, int sorb, int nhidden) {
+  RdmLayout r;
+  if (!make_rdm_layout(nbatch, sorb, 0, 0, nhidden, &r)) return -1;
+  return (r.total + nbatch * sorb) * 8;  // r [n][sorb] behind pynqs_rdm_rbm's
+}
+
+extern "C" int pynqs_rdm_jrbm(const uint64_t *bra, int64_t nbatch, int sorb, int nele, int noA, int noB, const double *w,
+                              const void *rbm_table, const void *jastrow_table, int nhidden, void *workspace, double *rdm1, double *rdm2,
+                              void *stream) {
+  pynqs::DeviceScope device_scope_(rdm1);
+  if (!pynqs_rdm_jrbm_supported(sorb, nele, noA, noB, nhidden)) return set_error(PYNQS_EINVAL, "rdm_jrbm: sizes not served by the fused kernel");
+  if (!rbm_table || !jastrow_table || !workspace || !rdm1 || !rdm2 || (nbatch > 0 && (!bra || !w))) return set_error(PYNQS_EINVAL, "null pointer");
+  return rdm_fused_launch("rdm_jrbm", bra, nbatch, sorb, nele, noA, noB, w, rbm_table, jastrow_table, nhidden, workspace, rdm1, rdm2, stream);
 }

@@ -76,9 +76,10 @@ class JastrowRBM(nn.Module):
     exp(sum_ij M_ij x_i x_j), prod_dim = 1).  jastrow: M [sorb, sorb], any real matrix -- not symmetric, diagonal allowed (it scales psi).
     forward() is plain torch, so every generic route of the package works with it; the fused routes are its own: SIMPLE local energies
     (pynqs_amd.energy, pynqs_eloc_jrbm), pynqs_amd.grad.FusedJastrowRbmGrad, the many-chain sampler (pynqs_amd.mcmc,
-    pynqs_mcmc_jrbm), stochastic reconfiguration (pynqs_amd.sr.FusedJastrowRbmSR) and, as a GFMC trial function, the fixed-node
+    pynqs_mcmc_jrbm), stochastic reconfiguration (pynqs_amd.sr.FusedJastrowRbmSR), as a GFMC trial function, the fixed-node
     Green's row (pynqs_amd.gfmc.green_kernel, pynqs_green_jrbm: the move then goes by the column's rank and nothing of size
-    walkers x columns x words is materialised).  On purpose NOT a RealRBM and without an `rbm_type`: the
+    walkers x columns x words is materialised) and the reduced density matrices (pynqs_amd.rdm, pynqs_rdm_jrbm: bit-reproducible,
+    nothing of size walkers x columns exists).  On purpose NOT a RealRBM and without an `rbm_type`: the
     fused routes of the plain RBMs recognise their modules by those two and would drop M."""
 
     def __init__(self, weights: Tensor, hidden_bias: Tensor, visible_bias: Tensor, jastrow: Tensor) -> None:

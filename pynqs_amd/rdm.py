@@ -5,7 +5,8 @@ density matrices"):
 
 so that dot(h1e, rdm1) + dot(h2e, rdm2) is the SIMPLE energy estimate for ANY integrals.  Two routes, chosen as energy.py chooses
 FUSED_RBM: a RealRBM (rbm_type "real", float64 parameters on the GPU) within pynqs_rdm_rbm_supported takes the fused kernel
-(pynqs_rdm_rbm: nothing of size n x ncomb exists, bit-reproducible); everything else takes the generic route: chunks of walkers,
+(pynqs_rdm_rbm: nothing of size n x ncomb exists, bit-reproducible), a JastrowRBM (float64 parameters on the GPU, jastrow [sorb, sorb])
+within pynqs_rdm_jrbm_supported the same kernel in its Jastrow flavour (pynqs_rdm_jrbm); everything else takes the generic route: chunks of walkers,
 get_comb_tensor, the module's own forward on every x', psi(x') / psi(x), pynqs_rdm_scatter (f64 atomics: not bit-reproducible).
 Under torch.distributed every rank passes its shard of the walkers with probabilities pre-scaled by the world size, as everywhere in
 this package; both packed arrays are all-reduced in one flat buffer and divided by the world size."""
@@ -108,34 +109,47 @@ def _check(x: Tensor, state_prob: Tensor, sorb: int, nele: int, noa: int, nob: i
 
 
 def _fused_params(ansatz, sorb: int, nele: int, noa: int, nob: int):
-    """(W, hb, vb) if the fused kernel serves this ansatz, else None"""
-    from .rbm import RealRBM
+    """(W, hb, vb, M or None) if the fused kernel serves this ansatz (M: the Jastrow matrix of a JastrowRBM), else None"""
+    from .rbm import JastrowRBM, RealRBM
 
     m = getattr(ansatz, "module", ansatz)
-    if not isinstance(m, RealRBM) or m.rbm_type != "real":
+    jastrow = isinstance(m, JastrowRBM)
+    if not jastrow and (not isinstance(m, RealRBM) or m.rbm_type != "real"):
         return None
     W, hb, vb = m.weights, m.hidden_bias, m.visible_bias
     if W.dtype != torch.float64 or hb.dtype != torch.float64 or vb.dtype != torch.float64 or not W.is_cuda or W.dim() != 2 or W.size(1) != sorb:
         return None
+    if jastrow:
+        M = m.jastrow
+        if M.dtype != torch.float64 or M.device != W.device or tuple(M.shape) != (sorb, sorb):
+            return None
+        if not N.lib().pynqs_rdm_jrbm_supported(sorb, nele, noa, nob, int(W.size(0))):
+            return None
+        return W.detach(), hb.detach().reshape(-1), vb.detach().reshape(-1), M.detach()
     if not N.lib().pynqs_rdm_rbm_supported(sorb, nele, noa, nob, int(W.size(0))):
         return None
-    return W.detach(), hb.detach().reshape(-1), vb.detach().reshape(-1)
+    return W.detach(), hb.detach().reshape(-1), vb.detach().reshape(-1), None
 
 
 def _rdm_fused(x: Tensor, prob: Tensor, params, sorb: int, nele: int, noa: int, nob: int, out: Tensor) -> None:
-    W, hb, vb = params
+    W, hb, vb, M = params
     dev = x.device
     if W.device != dev:
         raise ValueError("reduced_density_matrices: walkers and parameters on different devices")
     table = CX.RBMTable(W, hb, vb)
+    jtable = CX.JastrowTable(M) if M is not None else None
     n, H = x.size(0), int(W.size(0))
-    need = N.lib().pynqs_rdm_rbm_workspace(n, sorb, H)
+    need = (N.lib().pynqs_rdm_rbm_workspace if M is None else N.lib().pynqs_rdm_jrbm_workspace)(n, sorb, H)
     if need < 0:
         raise ValueError("reduced_density_matrices: bad sizes")
     work = torch.empty(max(need // 8, 1), dtype=torch.float64, device=dev)
     n1, _ = _sizes(sorb)
-    N.check(N.lib().pynqs_rdm_rbm(x.data_ptr(), n, sorb, nele, noa, nob, prob.data_ptr(), table.data_ptr(), H, work.data_ptr(),
-                                  out.data_ptr(), out[n1:].data_ptr(), torch.cuda.current_stream(dev).cuda_stream), "pynqs_rdm_rbm")
+    tail = (H, work.data_ptr(), out.data_ptr(), out[n1:].data_ptr(), torch.cuda.current_stream(dev).cuda_stream)
+    if M is None:
+        N.check(N.lib().pynqs_rdm_rbm(x.data_ptr(), n, sorb, nele, noa, nob, prob.data_ptr(), table.data_ptr(), *tail), "pynqs_rdm_rbm")
+    else:
+        N.check(N.lib().pynqs_rdm_jrbm(x.data_ptr(), n, sorb, nele, noa, nob, prob.data_ptr(), table.data_ptr(), jtable.data_ptr(), *tail),
+                "pynqs_rdm_jrbm")
 
 
 def scatter(x: Tensor, prob: Tensor, ratio: Tensor, sorb: int, nele: int, noa: int, nob: int, out: Tensor) -> None:
@@ -179,8 +193,8 @@ def reduced_density_matrices(x: Tensor, state_prob: Tensor, ansatz, sorb: int, n
     x = x.contiguous()
     params = _fused_params(ansatz, sorb, nele, noa, nob) if fused is not False and (FUSED_RBM or fused) else None
     if fused and params is None:
-        raise ValueError("reduced_density_matrices: fused=True needs a RealRBM (rbm_type 'real', float64 parameters on the GPU) within "
-                         "pynqs_rdm_rbm_supported")
+        raise ValueError("reduced_density_matrices: fused=True needs a RealRBM (rbm_type 'real') within pynqs_rdm_rbm_supported or a "
+                         "JastrowRBM within pynqs_rdm_jrbm_supported, float64 parameters on the GPU")
     n1, n2 = _sizes(sorb)
     out = torch.zeros(n1 + n2, dtype=torch.float64, device=x.device)
     if params is not None:
