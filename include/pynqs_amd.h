@@ -303,7 +303,18 @@ int pynqs_jastrow_grad(const uint64_t *onv, int64_t n, int sorb, const double *j
  * green double[n][ncomb] (the fixed-node Green's function row of each walker, >= 0), rand_num double[n] in [0, 1),
  * comb uint64[n][ncomb][len] (get_comb_hij_fused's first output).  Per walker: beta = sum_k green[k];
  * index = first k with (green[0] + ... + green[k]) >= rand_num * beta  (the reference's
- * searchsorted(cumsum / beta, rand_num, right=False), clamped to ncomb - 1); x_new = comb[index]. */
+ * searchsorted(cumsum / beta, rand_num, right=False), clamped to ncomb - 1); x_new = comb[index].
+ * The sums run in float64 in the kernel's own order, so the law is stated on the exact row.  G = green[x] >= 0 with m = ncomb columns,
+ * S = sum G, C_k = G_0 + ... + G_k in exact arithmetic, C_{-1} = 0, u = rand_num[x], tau = m 2^-52 S:
+ *   index = k only if  C_{k-1} - tau < u S <= C_k + tau  AND  (G_k > 0 or k = 0):  a column without weight is never chosen -- in fixed-node
+ *     GFMC it is a move across the node -- although the bracket alone would admit it (C_{k-1} = C_k there).  u = 0 with G_0 = 0 may
+ *     give index 0 or the first column with weight; the kernel gives index 0, as the reference's searchsorted does (the walker stays).
+ *     A uniform farther than tau from every C_j leaves exactly one column, the exact one.
+ *   A row with S = 0 gives index 0, beta = 0 and x_new = comb[0] (the rank form: bra[x]).
+ *   |beta - S| <= (m - 1) 2^-53 S; equal rows give bit-equal beta, and pynqs_gfmc_sample and pynqs_gfmc_sample_rank give the same bits.
+ * tau: every running sum the kernel compares is a float64 sum of at most m non-negative entries in some order, within (m - 1) 2^-53 S of
+ * its exact value; so is beta, and u * beta adds one rounding; two such quantities are compared.
+ * n = 0 returns PYNQS_OK and writes nothing.  (tests/gfmc_exact.py holds the law in exact integer arithmetic.) */
 int pynqs_gfmc_sample(const double *green, int64_t n, int64_t ncomb, const double *rand_num, const uint64_t *comb,
                       int sorb, int64_t *index, double *beta, uint64_t *x_new, void *stream);
 

@@ -4,8 +4,14 @@
 // [n, ncomb] Green's-function matrix; here one workgroup per walker reads its row twice at most (once for the
 // tile sums, then only the tile that holds the target), the row never leaves L2 in between.
 //   1. every wave sums whole tiles of the row (a lane reads kPerLane consecutive values, 16-byte loads) -> LDS
-//   2. the first wave scans the tile sums, finds the tile in which the running sum reaches u * beta,
-//   3. re-reads that tile, scans it in column order and takes the first column that reaches the target.
+//   2. the first wave scans the tile sums, finds the first tile WITH WEIGHT in which the running sum reaches u * beta,
+//   3. re-reads that tile, scans it in column order and takes the first column WITH WEIGHT that reaches the target.
+// The law (include/pynqs_amd.h): C_{k-1} - tau < u S <= C_k + tau with tau = m 2^-52 S, and G[index] > 0 unless index = 0.
+// Every running sum compared with the target is a plain sum of the row's entries in some order (no difference of sums), so
+// each is within (m - 1) 2^-53 S of its exact value.  The scans add in trees that differ from lane to lane, so across a
+// zero-weight column (or an empty tile) the running sum may move by an ulp in either direction: only entries with weight
+// are candidates, and where none reaches the target the last one with weight is taken, at tile level and inside the tile.
+// A row of sum zero goes to index 0, and so does u = 0.
 // Memory-bound: 8 B per matrix element, once.
 #include "detcore.h"
 #include "launch.h"
@@ -59,23 +65,31 @@ __global__ __launch_bounds__(kBlock) void gfmc_sample_kernel(const double *__res
     const double incl = wave_incl_scan(s, lane);
     const double total = __shfl(incl, 63);
     const double target = rnd[walker] * total;
-    double before = incl - s;  // sum of the tiles of the lanes in front
-    // first tile whose inclusive sum reaches the target (tiles in order: lanes in order, then i in order)
-    uint32_t mine = 0xffffffffu;
-    double mine_before = 0.0;
+    const double lower = __shfl_up(incl, 1);
+    double before = lane ? lower : 0.0;  // sum of the tiles of the lanes in front
+    // first tile with weight whose inclusive sum reaches the target (tiles in order: lanes in order, then i in order), and the
+    // last tile with weight at all
+    uint32_t mine = 0xffffffffu, last = 0xffffffffu;
+    double mine_before = 0.0, last_before = 0.0;
 #pragma unroll
     for (int i = 0; i < kPer; ++i) {
       const uint32_t t = lane * kPer + i;
-      if (mine == 0xffffffffu && t < ntiles && before + loc[i] >= target) { mine = t; mine_before = before; }
+      if (loc[i] > 0.0) {
+        if (mine == 0xffffffffu && before + loc[i] >= target) { mine = t; mine_before = before; }
+        last = t; last_before = before;
+      }
       before += loc[i];
     }
     const uint64_t have = __ballot(mine != 0xffffffffu);
-    const int first = have ? __ffsll((long long)have) - 1 : -1;
-    if (lane == (first < 0 ? 0 : first)) {
-      // first < 0: rounding put the target beyond the last partial sum -> last tile, whose scan then ends on the
-      // row's last column
-      s_tile = first < 0 ? ntiles - 1 : mine;
-      s_before = first < 0 ? total - tsum[ntiles - 1] : mine_before;
+    const uint64_t any = __ballot(last != 0xffffffffu);
+    // no tile reaches the target: rounding put it beyond the last partial sum -> the last tile with weight, whose scan then
+    // ends on the row's last column with weight.  No tile has weight: the row's sum is zero.  A target of zero (u = 0, or
+    // the product underflows) is reached by the empty sum in front of column 0 already: index 0 with or without weight
+    // there, which is what the reference's searchsorted(.., right=False) gives for u = 0 on a clamped diagonal.
+    const int src = have ? __ffsll((long long)have) - 1 : any ? 63 - __clzll((long long)any) : 0;
+    if (lane == src) {
+      s_tile = !(target > 0.0) ? 0xffffffffu : have ? mine : any ? last : 0xffffffffu;
+      s_before = have ? mine_before : last_before;
       s_target = target;
     }
     if (lane == 0) beta[walker] = total;
@@ -88,19 +102,21 @@ __global__ __launch_bounds__(kBlock) void gfmc_sample_kernel(const double *__res
     double run = s_before;
     const int64_t c0 = (int64_t)t * tile, c1 = min(c0 + (int64_t)tile, m);
     int64_t found = -1, last_pos = -1;
+    if (t == 0xffffffffu) found = 0;  // a row of sum zero, or a target of zero
     for (int64_t c = c0; c < c1 && found < 0; c += 64) {
       const double v = c + lane < c1 ? row[c + lane] : 0.0;
       const double incl = wave_incl_scan(v, lane) + run;
-      const uint64_t hit = __ballot(c + lane < c1 && incl >= target);
-      if (hit) found = c + __ffsll((long long)hit) - 1;
       const uint64_t pos = __ballot(v > 0.0);
+      const uint64_t hit = pos & __ballot(incl >= target);
+      if (hit) found = c + __ffsll((long long)hit) - 1;
       if (pos) last_pos = c + 63 - __clzll((long long)pos);
       run = __shfl(incl, 63);
     }
     // The tile was chosen from lane-strided partial sums, the scan above adds in column order: when the two roundings
     // disagree at the tile's end the target is "just behind" the tile's last weight -> take the last column that HAS
-    // weight (never a zero-weight column, which the reference's searchsorted cannot return either)
-    if (found < 0) found = last_pos >= 0 ? last_pos : c1 - 1;
+    // weight (the tile has one: its sum is positive; never a zero-weight column, which the reference's searchsorted
+    // cannot return either)
+    if (found < 0) found = last_pos >= 0 ? last_pos : 0;
     if (lane == 0) index[walker] = found;
     if constexpr (FROM_RANK) {
       if (lane == 0) {

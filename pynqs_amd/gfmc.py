@@ -2,7 +2,8 @@
 
 green_kernel(): for every walker x the row G(x' <- x) = psi(x') <x'|Lambda - H_eff|x> / psi(x) over its S+D
 list, the fixed-node effective Hamiltonian with the sign-flip potential on the diagonal, and the local energy;
-sample_update(): one multinomial move per walker by inverse-CDF (row cumsum + searchsorted).
+sample_update(): one multinomial move per walker by inverse-CDF (row cumsum + searchsorted).  The law of the move (never a column
+without weight, a row of sum zero stays where it is; include/pynqs_amd.h) is held in exact arithmetic by tests/gfmc_exact.py.
 Enumeration and matrix elements come from the fused HIP kernel; psi from pynqs_amd.energy.Func.
 """
 from __future__ import annotations
@@ -133,6 +134,15 @@ def sample_update(x: Tensor, weight: Tensor, comb_x: Tensor, green_kernel: Tenso
     if rand_num is None:
         rand_num = torch.rand_like(beta)
     index = torch.searchsorted(cum_prob, rand_num, right=False).reshape(-1)
+    # cumsum's last entry and sum's total round differently: a uniform next to 1 can lie beyond the last quotient, and a row of sum zero is
+    # 0 / 0.  As the kernel does: the last column with weight, and index 0 for the empty row (searchsorted's own answer is out of range)
+    m = green_kernel.size(-1)
+    empty = ~(beta.reshape(-1) > 0)
+    over = (index >= m) & ~empty
+    if bool(over.any()):
+        last = m - 1 - (green_kernel.flip(-1) > 0).to(torch.uint8).argmax(-1).reshape(-1)
+        index = torch.where(over, last, index)
+    index = torch.where(empty, torch.zeros_like(index), index)
     x_new = comb_x[torch.arange(beta.size(0), device=comb_x.device), index]
     weight_new = weight * beta.squeeze()
     accept_nums = index.nonzero().size(0)

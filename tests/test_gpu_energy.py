@@ -307,8 +307,9 @@ def test_gfmc_step_matches_direct_tensor_algebra(env):
 def test_gfmc_sample_kernel_matches_sequential_oracle(n, m, L):
     """pynqs_gfmc_sample (sum + cumsum + searchsorted + gather in one kernel) against a sequential float64 cumsum:
     index = first k with cum[k] >= u * beta (gfmc/walker.py:268-271); a different k is accepted only when the
-    running sum is within rounding of the target there.  Rows contain exact zeros, one row is a single spike and
-    the uniforms include 0 and 1 - 2^-53."""
+    running sum is within rounding of the target there, and the chosen column has weight.  Rows contain exact zeros,
+    one row is a single spike and the uniforms include 0 and 1 - 2^-53.  (The exact law at the CDF boundaries:
+    tests/test_gpu_gfmc_exact.py.)"""
     from pynqs_amd import gfmc
 
     g = torch.Generator().manual_seed(100 * n + m)
@@ -339,6 +340,7 @@ def test_gfmc_sample_kernel_matches_sequential_oracle(n, m, L):
     for i in range(n):
         hits = np.nonzero((comb[i] == xn[i]).all(dim=1).numpy())[0]
         assert hits.size >= 1
+        assert all(gk[i, int(k)] > 0 for k in hits), (i, hits, "a column without weight")  # (every row has weight at column 0)
         target = u[i, 0].item() * tot[i]
         want = min(int(np.searchsorted(cum[i], target, side="left")), m - 1)
         if want not in hits:

@@ -102,6 +102,8 @@ while time.time() - t0 < budget:
         xn = torch.empty((n, (sorb - 1) // 64 + 1), dtype=torch.int64, device=dev)
         N_.check(N_.lib().pynqs_gfmc_sample_rank(gk.data_ptr(), n, u.data_ptr(), G(x).data_ptr(), sorb, nele, noA, noB, xi.data_ptr(), be.data_ptr(),
                                                xn.data_ptr(), torch.cuda.current_stream().cuda_stream), "sample_rank")
+        bh, ih = be.cpu().numpy().reshape(n), xi.cpu().numpy()
+        assert bool((gk.cpu().numpy()[np.arange(n), ih][bh > 0] > 0).all()), ("rank move onto a column without weight", sorb, noA, noB, n)
         if bool((be > 0).all()):
             picked = co[np.arange(n), xi.cpu().numpy()]
             assert np.array_equal(xn.cpu().numpy().view(np.uint64), np.ascontiguousarray(picked).view(np.uint64).reshape(n, -1)), ("rank move", sorb, noA, noB, n, xi.cpu().numpy()[:4])
