@@ -242,6 +242,33 @@ int pynqs_eloc_rbm(const uint64_t *bra, int64_t nbatch, int sorb, int nele, int 
 int pynqs_eloc_rbm_flavour(const uint64_t *bra, int64_t nbatch, int sorb, int nele, int noA, int noB, const void *plan,
                            const void *rbm_table, int nhidden, int flavour, double *eloc, double *psi, void *stream);
 
+/* ---- the spin-flip-projected SIMPLE local energy (vmc/energy/flip.py, _simple_flip) of the three flavours above, fused ----------------
+ *   E_proj(x) = sum_k <x|H|x'_k> [psi(x'_k) + eta eta_m(x'_k) psi(flip x'_k)] / psi(x) / extra_norm^2
+ * flip exchanges the orbitals 2k <-> 2k+1, eta_m(y) = (-1)^(number of doubly occupied spatial orbitals of y), eta = +-1 the projection.
+ * THE MIRRORED TABLE: psi(flip y) of the parameters (W, a, b) is psi(y) of (Wm, am, b) with Wm[h][o] = W[h][o^1], am[o] = a[o^1]
+ * (for the Jastrow factor Mm[i][j] = M[i^1][j^1]): a second table, built by pynqs_rbm_table_build (pynqs_jastrow_table_build) from the
+ * mirrored parameters, on the same walkers and the same excitations.  With psim the amplitude of the mirrored table,
+ *   R(x) = psim(x) / psi(x),   E(x) = sum_k h_k psi(x'_k) / psi(x),   Em(x) = sum_k sigma_k h_k psim(x'_k) / psim(x),
+ *   E_proj(x) = [E(x) + eta eta_m(x) R(x) Em(x)] / extra_norm^2,      sigma_k = eta_m(x'_k) eta_m(x) = (-1)^pi_k,
+ *   pi_k = XOR over the flipped orbitals o of x'_k of the walker's bit at o^1, XOR the number of spatial orbitals with both spin orbitals
+ *   flipped (the diagonal column: sigma = +1).  No spin symmetry of the integrals is assumed (Em is NOT E of the flipped walker).
+ *   pynqs_eloc_rbm_signed : pynqs_eloc_rbm_flavour with every column's matrix element times sigma_k: called with the MIRRORED table it
+ *                           returns eloc = Em and psi = psim (same shapes, psi may be NULL); with any table, that table's signed sum.
+ *   pynqs_eloc_rbm_flip   : eloc = E_proj, psi = psi(x) (required).  rbm_table_mirror: the mirrored table.  extra_norm_dev: DEVICE pointer
+ *                           to extra_norm, or NULL to take the value `extra_norm`.  work: 2 nbatch doubles (PYNQS_RBM_PHASE: 4 nbatch) of
+ *                           device scratch; on return work[0 .. ) = Em and behind it psim, in eloc's / psi's layout.  Three launches on
+ *                           `stream` (the plain pass, the signed pass, a combine kernel that forms R and eta_m(x) from the walker's bits,
+ *                           in complex arithmetic for PYNQS_RBM_PHASE); no host read-back or synchronisation.
+ *   pynqs_eloc_rbm_flip_supported / _form : [host] as pynqs_eloc_rbm_supported / pynqs_eloc_rbm_form(green = 0); both passes (and
+ *                           pynqs_eloc_rbm_signed) take the form of the plain launch. */
+int pynqs_eloc_rbm_flip_supported(int sorb, int nele, int noA, int noB, int nhidden);
+int pynqs_eloc_rbm_flip_form(int64_t nbatch, int sorb, int nele, int noA, int noB, int nhidden);
+int pynqs_eloc_rbm_signed(const uint64_t *bra, int64_t nbatch, int sorb, int nele, int noA, int noB, const void *plan,
+                          const void *rbm_table, int nhidden, int flavour, double *eloc, double *psi, void *stream);
+int pynqs_eloc_rbm_flip(const uint64_t *bra, int64_t nbatch, int sorb, int nele, int noA, int noB, const void *plan,
+                        const void *rbm_table, const void *rbm_table_mirror, int nhidden, int flavour, double eta, double extra_norm,
+                        const double *extra_norm_dev, double *eloc, double *psi, double *work, void *stream);
+
 /* ---- SIMPLE method with an RBM with COMPLEX parameters, fully fused (kernels_rbm_complex.hip) -----------------------------
  * psi(x) = exp(a.x) prod_h 2 cosh(b_h + sum_o W[h][o] x_o) with complex a, b, W: rbm.py:199-211, rbm_type "complex"
  * (weights double[nhidden][sorb][2], hidden_bias double[nhidden][2], visible_bias double[sorb][2] or NULL: the reference's
@@ -293,6 +320,16 @@ int pynqs_eloc_jrbm_supported(int sorb, int nele, int noA, int noB, int nhidden)
 int pynqs_eloc_jrbm_form(int64_t nbatch, int sorb, int nele, int noA, int noB, int nhidden);
 int pynqs_eloc_jrbm(const uint64_t *bra, int64_t nbatch, int sorb, int nele, int noA, int noB, const void *plan,
                     const void *rbm_table, const void *jastrow_table, int nhidden, double *eloc, double *psi, void *stream);
+/* The spin-flip-projected form for the Jastrow-RBM: pynqs_eloc_rbm_signed / _flip (formula and mirrored-table convention there) with the
+ * Jastrow table and its mirror (built from Mm[i][j] = M[i^1][j^1]); served where pynqs_eloc_jrbm is; work: 2 nbatch doubles. */
+int pynqs_eloc_jrbm_flip_supported(int sorb, int nele, int noA, int noB, int nhidden);
+int pynqs_eloc_jrbm_flip_form(int64_t nbatch, int sorb, int nele, int noA, int noB, int nhidden);
+int pynqs_eloc_jrbm_signed(const uint64_t *bra, int64_t nbatch, int sorb, int nele, int noA, int noB, const void *plan,
+                           const void *rbm_table, const void *jastrow_table, int nhidden, double *eloc, double *psi, void *stream);
+int pynqs_eloc_jrbm_flip(const uint64_t *bra, int64_t nbatch, int sorb, int nele, int noA, int noB, const void *plan,
+                         const void *rbm_table, const void *jastrow_table, const void *rbm_table_mirror, const void *jastrow_table_mirror,
+                         int nhidden, double eta, double extra_norm, const double *extra_norm_dev, double *eloc, double *psi, double *work,
+                         void *stream);
 int pynqs_jrbm_forward(const uint64_t *onv, int64_t n, int sorb, const double *weights, const double *hidden_bias,
                        const double *visible_bias, const double *jastrow, int nhidden, double *psi, void *stream);
 int64_t pynqs_jastrow_grad_workspace(int64_t n, int sorb);

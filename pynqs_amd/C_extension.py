@@ -652,6 +652,91 @@ def eloc_jrbm(bra: Tensor, h1e: Tensor, h2e: Tensor, rbm_table: RBMTable, jastro
                                 rbm_table.nhidden, eloc.data_ptr(), psi, st), "pynqs_eloc_jrbm"))
 
 
+def spin_mirror(sorb: int, device) -> Tensor:
+    """the orbital permutation o -> o ^ 1 (alpha <-> beta of every spatial orbital) as an index tensor"""
+    return torch.arange(sorb, device=device) ^ 1
+
+
+def mirrored_rbm_table(weights: Tensor, hidden_bias: Tensor, visible_bias: "Tensor | None" = None) -> RBMTable:
+    """The RBMTable of the spin-mirrored parameters Wm[h][o] = W[h][o ^ 1], am[o] = a[o ^ 1] (one index_select each, on the parameters'
+    device): psi(flip y) of (W, a, b) is psi(y) of (Wm, am, b) (include/pynqs_amd.h, pynqs_eloc_rbm_flip).  Build it wherever the plain
+    table is built: the two belong to one parameter state."""
+    idx = spin_mirror(weights.size(1), weights.device)
+    return RBMTable(weights.detach().index_select(1, idx), hidden_bias, None if visible_bias is None else visible_bias.detach().reshape(-1).index_select(0, idx))
+
+
+def mirrored_jastrow_table(jastrow: Tensor) -> JastrowTable:
+    """The JastrowTable of Mm[i][j] = M[i ^ 1][j ^ 1]"""
+    idx = spin_mirror(jastrow.size(0), jastrow.device)
+    return JastrowTable(jastrow.detach().index_select(0, idx).index_select(1, idx))
+
+
+def _norm_args(extra_norm, dev):
+    """(value, device pointer or None, the tensor behind the pointer) of an extra_norm given as a number or as a one-element tensor"""
+    if isinstance(extra_norm, Tensor):
+        t = extra_norm.detach().reshape(-1)[:1].to(device=dev, dtype=torch.float64).contiguous()
+        return 1.0, t.data_ptr(), t
+    return float(extra_norm), None, None
+
+
+def eloc_rbm_signed(bra: Tensor, h1e: Tensor, h2e: Tensor, table: RBMTable, sorb: int, nele: int, noA: int, noB: int,
+                    want_psi: bool = True, rbm_type: str = "real") -> Tuple[Tensor, "Tensor | None"]:
+    """eloc_rbm with every column's matrix element times sigma_k = eta_m(x'_k) eta_m(x) (pynqs_eloc_rbm_signed): on the mirrored table
+    the second term Em of the spin-flip-projected local energy, and psim(x)."""
+    _check_onv(bra, "bra", sorb, (2,))
+    if rbm_type not in RBM_FLAVOURS:
+        raise RuntimeError(f"rbm_type {rbm_type!r} has no fused local energy (fused: {sorted(RBM_FLAVOURS)})")
+    return _eloc_fused(bra, h1e, h2e, table, sorb, want_psi, _rbm_dtype(rbm_type), lambda x, n, plan, eloc, psi, st: N.check(
+        N.lib().pynqs_eloc_rbm_signed(x.data_ptr(), n, sorb, nele, noA, noB, plan.data_ptr(), table.data_ptr(), table.nhidden,
+                                      RBM_FLAVOURS[rbm_type], eloc.data_ptr(), psi, st), "pynqs_eloc_rbm_signed"))
+
+
+def eloc_rbm_flip(bra: Tensor, h1e: Tensor, h2e: Tensor, table: RBMTable, table_mirror: RBMTable, sorb: int, nele: int, noA: int, noB: int,
+                  eta: float, extra_norm=1.0, rbm_type: str = "real", want_psi: bool = True) -> Tuple[Tensor, "Tensor | None"]:
+    """The spin-flip-projected SIMPLE local energy (vmc/energy/flip.py, _simple_flip) with both amplitude ratios evaluated on chip
+    (pynqs_eloc_rbm_flip): (E_proj[n], psi(x)[n]).  table_mirror: mirrored_rbm_table of the same parameters; extra_norm: a number or a
+    one-element tensor (read on the device, no synchronisation)."""
+    _check_onv(bra, "bra", sorb, (2,))
+    if rbm_type not in RBM_FLAVOURS:
+        raise RuntimeError(f"rbm_type {rbm_type!r} has no fused local energy (fused: {sorted(RBM_FLAVOURS)})")
+    if table_mirror.sorb != sorb or table_mirror.nhidden != table.nhidden or table_mirror.device != table.device:
+        raise RuntimeError("the mirrored RBM table does not belong to the plain one")
+    dt = _rbm_dtype(rbm_type)
+
+    def call(x, n, plan, eloc, psi, st):
+        nv, nptr, keep = _norm_args(extra_norm, x.device)
+        work = torch.empty(2 * n, dtype=dt, device=x.device)
+        N.check(N.lib().pynqs_eloc_rbm_flip(x.data_ptr(), n, sorb, nele, noA, noB, plan.data_ptr(), table.data_ptr(), table_mirror.data_ptr(),
+                                            table.nhidden, RBM_FLAVOURS[rbm_type], float(eta), nv, nptr, eloc.data_ptr(), psi, work.data_ptr(), st),
+                "pynqs_eloc_rbm_flip")
+
+    eloc, psi = _eloc_fused(bra, h1e, h2e, table, sorb, True, dt, call)
+    return eloc, (psi if want_psi else None)
+
+
+def eloc_jrbm_flip(bra: Tensor, h1e: Tensor, h2e: Tensor, rbm_table: RBMTable, jastrow_table: JastrowTable, rbm_table_mirror: RBMTable,
+                   jastrow_table_mirror: JastrowTable, sorb: int, nele: int, noA: int, noB: int, eta: float, extra_norm=1.0,
+                   want_psi: bool = True) -> Tuple[Tensor, "Tensor | None"]:
+    """eloc_rbm_flip for the Jastrow-RBM (pynqs_eloc_jrbm_flip): the tables of eloc_jrbm and their mirrors (mirrored_rbm_table,
+    mirrored_jastrow_table)."""
+    _check_onv(bra, "bra", sorb, (2,))
+    for t in (jastrow_table, rbm_table_mirror, jastrow_table_mirror):
+        if t.sorb != sorb or t.device != rbm_table.device:
+            raise RuntimeError("the tables of the spin-flip-projected Jastrow-RBM energy must share sorb and device")
+    if rbm_table_mirror.nhidden != rbm_table.nhidden:
+        raise RuntimeError("the mirrored RBM table does not belong to the plain one")
+
+    def call(x, n, plan, eloc, psi, st):
+        nv, nptr, keep = _norm_args(extra_norm, x.device)
+        work = torch.empty(2 * n, dtype=torch.float64, device=x.device)
+        N.check(N.lib().pynqs_eloc_jrbm_flip(x.data_ptr(), n, sorb, nele, noA, noB, plan.data_ptr(), rbm_table.data_ptr(), jastrow_table.data_ptr(),
+                                             rbm_table_mirror.data_ptr(), jastrow_table_mirror.data_ptr(), rbm_table.nhidden, float(eta), nv, nptr,
+                                             eloc.data_ptr(), psi, work.data_ptr(), st), "pynqs_eloc_jrbm_flip")
+
+    eloc, psi = _eloc_fused(bra, h1e, h2e, rbm_table, sorb, True, torch.float64, call)
+    return eloc, (psi if want_psi else None)
+
+
 def green_jrbm(bra: Tensor, h1e: Tensor, h2e: Tensor, rbm_table: RBMTable, jastrow_table: JastrowTable, sorb: int, nele: int, noA: int, noB: int,
                Lambda: float, want_psi: bool = False) -> Tuple[Tensor, Tensor, Tensor, "Tensor | None"]:
     """The fixed-node Green's row of every walker for the trial function of eloc_jrbm, one kernel (pynqs_green_jrbm):

@@ -58,6 +58,10 @@ SIGNATURES = {
     "pynqs_rbm_table_build": (_int, [_vp, _vp, _vp, _int, _int, _vp, _vp]),
     "pynqs_eloc_rbm": (_int, [_vp, _i64, _int, _int, _int, _int, _vp, _vp, _int, _vp, _vp, _vp]),
     "pynqs_eloc_rbm_flavour": (_int, [_vp, _i64, _int, _int, _int, _int, _vp, _vp, _int, _int, _vp, _vp, _vp]),
+    "pynqs_eloc_rbm_flip_supported": (_int, [_int, _int, _int, _int, _int]),
+    "pynqs_eloc_rbm_flip_form": (_int, [_i64, _int, _int, _int, _int, _int]),
+    "pynqs_eloc_rbm_signed": (_int, [_vp, _i64, _int, _int, _int, _int, _vp, _vp, _int, _int, _vp, _vp, _vp]),
+    "pynqs_eloc_rbm_flip": (_int, [_vp, _i64, _int, _int, _int, _int, _vp, _vp, _vp, _int, _int, _dbl, _dbl, _vp, _vp, _vp, _vp, _vp]),
     "pynqs_eloc_crbm_supported": (_int, [_int, _int, _int, _int, _int]),
     "pynqs_eloc_crbm_form": (_int, [_i64, _int, _int, _int, _int, _int]),
     "pynqs_crbm_table_bytes": (_i64, [_int, _int]),
@@ -128,6 +132,10 @@ SIGNATURES.update({
     "pynqs_eloc_jrbm_supported": (_int, [_int, _int, _int, _int, _int]),
     "pynqs_eloc_jrbm_form": (_int, [_i64, _int, _int, _int, _int, _int]),
     "pynqs_eloc_jrbm": (_int, [_vp, _i64, _int, _int, _int, _int, _vp, _vp, _vp, _int, _vp, _vp, _vp]),
+    "pynqs_eloc_jrbm_flip_supported": (_int, [_int, _int, _int, _int, _int]),
+    "pynqs_eloc_jrbm_flip_form": (_int, [_i64, _int, _int, _int, _int, _int]),
+    "pynqs_eloc_jrbm_signed": (_int, [_vp, _i64, _int, _int, _int, _int, _vp, _vp, _vp, _int, _vp, _vp, _vp]),
+    "pynqs_eloc_jrbm_flip": (_int, [_vp, _i64, _int, _int, _int, _int, _vp, _vp, _vp, _vp, _vp, _int, _dbl, _dbl, _vp, _vp, _vp, _vp, _vp]),
     "pynqs_green_jrbm": (_int, [_vp, _i64, _int, _int, _int, _int, _vp, _vp, _vp, _int, _dbl, _vp, _vp, _vp, _vp, _vp]),
     "pynqs_jrbm_forward": (_int, [_vp, _i64, _int, _vp, _vp, _vp, _vp, _int, _vp, _vp]),
     "pynqs_jastrow_grad_workspace": (_i64, [_i64, _int]),

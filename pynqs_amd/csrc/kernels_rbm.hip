@@ -55,6 +55,14 @@
 // argument `jastrow` (nullptr in every other form) and the LDS flag in bit 1 of the chunk count, which is 1 in this form by construction
 // (one workgroup per walker: the row finishes its diagonal in the kernel).  The other instantiations' registers are what they were
 // (DESIGN 4.8).
+//
+// SIGNED (no GREEN form): every column's matrix element times sigma_k = eta_m(x'_k) eta_m(x), eta_m(y) = (-1)^(doubly occupied spatial
+// orbitals of y): the second pass of the spin-flip-projected local energy (vmc/energy/flip.py, _simple_flip; pynqs_eloc_rbm_flip /
+// pynqs_eloc_jrbm_flip below, formula in include/pynqs_amd.h), run on the spin-mirrored table W[h][o ^ 1], a[o ^ 1] (M[i ^ 1][j ^ 1]), whose
+// amplitude is psi(flip y).  Flipping orbital o changes the number of doubly occupied spatial orbitals by the walker's bit at o ^ 1, so
+// sigma_k = (-1)^pi_k with pi_k = XOR_{o in F} occ(o ^ 1) XOR #(spatial orbitals with both spin orbitals in F): two 4-bit masks per lane in
+// the tile epilogue, XORed into the doubles' fermionic parity and applied to the staged singles where they are consumed; x' = x has +1.
+// Every statement of it stands under `if constexpr (SIGNED)`; the other instantiations' registers are what they were.
 #include <string.h>
 
 #include "rbm.h"
@@ -116,7 +124,7 @@ __host__ __device__ inline size_t lds_bytes_rbm(const SDParams &p, const RbmLayo
 //                   windows (two barriers per window).
 enum : int { kRbmReal = 0, kRbmTanh = 1, kRbmPhase = 2 };
 
-template <int LEN, bool WINDOWED, int FLAVOUR, bool GREEN, bool JASTROW = false>
+template <int LEN, bool WINDOWED, int FLAVOUR, bool GREEN, bool JASTROW = false, bool SIGNED = false>
 __global__ __launch_bounds__(1024, 4) void eloc_rbm_kernel(const uint64_t *__restrict__ bra, SDParams p, PlanLayout pl, RbmLayout rl,
                                                           RbmBlocks<kRbmFB> B, uint32_t nchunks_arg, uint32_t hw, const double *__restrict__ plan,
                                                           const double *__restrict__ rbm, double *__restrict__ eloc,
@@ -124,6 +132,7 @@ __global__ __launch_bounds__(1024, 4) void eloc_rbm_kernel(const uint64_t *__res
                                                           uint8_t *__restrict__ clamped, const double *__restrict__ jastrow) {
   static_assert(!GREEN || FLAVOUR != kRbmPhase, "the fixed-node row needs a real-valued amplitude");
   static_assert(!JASTROW || (FLAVOUR == kRbmReal && !WINDOWED), "the Jastrow factor: real flavour, resident form");
+  static_assert(!SIGNED || !GREEN, "the signed sum is the second pass of the spin-flip-projected energy: no row");
   // GREEN and JASTROW together (pynqs_green_jrbm): `green`, `lambda` and `clamped` are the row's, so the Jastrow table comes in `jastrow`
   // and the "pair factors in LDS" flag in bit 1 of `nchunks_arg` -- the row is launched with one workgroup per walker, so the chunk
   // count is the constant 1 in that form.  Every other instantiation reads what it read before.
@@ -474,6 +483,17 @@ __global__ __launch_bounds__(1024, 4) void eloc_rbm_kernel(const uint64_t *__res
           as[i] = cls == 0 ? 1.0 : R.Aq[es[i] & 0xff] * R.Aq[(es[i] >> 8) & 0xff];
         }
       }
+      // SIGNED: sigma_k = (-1)^pi_k, pi_k = XOR over the flipped orbitals o of the walker's bit at the spin partner o ^ 1, XOR the number
+      // of spatial orbitals with both spin orbitals flipped.  An entry's two orbitals have one spin, so only a fast and a slow orbital of
+      // the alpha-beta class can be partners.  Bit i of sgf / sgs: the XOR over fast entry i's / slow entry i's two orbitals.
+      [[maybe_unused]] uint32_t sgf = 0, sgs = 0;
+      if constexpr (SIGNED) {
+#pragma unroll
+        for (int i = 0; i < 4; ++i) {
+          sgf |= (bit_of<LEN>(wk.w, (int)((ef[i] & 0xff) ^ 1u)) ^ bit_of<LEN>(wk.w, (int)(((ef[i] >> 8) & 0xff) ^ 1u))) << i;
+          sgs |= (bit_of<LEN>(wk.w, (int)((es[i] & 0xff) ^ 1u)) ^ bit_of<LEN>(wk.w, (int)(((es[i] >> 8) & 0xff) ^ 1u))) << i;
+        }
+      }
       if constexpr (JASTROW) {
         // exp(4 S_ab x_a x_b) of two flipped orbitals, from the walker's triangle in LDS or from the table; the sign x_a x_b from the
         // walker's bits (hole-hole and particle-particle pairs +, hole-particle pairs -, whichever class and entry they come from).  The
@@ -528,7 +548,8 @@ __global__ __launch_bounds__(1024, 4) void eloc_rbm_kernel(const uint64_t *__res
 #pragma unroll
         for (int i = 0; i < 4; ++i) {
           const uint32_t f = 4 * bf + i;
-          add_column(f < nF, R.hs[1 + min(f, nF - 1)], acc[4 * i] * cf[i], af[i], 1u + f);
+          if constexpr (SIGNED) add_column(f < nF, ((sgf >> i) & 1u) ? -R.hs[1 + min(f, nF - 1)] : R.hs[1 + min(f, nF - 1)], acc[4 * i] * cf[i], af[i], 1u + f);
+          else add_column(f < nF, R.hs[1 + min(f, nF - 1)], acc[4 * i] * cf[i], af[i], 1u + f);
         }
       } else {
         const bool opp = cls == 3;
@@ -552,6 +573,9 @@ __global__ __launch_bounds__(1024, 4) void eloc_rbm_kernel(const uint64_t *__res
             uint32_t par = ((ef[i] ^ es[j]) >> 16) & 1u;  // as plan_dev.h: finish_double
             if (opp) par ^= (uint32_t)(a0 < b1) ^ (uint32_t)(b0 < a1) ^ 1u;
             else par ^= (uint32_t)(a0 < b0) ^ (uint32_t)(a1 < b0) ^ (uint32_t)(a0 < b1) ^ (uint32_t)(a1 < b1);
+            if constexpr (SIGNED)
+              par ^= (((sgf >> i) ^ (sgs >> j)) & 1u) ^ (uint32_t)((a0 ^ 1) == b0) ^ (uint32_t)((a0 ^ 1) == b1) ^ (uint32_t)((a1 ^ 1) == b0) ^
+                     (uint32_t)((a1 ^ 1) == b1);
             const bool ok = 4 * bf + i < nF && 4 * bs + j < nS;
             const double t = (acc[4 * i + j] * cf[i]) * cs[j];
             uint32_t col = 0;
@@ -715,7 +739,7 @@ extern "C" int pynqs_rbm_table_build(const double *weights, const double *hidden
 
 static int eloc_rbm_impl(const uint64_t *bra, int64_t nbatch, int sorb, int nele, int noA, int noB, const void *plan,
                          const void *rbm_table, int nhidden, int flavour, double *eloc, double *psi, double lambda, double *green,
-                         uint8_t *clamped, void *stream) {
+                         uint8_t *clamped, void *stream, bool sgn = false) {  // sgn: the SIGNED form (every column times sigma_k; never with green)
   pynqs::DeviceScope device_scope_(bra);
   if (flavour < PYNQS_RBM_REAL || flavour > PYNQS_RBM_PHASE) return set_error(PYNQS_EINVAL, "unknown RBM flavour");
   if (green && (flavour == PYNQS_RBM_PHASE || !clamped)) return set_error(PYNQS_EINVAL, "the Green's-function row needs a real-valued flavour");
@@ -741,9 +765,15 @@ static int eloc_rbm_impl(const uint64_t *bra, int64_t nbatch, int sorb, int nele
 #define PYNQS_RBM_LAUNCH(W, F, G)                                                                                                            \
   rc = rbm_launch("eloc_rbm", eloc_rbm_kernel<LEN, W, F, G>, grid, threads, lds, st, bra, p, pl, rl, B, nchunks, hw, (const double *)plan, \
                   (const double *)rbm_table, eloc, psi, lambda, green, clamped, (const double *)nullptr)
+#define PYNQS_RBM_LAUNCH_SIGNED(W, F)                                                                                                        \
+  rc = rbm_launch("eloc_rbm_signed", eloc_rbm_kernel<LEN, W, F, false, false, true>, grid, threads, lds, st, bra, p, pl, rl, B, nchunks, hw, \
+                  (const double *)plan, (const double *)rbm_table, eloc, psi, 0.0, (double *)nullptr, (uint8_t *)nullptr, (const double *)nullptr)
 #define PYNQS_RBM_FLAVOURS(W)                                                \
   do {                                                                       \
-    if (green && flavour == PYNQS_RBM_REAL) PYNQS_RBM_LAUNCH(W, kRbmReal, true);  \
+    if (sgn && flavour == PYNQS_RBM_REAL) PYNQS_RBM_LAUNCH_SIGNED(W, kRbmReal);  \
+    else if (sgn && flavour == PYNQS_RBM_TANH) PYNQS_RBM_LAUNCH_SIGNED(W, kRbmTanh);  \
+    else if (sgn) PYNQS_RBM_LAUNCH_SIGNED(W, kRbmPhase);                     \
+    else if (green && flavour == PYNQS_RBM_REAL) PYNQS_RBM_LAUNCH(W, kRbmReal, true);  \
     else if (green) PYNQS_RBM_LAUNCH(W, kRbmTanh, true);                     \
     else if (flavour == PYNQS_RBM_REAL) PYNQS_RBM_LAUNCH(W, kRbmReal, false); \
     else if (flavour == PYNQS_RBM_TANH) PYNQS_RBM_LAUNCH(W, kRbmTanh, false); \
@@ -754,6 +784,7 @@ static int eloc_rbm_impl(const uint64_t *bra, int64_t nbatch, int sorb, int nele
     else PYNQS_RBM_FLAVOURS(false);
   });
 #undef PYNQS_RBM_FLAVOURS
+#undef PYNQS_RBM_LAUNCH_SIGNED
 #undef PYNQS_RBM_LAUNCH
   return rc;
 }
@@ -804,8 +835,8 @@ extern "C" int pynqs_eloc_jrbm_form(int64_t nbatch, int sorb, int nele, int noA,
   return (rbm_chunks(make_rbm_blocks<kRbmFB>(s.p).ntiles, nbatch) > 1 ? 2 : 0) | (jrbm_pairs_in_lds(s) ? 4 : 0);
 }
 
-extern "C" int pynqs_eloc_jrbm(const uint64_t *bra, int64_t nbatch, int sorb, int nele, int noA, int noB, const void *plan,
-                               const void *rbm_table, const void *jastrow_table, int nhidden, double *eloc, double *psi, void *stream) {
+static int eloc_jrbm_impl(const uint64_t *bra, int64_t nbatch, int sorb, int nele, int noA, int noB, const void *plan, const void *rbm_table,
+                          const void *jastrow_table, int nhidden, double *eloc, double *psi, void *stream, bool sgn) {
   pynqs::DeviceScope device_scope_(bra);
   RbmSystem<RbmLayout> sys;
   if (const char *bad = rbm_system(sorb, nele, noA, noB, nhidden, make_rbm_layout, &sys)) return set_error(PYNQS_EINVAL, bad);
@@ -829,9 +860,119 @@ extern "C" int pynqs_eloc_jrbm(const uint64_t *bra, int64_t nbatch, int sorb, in
 #define PYNQS_JRBM_LAUNCH                                                                                                                  \
   rc = rbm_launch("eloc_jrbm", eloc_rbm_kernel<LEN, false, kRbmReal, false, true>, grid, threads, lds, st, bra, p, pl, rl, B, nchunks, hw, \
                   (const double *)plan, (const double *)rbm_table, eloc, psi, pairs_in_lds ? 1.0 : 0.0, jas, (uint8_t *)nullptr, (const double *)nullptr)
-  DISPATCH_LEN(len, { PYNQS_JRBM_LAUNCH; });
+#define PYNQS_JRBM_LAUNCH_SIGNED                                                                                                            \
+  rc = rbm_launch("eloc_jrbm_signed", eloc_rbm_kernel<LEN, false, kRbmReal, false, true, true>, grid, threads, lds, st, bra, p, pl, rl, B, nchunks, \
+                  hw, (const double *)plan, (const double *)rbm_table, eloc, psi, pairs_in_lds ? 1.0 : 0.0, jas, (uint8_t *)nullptr,           \
+                  (const double *)nullptr)
+  DISPATCH_LEN(len, {
+    if (sgn) PYNQS_JRBM_LAUNCH_SIGNED;
+    else PYNQS_JRBM_LAUNCH;
+  });
+#undef PYNQS_JRBM_LAUNCH_SIGNED
 #undef PYNQS_JRBM_LAUNCH
   return rc;
+}
+
+extern "C" int pynqs_eloc_jrbm(const uint64_t *bra, int64_t nbatch, int sorb, int nele, int noA, int noB, const void *plan,
+                               const void *rbm_table, const void *jastrow_table, int nhidden, double *eloc, double *psi, void *stream) {
+  return eloc_jrbm_impl(bra, nbatch, sorb, nele, noA, noB, plan, rbm_table, jastrow_table, nhidden, eloc, psi, stream, false);
+}
+
+// ---- the spin-flip-projected local energy (vmc/energy/flip.py, _simple_flip; formula and mirrored-table convention: include/pynqs_amd.h):
+//   E_proj = [E + eta eta_m(x) R Em] / extra_norm^2,  E: the plain pass, Em: the SIGNED pass on the mirrored table, R = psim(x) / psi(x).
+// One thread per walker; eloc holds E on entry and E_proj on return.  PHASE: (re, im) pairs, R and the product in complex arithmetic.
+namespace pynqs {
+template <bool PHASE>
+__global__ __launch_bounds__(kBlock) void flip_combine_kernel(const uint64_t *__restrict__ bra, int64_t n, int len, double eta, double extra_norm,
+                                                              const double *__restrict__ extra_norm_dev, const double *__restrict__ psi,
+                                                              const double *__restrict__ em, const double *__restrict__ psim,
+                                                              double *__restrict__ eloc) {
+  const int64_t i = (int64_t)blockIdx.x * kBlock + threadIdx.x;
+  if (i >= n) return;
+  uint32_t docc = 0;  // doubly occupied spatial orbitals: bits 2k and 2k + 1 of a word
+  for (int w = 0; w < len; ++w) {
+    const uint64_t v = bra[i * len + w];
+    docc += (uint32_t)__popcll(v & (v >> 1) & 0x5555555555555555ull);
+  }
+  const double nrm = extra_norm_dev ? *extra_norm_dev : extra_norm;
+  const double c = (docc & 1u) ? -eta : eta, n2 = nrm * nrm;
+  if constexpr (PHASE) {
+    const double pr = psi[2 * i], pi = psi[2 * i + 1], qr = psim[2 * i], qi = psim[2 * i + 1], d = pr * pr + pi * pi;
+    const double rr = (qr * pr + qi * pi) / d, ri = (qi * pr - qr * pi) / d;  // R = psim conj(psi) / |psi|^2
+    const double er = em[2 * i], ei = em[2 * i + 1];
+    eloc[2 * i] = (eloc[2 * i] + c * (rr * er - ri * ei)) / n2;
+    eloc[2 * i + 1] = (eloc[2 * i + 1] + c * (rr * ei + ri * er)) / n2;
+  } else {
+    eloc[i] = (eloc[i] + c * ((psim[i] / psi[i]) * em[i])) / n2;
+  }
+}
+}  // namespace pynqs
+
+static int flip_combine(const uint64_t *bra, int64_t nbatch, int sorb, bool phase, double eta, double extra_norm, const double *extra_norm_dev,
+                        const double *psi, const double *work, double *eloc, void *stream) {
+  const int len = (sorb - 1) / 64 + 1;
+  const int64_t k = phase ? 2 : 1;
+  const uint32_t grid = (uint32_t)((nbatch + kBlock - 1) / kBlock);
+  if (phase)
+    hipLaunchKernelGGL(flip_combine_kernel<true>, dim3(grid), dim3(kBlock), 0, (hipStream_t)stream, bra, nbatch, len, eta, extra_norm, extra_norm_dev,
+                       psi, work, work + k * nbatch, eloc);
+  else
+    hipLaunchKernelGGL(flip_combine_kernel<false>, dim3(grid), dim3(kBlock), 0, (hipStream_t)stream, bra, nbatch, len, eta, extra_norm, extra_norm_dev,
+                       psi, work, work + k * nbatch, eloc);
+  return check_launch("flip_combine");
+}
+
+extern "C" int pynqs_eloc_rbm_flip_supported(int sorb, int nele, int noA, int noB, int nhidden) {
+  return pynqs_eloc_rbm_supported(sorb, nele, noA, noB, nhidden);
+}
+
+extern "C" int pynqs_eloc_rbm_flip_form(int64_t nbatch, int sorb, int nele, int noA, int noB, int nhidden) {
+  return pynqs_eloc_rbm_form(nbatch, sorb, nele, noA, noB, nhidden, 0);
+}
+
+extern "C" int pynqs_eloc_rbm_signed(const uint64_t *bra, int64_t nbatch, int sorb, int nele, int noA, int noB, const void *plan,
+                                     const void *rbm_table, int nhidden, int flavour, double *eloc, double *psi, void *stream) {
+  return eloc_rbm_impl(bra, nbatch, sorb, nele, noA, noB, plan, rbm_table, nhidden, flavour, eloc, psi, 0.0, nullptr, nullptr, stream, true);
+}
+
+extern "C" int pynqs_eloc_rbm_flip(const uint64_t *bra, int64_t nbatch, int sorb, int nele, int noA, int noB, const void *plan,
+                                   const void *rbm_table, const void *rbm_table_mirror, int nhidden, int flavour, double eta, double extra_norm,
+                                   const double *extra_norm_dev, double *eloc, double *psi, double *work, void *stream) {
+  if (nbatch > 0 && (!rbm_table_mirror || !psi || !work)) return set_error(PYNQS_EINVAL, "null pointer");
+  if (int rc = eloc_rbm_impl(bra, nbatch, sorb, nele, noA, noB, plan, rbm_table, nhidden, flavour, eloc, psi, 0.0, nullptr, nullptr, stream)) return rc;
+  if (nbatch == 0) return PYNQS_OK;
+  const int64_t k = flavour == PYNQS_RBM_PHASE ? 2 : 1;
+  if (int rc = eloc_rbm_impl(bra, nbatch, sorb, nele, noA, noB, plan, rbm_table_mirror, nhidden, flavour, work, work + k * nbatch, 0.0, nullptr,
+                             nullptr, stream, true))
+    return rc;
+  pynqs::DeviceScope device_scope_(bra);
+  return flip_combine(bra, nbatch, sorb, k == 2, eta, extra_norm, extra_norm_dev, psi, work, eloc, stream);
+}
+
+extern "C" int pynqs_eloc_jrbm_flip_supported(int sorb, int nele, int noA, int noB, int nhidden) {
+  return pynqs_eloc_jrbm_supported(sorb, nele, noA, noB, nhidden);
+}
+
+extern "C" int pynqs_eloc_jrbm_flip_form(int64_t nbatch, int sorb, int nele, int noA, int noB, int nhidden) {
+  return pynqs_eloc_jrbm_form(nbatch, sorb, nele, noA, noB, nhidden);
+}
+
+extern "C" int pynqs_eloc_jrbm_signed(const uint64_t *bra, int64_t nbatch, int sorb, int nele, int noA, int noB, const void *plan,
+                                      const void *rbm_table, const void *jastrow_table, int nhidden, double *eloc, double *psi, void *stream) {
+  return eloc_jrbm_impl(bra, nbatch, sorb, nele, noA, noB, plan, rbm_table, jastrow_table, nhidden, eloc, psi, stream, true);
+}
+
+extern "C" int pynqs_eloc_jrbm_flip(const uint64_t *bra, int64_t nbatch, int sorb, int nele, int noA, int noB, const void *plan,
+                                    const void *rbm_table, const void *jastrow_table, const void *rbm_table_mirror,
+                                    const void *jastrow_table_mirror, int nhidden, double eta, double extra_norm, const double *extra_norm_dev,
+                                    double *eloc, double *psi, double *work, void *stream) {
+  if (nbatch > 0 && (!rbm_table_mirror || !jastrow_table_mirror || !psi || !work)) return set_error(PYNQS_EINVAL, "null pointer");
+  if (int rc = eloc_jrbm_impl(bra, nbatch, sorb, nele, noA, noB, plan, rbm_table, jastrow_table, nhidden, eloc, psi, stream, false)) return rc;
+  if (nbatch == 0) return PYNQS_OK;
+  if (int rc = eloc_jrbm_impl(bra, nbatch, sorb, nele, noA, noB, plan, rbm_table_mirror, jastrow_table_mirror, nhidden, work, work + nbatch, stream, true))
+    return rc;
+  pynqs::DeviceScope device_scope_(bra);
+  return flip_combine(bra, nbatch, sorb, false, eta, extra_norm, extra_norm_dev, psi, work, eloc, stream);
 }
 
 // ---- the fixed-node Green's row with the Jastrow factor (GREEN and JASTROW): pynqs_green_rbm's row for pynqs_eloc_jrbm's amplitude.

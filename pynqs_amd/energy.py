@@ -15,7 +15,8 @@ What differs is where the work happens (all on the MI355X, through pynqs_amd.C_e
     (pynqs_eloc_sample_space[_hash]), or over the TABLE (pynqs_eloc_sample_space_keys: work ~ walkers x keys instead of walkers x ncomb,
     the form for large orbital spaces);
   * SIMPLE with an RBM ansatz (real parameters: rbm_type real / tanh / pRBM; complex parameters; cos) evaluates the amplitude ratios
-    inside the kernel (pynqs_eloc_rbm[_flavour], pynqs_eloc_crbm);
+    inside the kernel (pynqs_eloc_rbm[_flavour], pynqs_eloc_crbm); its spin-flip-projected form, for the real-parameter flavours and the
+    Jastrow-RBM, as two passes of the same kernels and a combine kernel (pynqs_eloc_rbm_flip, pynqs_eloc_jrbm_flip);
   * REDUCE compacts the kept columns on chip (pynqs_reduce_count / _emit, and pynqs_reduce_sample for eps_sample > 0) instead of
     writing the whole (batch, ncomb) comb / Hmat and filtering afterwards; the projected / multi-psi / <S-S+> factors are evaluated on
     the kept records.
@@ -834,15 +835,22 @@ def _eloc_sample_space_fused(c):
 
 
 def _eloc_simple_rbm(c):
-    """SIMPLE with an RBM: amplitude ratios on chip.  None: not such an RBM / `dtype` is not its own / its parameters do not fit the LDS."""
+    """SIMPLE with an RBM: amplitude ratios on chip.  None: not such an RBM / `dtype` is not its own / its parameters do not fit the LDS.
+    use_spin_flip (flip.py, _simple_flip): the real-parameter flavours and the Jastrow-RBM run the plain pass, the signed pass on the
+    spin-mirrored tables and the combine kernel (pynqs_eloc_rbm_flip / pynqs_eloc_jrbm_flip); complex parameters and "cos" decline."""
     x, dtype, system = c.x, c.dtype, c.system
+    flip = c.use_spin_flip
     prm = _real_rbm_params(c.ansatz)
-    cprm = _complex_rbm_params(c.ansatz) if prm is None else None
+    cprm = _complex_rbm_params(c.ansatz) if prm is None and not flip else None
     jprm = _jastrow_rbm_params(c.ansatz) if prm is None and cprm is None else None
     # the phase flavour (pRBM) is complex-valued; the others need a real `dtype` like the module itself
     if (prm is not None and dtype in ((torch.complex128, torch.complex64) if prm[3] == "pRBM" else (torch.double, torch.float32))
             and _rbm_lds_ok(*system, prm[0].size(0))):
         table, run, psi_kw = CX.RBMTable(*prm[:3]), partial(CX.eloc_rbm, rbm_type=prm[3]), {}
+        if flip:   # (the mirrored table belongs to the same parameter state: built wherever the plain one is)
+            mirror = CX.mirrored_rbm_table(*prm[:3])
+            run = lambda x, h1, h2, tab, *sys, **kw: CX.eloc_rbm_flip(x, h1, h2, tab, mirror, *sys, SpinProjection.eta, c.extra_norm,  # noqa: E731
+                                                                      rbm_type=prm[3], **kw)
     # complex parameters (complex running products in the kernel); "cos" is real-valued and rides on the same kernel
     elif (cprm is not None and dtype in ((torch.double, torch.float32) if cprm[4] else (torch.complex128, torch.complex64))
             and N.lib().pynqs_eloc_crbm_supported(*system, cprm[0].size(0))):
@@ -852,6 +860,10 @@ def _eloc_simple_rbm(c):
         jtable = CX.JastrowTable(jprm[3])
         table, psi_kw = CX.RBMTable(*jprm[:3]), {}
         run = lambda x, h1, h2, tab, *sys, **kw: CX.eloc_jrbm(x, h1, h2, tab, jtable, *sys, **kw)  # noqa: E731
+        if flip:
+            mirror, jmirror = CX.mirrored_rbm_table(*jprm[:3]), CX.mirrored_jastrow_table(jprm[3])
+            run = lambda x, h1, h2, tab, *sys, **kw: CX.eloc_jrbm_flip(x, h1, h2, tab, jtable, mirror, jmirror, *sys, SpinProjection.eta,  # noqa: E731
+                                                                       c.extra_norm, **kw)
     else:
         return None
     eloc, psi0 = run(x, *CX.integrals_f64(c.h1e, c.h2e), table, *system, **psi_kw)
@@ -1043,7 +1055,9 @@ def local_energy(
         gpu_ok = FUSED and x.is_cuda and sorb % 2 == 0   # (every fused kernel packs an even number of spin orbitals)
         if use_sample_space and _fast_sample_space_ok(x, h1e, sorb, WF_LUT):
             return _eloc_sample_space_fused(c)
-        simple_rbm = gpu_ok and FUSED_RBM and not reduce_psi and not use_sample_space and WF_LUT is None and plain and h1e.dtype in (torch.float64, torch.float32)
+        # (the spin-flip-projected form too, for the real-parameter RBMs and the Jastrow-RBM: _eloc_simple_rbm declines the others)
+        simple_rbm = (gpu_ok and FUSED_RBM and not reduce_psi and not use_sample_space and WF_LUT is None and not use_multi_psi
+                      and h1e.dtype in (torch.float64, torch.float32))
         out = _eloc_simple_rbm(c) if simple_rbm else None
         if out is not None:
             return out
@@ -1079,6 +1093,12 @@ def auto_nbatch(x, h1e, sorb, nele, noa, nob, ansatz, WF_LUT, dtype, reduce_psi,
         elif (not reduce_psi and not use_sample_space and FUSED_RBM and WF_LUT is None and not (use_multi_psi or use_spin_flip)
               and (_real_rbm_params(ansatz) is not None or _complex_rbm_params(ansatz) is not None)):
             fused = "simple_rbm"
+        elif (not reduce_psi and not use_sample_space and FUSED_RBM and WF_LUT is None and use_spin_flip and not use_multi_psi
+              and h1e.dtype in (torch.float64, torch.float32)
+              and ((_real_rbm_params(ansatz) is not None and _rbm_lds_ok(sorb, nele, noa, nob, _real_rbm_params(ansatz)[0].size(0)))
+                   or (_jastrow_rbm_params(ansatz) is not None
+                       and CX.eloc_jrbm_supported(sorb, nele, noa, nob, _jastrow_rbm_params(ansatz)[0].size(0))))):
+            fused = "simple_rbm"   # (the spin-flip-projected form of the same kernels: nothing of size nbatch x ncomb either)
     dt = dtype if dtype in (torch.double, torch.complex128) else torch.double
     if fused is None:
         return max(1, get_nbatch(sorb, max(n, 1), n_sd, max_memory, alpha, x.device, use_sample_space, dt, fused=None, eps_sample=int(eps_sample)))
