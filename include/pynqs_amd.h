@@ -393,6 +393,16 @@ int pynqs_weighted_moments(const double *x, int is_complex, const double *prob, 
  * what the two calls leave. */
 int pynqs_weighted_moments_finish(const double *x, int is_complex, const double *prob, int64_t n, void *workspace, double inv_world,
                                   double counts, double *out5, void *stream);
+/* Two forms compute these sums, with the same additions in the same order (the same bits in workspace and out5): several workgroups and
+ * a ticket for the last one to finish, or -- for n <= pynqs_moments_onegroup_max() [host], where it is the faster one -- ONE workgroup
+ * that needs neither ticket nor fence.  The two entry points above choose by n; this one takes the form per call (PYNQS_MOMENTS_ONEGROUP
+ * runs up to n = 32768) and is pynqs_weighted_moments for out5 == NULL, pynqs_weighted_moments_finish otherwise. */
+#define PYNQS_MOMENTS_AUTO 0
+#define PYNQS_MOMENTS_BLOCKS 1
+#define PYNQS_MOMENTS_ONEGROUP 2
+int64_t pynqs_moments_onegroup_max(void);
+int pynqs_weighted_moments_form(const double *x, int is_complex, const double *prob, int64_t n, void *workspace, double inv_world,
+                                double counts, double *out5, int form, void *stream);
 
 /* REDUCE method front end: vmc/energy/eloc.py:205-324 with eps_sample == 0 keeps the columns with
  * |<x|H|x'>| >= eps (eloc.py:297-298; column 0 is treated like any other).  Two passes, nothing materialised, no
@@ -535,6 +545,14 @@ int pynqs_reduce_onepass(const uint64_t *bra, int64_t nbatch, int sorb, int nele
 int pynqs_reduce_contract(int64_t nbatch, int sorb, int nele, int noA, int noB, int dtype, int eps_sample,
                           const pynqs_reduce_io *io, const double *psi_unique, const double *psi_table, int psi_is_complex,
                           int divide, double *eloc, double *psi_x, void *stream);
+/* the same with the kernel chosen per call (pynqs_reduce_contract takes PYNQS_CONTRACT_BATCHED): PYNQS_CONTRACT_BATCHED reads a slot's
+ * column first, loads weight and link of live slots only and keeps the loads of several slots per lane in flight; PYNQS_CONTRACT_SERIAL
+ * visits a lane's slots one at a time.  Same additions in the same order: eloc and psi_x are the same bit for bit. */
+#define PYNQS_CONTRACT_BATCHED 0
+#define PYNQS_CONTRACT_SERIAL 1
+int pynqs_reduce_contract_form(int64_t nbatch, int sorb, int nele, int noA, int noB, int dtype, int eps_sample,
+                               const pynqs_reduce_io *io, const double *psi_unique, const double *psi_table, int psi_is_complex,
+                               int divide, double *eloc, double *psi_x, int form, void *stream);
 /* ---- the draw law of the short-row form (pynqs_reduce_onepass where pynqs_reduce_onepass_wants_row_f32 says 1 and io->row_f32 is given:
  * rows of at most 8192 columns, at most 16383 draws, the kept records within the list; pynqs_amd/csrc/reduce_draw.h).  This form's random
  * STREAM is part of the contract: which columns walker i draws, and how often, is a pure function of (seed, *io->seed_dev, i, the row).
@@ -644,6 +662,17 @@ int pynqs_rbm_grad_loss(const uint64_t *onv, int64_t n, int sorb, const double *
                         int eloc_is_complex, const double *e_total, const double *pow, double *grad_weights,
                         double *grad_hidden_bias, double *grad_visible_bias, double *loss, double *loss_copy, void *workspace,
                         void *stream);
+/* the same with the schedule of the first kernel chosen per call (the two entry points above take PYNQS_GRAD_ONEPASS and block 0):
+ *   PYNQS_GRAD_ONEPASS: the theta chains of 64 hidden units at a time run side by side, W of those units staged in LDS where it fits;
+ *   PYNQS_GRAD_TWOPASS: passes of 32 hidden units, W from global memory.  Gradient and loss are the same bit for bit.
+ *   block: threads per workgroup, 256 or 512; 0: 512 unless the environment says PYNQS_RBM_GRAD_BLOCK=256. */
+#define PYNQS_GRAD_ONEPASS 0
+#define PYNQS_GRAD_TWOPASS 1
+int pynqs_rbm_grad_loss_form(const uint64_t *onv, int64_t n, int sorb, const double *weights, const double *hidden_bias,
+                             const double *visible_bias, int nhidden, int flavour, const double *prob, const double *eloc,
+                             int eloc_is_complex, const double *e_total, const double *pow, double *grad_weights,
+                             double *grad_hidden_bias, double *grad_visible_bias, double *loss, double *loss_copy, void *workspace,
+                             int schedule, int block, void *stream);
 
 /* ---- stochastic reconfiguration for RBM amplitudes, matrix-free (kernels_rbm_sr.hip; vmc/grad/sr.py with vmc/grad/_jacobian.py, the
  * reference's `sr=True`, which builds a dense P x P matrix and inverts it) ---------------------------------------------------------------

@@ -74,6 +74,8 @@ SIGNATURES = {
     "pynqs_stats_finish": (_int, [_vp, _dbl, _dbl, _vp, _vp]),
     "pynqs_weighted_moments": (_int, [_vp, _int, _vp, _i64, _vp, _vp]),
     "pynqs_weighted_moments_finish": (_int, [_vp, _int, _vp, _i64, _vp, _dbl, _dbl, _vp, _vp]),
+    "pynqs_moments_onegroup_max": (_i64, []),
+    "pynqs_weighted_moments_form": (_int, [_vp, _int, _vp, _i64, _vp, _dbl, _dbl, _vp, _int, _vp]),
     "pynqs_reduce_tiles": (_i64, [_i64, _int, _int, _int, _int]),
     "pynqs_reduce_count": (_int, [_vp, _i64, _int, _int, _int, _int, _vp, _int, _dbl, _vp, _vp]),
     "pynqs_reduce_count_sums": (_int, [_vp, _i64, _int, _int, _int, _int, _vp, _int, _dbl, _vp, _vp, _vp]),
@@ -110,7 +112,10 @@ SIGNATURES.update({
     "pynqs_rbm_grad_workspace": (_i64, [_i64, _int, _int, _int]),
     "pynqs_rbm_grad": (_int, [_vp, _i64, _int, _vp, _vp, _vp, _int, _int, _vp, _vp, _int, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp]),
     "pynqs_rbm_grad_loss": (_int, [_vp, _i64, _int, _vp, _vp, _vp, _int, _int, _vp, _vp, _int, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp]),
-    "pynqs_reduce_contract": (_int, [_i64, _int, _int, _int, _int, _int, _int, C.POINTER(ReduceIO), _vp, _vp, _int, _int, _vp, _vp, _vp]),    "pynqs_mcmc_rbm_supported": (_int, [_int, _int, _int]),
+    "pynqs_rbm_grad_loss_form": (_int, [_vp, _i64, _int, _vp, _vp, _vp, _int, _int, _vp, _vp, _int, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _int, _int, _vp]),
+    "pynqs_reduce_contract": (_int, [_i64, _int, _int, _int, _int, _int, _int, C.POINTER(ReduceIO), _vp, _vp, _int, _int, _vp, _vp, _vp]),
+    "pynqs_reduce_contract_form": (_int, [_i64, _int, _int, _int, _int, _int, _int, C.POINTER(ReduceIO), _vp, _vp, _int, _int, _vp, _vp, _int, _vp]),
+    "pynqs_mcmc_rbm_supported": (_int, [_int, _int, _int]),
     "pynqs_mcmc_rbm": (_int, [_vp, _i64, _int, _int, _int, _vp, _int, _int, C.c_uint64, C.c_uint64, C.c_uint64, _int, _int, _vp, _vp, _vp, _vp]),
     "pynqs_rbm_sr_workspace": (_i64, [_i64, _int, _int, _int]),
     "pynqs_rbm_sr_prepare": (_int, [_vp, _i64, _int, _vp, _vp, _int, _int, _vp, _vp, _vp, _vp]),

@@ -236,6 +236,88 @@ __global__ __launch_bounds__(kBlock) void moments_kernel(const double *__restric
   }
 }
 
+// The same sums by ONE workgroup of 1024 threads, for n <= kMomentBlocks * kBlock (every thread of the form above then holds at most one
+// element): no ticket, no fence, no read-back of the partial sums.  `blocks` is the grid the form above would take; its blocks x 4 waves
+// are played by the 16 waves here, eight at a time, all loads issued up front.  The 8 x 4 butterflies of such a batch are done together:
+// at distance d a lane keeps one of two vectors and hands the other to its partner (the lane bit picks which), so each step halves the
+// number of vectors and costs one shuffle per remaining vector -- 32 shuffles instead of 192 -- and every value is the one the plain
+// butterfly gives that lane for that vector (x[l] + x[l ^ d], the same two summands).  Then the four wave sums per block in wave order
+// and the blocks' sums in block order, as above: out[0..3], the partial sums behind them and out5 are the same bit for bit.
+constexpr int kMomentsGroupThreads = 1024;
+constexpr int kMomentsBatch = 8;  // virtual waves per wave and batch
+
+template <bool CPLX, bool FINISH>
+__global__ __launch_bounds__(kMomentsGroupThreads) void moments_onegroup_kernel(const double *__restrict__ x, const double *__restrict__ prob,
+                                                                                int64_t n, int blocks, double *__restrict__ out,
+                                                                                double inv_world, double counts, double *__restrict__ out5) {
+  constexpr int NW = kMomentsGroupThreads / 64, VW = kBlock / 64;  // waves here; waves of a block of the form above
+  __shared__ double wsum[kMomentBlocks * VW][4];
+  __shared__ double part[kMomentBlocks][4];
+  const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
+  const int V = blocks * VW;
+  for (int v0 = 0; v0 < V; v0 += NW * kMomentsBatch) {
+    double a[4 * kMomentsBatch];  // vector 4 slot + k
+    double pv[kMomentsBatch], rv[kMomentsBatch], iv[kMomentsBatch];
+#pragma unroll
+    for (int sl = 0; sl < kMomentsBatch; ++sl) {
+      const int64_t i = (int64_t)(v0 + wave * kMomentsBatch + sl) * 64 + lane;  // (v < V or not: i < n decides)
+      const bool in = i < n && v0 + wave * kMomentsBatch + sl < V;
+      pv[sl] = in ? prob[i] : 0.0;
+      rv[sl] = in ? (CPLX ? x[2 * i] : x[i]) : 0.0;
+      iv[sl] = CPLX && in ? x[2 * i + 1] : 0.0;
+    }
+#pragma unroll
+    for (int sl = 0; sl < kMomentsBatch; ++sl) {
+      const int64_t i = (int64_t)(v0 + wave * kMomentsBatch + sl) * 64 + lane;
+      double s[4] = {0.0, 0.0, 0.0, 0.0};
+      if (i < n && v0 + wave * kMomentsBatch + sl < V) {
+        const double p = pv[sl];
+        const double re = rv[sl], im = CPLX ? iv[sl] : 0.0;
+        s[0] += p * re; s[1] += p * im; s[2] += p * (re * re + im * im); s[3] += p;
+      }
+#pragma unroll
+      for (int k = 0; k < 4; ++k) a[4 * sl + k] = s[k];
+    }
+    // distance 32 .. 2: the lane bit picks the vector kept
+#pragma unroll
+    for (int d = 32, m = 4 * kMomentsBatch; m > 1; d >>= 1, m >>= 1) {
+      const bool hi = (lane & d) != 0;
+#pragma unroll
+      for (int j = 0; j < m / 2; ++j) {
+        const double keep = hi ? a[2 * j + 1] : a[2 * j], send = hi ? a[2 * j] : a[2 * j + 1];
+        a[j] = keep + __shfl_xor(send, d);
+      }
+    }
+    static_assert(4 * kMomentsBatch == 32, "five halving steps, then distance 1");
+    a[0] += __shfl_xor(a[0], 1);
+    // this lane's vector: bits (32, 16) of the lane are k, bits (8, 4, 2) the slot
+    const int k = ((lane >> 5) & 1) | (((lane >> 4) & 1) << 1);
+    const int sl = ((lane >> 3) & 1) | (((lane >> 2) & 1) << 1) | (((lane >> 1) & 1) << 2);
+    const int v = v0 + wave * kMomentsBatch + sl;
+    if (!(lane & 1) && v < V) wsum[v][k] = a[0];
+  }
+  __syncthreads();
+  if (tid < blocks * 4) {
+    const int b = tid >> 2, k = tid & 3;
+    double t = 0.0;
+#pragma unroll
+    for (int w = 0; w < VW; ++w) t += wsum[b * VW + w][k];
+    out[4 * (1 + b) + k] = t;
+    part[b][k] = t;
+  }
+  __syncthreads();
+  if (tid < 4) {
+    double t = 0.0;
+    for (int b = 0; b < blocks; ++b) t += part[b][tid];  // block order: reproducible
+    out[tid] = t;
+    if constexpr (FINISH) wsum[0][tid] = t;
+  }
+  if constexpr (FINISH) {
+    __syncthreads();
+    if (tid == 0) stats_finish(&wsum[0][0], inv_world, counts, out5);
+  }
+}
+
 __global__ void stats_finish_kernel(const double *__restrict__ m, double inv_world, double counts, double *__restrict__ out) {
   stats_finish(m, inv_world, counts, out);
 }
@@ -251,18 +333,35 @@ extern "C" int pynqs_stats_finish(const double *moments, double inv_world, doubl
 
 extern "C" int64_t pynqs_moments_workspace(void) { return 8 * 4 * (pynqs::kMomentBlocks + 1) + 8; }
 
+// n up to which the single-workgroup form is taken: all it can hold.  Measured (profiles/backhalf_trace.txt): 5.7 against 10.3 us per call
+// at n = 8192, 9.3 against 16.4 at 16384, 16.3 against 28.7 at 32768 -- it is the faster one wherever it runs.
+constexpr int64_t kMomentsOneGroupMax = (int64_t)kMomentBlocks * kBlock;
+
+extern "C" int64_t pynqs_moments_onegroup_max(void) { return kMomentsOneGroupMax; }
+
 static int weighted_moments_launch(const double *x, int is_complex, const double *prob, int64_t n, void *workspace, bool finish, double inv_world,
-                                   double counts, double *out5, void *stream) {
+                                   double counts, double *out5, int form, void *stream) {
   pynqs::DeviceScope device_scope_(x);
   if (n < 0) return set_error(PYNQS_EINVAL, "bad n");
   if (!workspace || (n > 0 && (!x || !prob))) return set_error(PYNQS_EINVAL, "null pointer");
   if (finish && (!out5 || !(counts > 0.0))) return set_error(PYNQS_EINVAL, "bad arguments");
+  if (form < PYNQS_MOMENTS_AUTO || form > PYNQS_MOMENTS_ONEGROUP || (form == PYNQS_MOMENTS_ONEGROUP && n > (int64_t)kMomentBlocks * kBlock))
+    return set_error(PYNQS_EINVAL, "bad form (the single-workgroup form takes n <= 32768)");
   double *out = (double *)workspace;
   unsigned int *done = (unsigned int *)(out + 4 * (kMomentBlocks + 1));
   int64_t blocks = (n + kBlock - 1) / kBlock;
   if (blocks > kMomentBlocks) blocks = kMomentBlocks;
   if (blocks < 1) blocks = 1;
   hipStream_t st = (hipStream_t)stream;
+  if (form == PYNQS_MOMENTS_ONEGROUP || (form == PYNQS_MOMENTS_AUTO && n <= kMomentsOneGroupMax)) {
+#define PYNQS_MK(C, F)                                                                                                                    \
+  hipLaunchKernelGGL((moments_onegroup_kernel<C, F>), dim3(1), dim3(kMomentsGroupThreads), 0, st, x, prob, n, (int)blocks, out, inv_world, \
+                     counts, out5)
+    if (finish) { if (is_complex) PYNQS_MK(true, true); else PYNQS_MK(false, true); }
+    else { if (is_complex) PYNQS_MK(true, false); else PYNQS_MK(false, false); }
+#undef PYNQS_MK
+    return check_launch("weighted_moments");
+  }
 #define PYNQS_MK(C, F) \
   hipLaunchKernelGGL((moments_kernel<C, F>), dim3((uint32_t)blocks), dim3(kBlock), 0, st, x, prob, n, out, done, inv_world, counts, out5)
   if (finish) { if (is_complex) PYNQS_MK(true, true); else PYNQS_MK(false, true); }
@@ -272,12 +371,18 @@ static int weighted_moments_launch(const double *x, int is_complex, const double
 }
 
 extern "C" int pynqs_weighted_moments(const double *x, int is_complex, const double *prob, int64_t n, void *workspace, void *stream) {
-  return weighted_moments_launch(x, is_complex, prob, n, workspace, false, 1.0, 1.0, nullptr, stream);
+  return weighted_moments_launch(x, is_complex, prob, n, workspace, false, 1.0, 1.0, nullptr, PYNQS_MOMENTS_AUTO, stream);
 }
 
 // pynqs_weighted_moments followed by pynqs_stats_finish in ONE launch (for one rank, where no all-reduce comes between them): the moments
 // land in the workspace as before, out5 gets bit for bit what the two calls give
 extern "C" int pynqs_weighted_moments_finish(const double *x, int is_complex, const double *prob, int64_t n, void *workspace, double inv_world,
                                              double counts, double *out5, void *stream) {
-  return weighted_moments_launch(x, is_complex, prob, n, workspace, true, inv_world, counts, out5, stream);
+  return weighted_moments_launch(x, is_complex, prob, n, workspace, true, inv_world, counts, out5, PYNQS_MOMENTS_AUTO, stream);
+}
+
+// either of the two with the form chosen per call (out5 NULL: the moments alone)
+extern "C" int pynqs_weighted_moments_form(const double *x, int is_complex, const double *prob, int64_t n, void *workspace, double inv_world,
+                                           double counts, double *out5, int form, void *stream) {
+  return weighted_moments_launch(x, is_complex, prob, n, workspace, out5 != nullptr, inv_world, counts, out5, form, stream);
 }

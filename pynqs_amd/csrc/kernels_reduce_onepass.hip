@@ -591,6 +591,126 @@ __global__ __launch_bounds__(kBlock) void reduce_contract_kernel(int64_t nbatch,
   }
 }
 
+// The same contraction with the loads batched (PYNQS_CONTRACT_BATCHED).  The kernel above lasts as long as one wave's chain of ~20 trips
+// of two dependent round trips each (records, then the amplitude through the link), and it loads weight and link of empty slots, too.
+// Here a lane takes its slots l, l + 64, ... U trips at a time: the U columns (loaded one batch ahead), then weight and link of the LIVE
+// slots only, then the de-duplication hop of the slot links, then the U amplitudes -- each stage's loads in flight together -- and adds
+// the U products in slot order with the additions of the kernel above: eloc and psi_x are the same bit for bit, the `bad` rules too.
+#ifndef PYNQS_CONTRACT_BATCH
+#define PYNQS_CONTRACT_BATCH 8  // (4, 8, 16 measured: profiles/backhalf_trace.txt)
+#endif
+constexpr int kContractBatch = PYNQS_CONTRACT_BATCH;
+
+// `ar += w * re` of the kernel above as the compiler contracts it there (one v_fmac_f64 per component, read off its ISA), spelled out
+__device__ __forceinline__ void contract_add(double &ar, double &ai, double w, double re, double im) {
+  ar = fma(w, re, ar);
+  ai = fma(w, im, ai);
+}
+
+template <typename T, bool CPLX, int U>
+__global__ __launch_bounds__(kBlock) void reduce_contract_batched_kernel(int64_t nbatch, uint32_t nchunks, uint32_t fixed, uint32_t cap_d,
+                                                                         uint32_t nsample, const int32_t *__restrict__ rec_col,
+                                                                         const T *__restrict__ rec_w, const int32_t *__restrict__ rec_link,
+                                                                         const int32_t *__restrict__ seg_count, const int32_t *__restrict__ srec_col,
+                                                                         const T *__restrict__ srec_w, const int32_t *__restrict__ srec_link,
+                                                                         const int32_t *__restrict__ dedup_i32, int slot_i32, int row_off, uint32_t ucap,
+                                                                         const double *__restrict__ psi_u, const double *__restrict__ psi_t, int divide,
+                                                                         double *__restrict__ eloc, double *__restrict__ psi_x) {
+  const uint32_t lane = threadIdx.x & 63;
+  const int64_t walker = (int64_t)blockIdx.x * (kBlock / 64) + (threadIdx.x >> 6);
+  if (walker >= nbatch) return;
+  double ar = 0.0, ai = 0.0, xr = 0.0, xi = 0.0;
+  bool bad = false;
+  // count slots at colp / wp / lp: this lane's, in ascending order
+  auto run = [&](const int32_t *__restrict__ colp, const T *__restrict__ wp, const int32_t *__restrict__ lp, uint32_t count) {
+    int32_t coln[U];
+#pragma unroll
+    for (int u = 0; u < U; ++u) {
+      const uint32_t i = lane + 64u * u;
+      coln[u] = i < count ? colp[i] : -1;
+    }
+    for (uint32_t i0 = lane; i0 < count; i0 += 64u * U) {
+      int32_t col[U], link[U];
+      T w[U];
+#pragma unroll
+      for (int u = 0; u < U; ++u) {
+        col[u] = coln[u];
+        const uint32_t i = i0 + 64u * u;  // (col >= 0: i < count)
+        w[u] = col[u] >= 0 ? wp[i] : T(0);
+        link[u] = col[u] >= 0 ? lp[i] : -1;
+      }
+#pragma unroll
+      for (int u = 0; u < U; ++u) {  // the next batch's columns
+        const uint32_t i = i0 + 64u * (U + u);
+        coln[u] = i < count ? colp[i] : -1;
+      }
+      // where the amplitude is: row of psi_u (>= 0), entry of psi_t (tab), or nowhere (at < 0 or at >= ucap: bad)
+      int64_t at[U];
+      bool tab[U];
+#pragma unroll
+      for (int u = 0; u < U; ++u) {
+        const int32_t l = link[u];
+        tab[u] = false;
+        at[u] = -1;
+        if (col[u] >= 0) {
+          if (l >= kDirectLink) at[u] = l - kDirectLink;
+          else if (l >= 0) { if (dedup_i32) at[u] = dedup_i32[(int64_t)l * slot_i32 + row_off]; }  // (no table: every link is direct)
+          else if (l <= -2) { tab[u] = true; at[u] = -2 - (int64_t)l; }
+        }
+      }
+      double re[U], im[U];
+#pragma unroll
+      for (int u = 0; u < U; ++u) {
+        re[u] = 0.0; im[u] = 0.0;
+        if (col[u] >= 0) {
+          if (tab[u]) {
+            if constexpr (CPLX) { re[u] = psi_t[2 * at[u]]; im[u] = psi_t[2 * at[u] + 1]; }
+            else re[u] = psi_t[at[u]];
+          } else if (at[u] >= 0 && (uint64_t)at[u] < (uint64_t)ucap) {
+            if constexpr (CPLX) { re[u] = psi_u[2 * at[u]]; im[u] = psi_u[2 * at[u] + 1]; }
+            else re[u] = psi_u[at[u]];
+          } else {
+            bad = true;
+          }
+        }
+      }
+#pragma unroll
+      for (int u = 0; u < U; ++u) {
+        if (col[u] >= 0) {
+          contract_add(ar, ai, (double)w[u], re[u], im[u]);
+          if (col[u] == 0) { xr = re[u]; xi = im[u]; }
+        }
+      }
+    }
+  };
+  const int64_t stride = (int64_t)fixed + cap_d;
+  for (uint32_t c = 0; c < nchunks; ++c) {
+    const int64_t seg = walker * nchunks + c, base = seg * stride;
+    const uint32_t kept = (uint32_t)seg_count[seg];
+    if (kept > cap_d) bad = true;
+    run(rec_col + base, rec_w + base, rec_link + base, fixed + min(kept, cap_d));
+  }
+  if (nsample) run(srec_col + walker * nsample, srec_w + walker * nsample, srec_link + walker * nsample, nsample);
+#pragma unroll
+  for (int d = 32; d > 0; d >>= 1) {
+    ar += __shfl_xor(ar, d); ai += __shfl_xor(ai, d);
+    xr += __shfl_xor(xr, d); xi += __shfl_xor(xi, d);  // (exactly one lane holds a non-zero psi(x))
+  }
+  const bool anybad = __ballot(bad) != 0;
+  if (lane == 0) {
+    if (anybad) { ar = ai = __builtin_nan(""); }
+    if constexpr (CPLX) {
+      if (divide) scaled_cdiv(ar, ai, xr, xi, ar, ai);
+      eloc[2 * walker] = ar;
+      eloc[2 * walker + 1] = ai;
+      psi_x[2 * walker] = xr; psi_x[2 * walker + 1] = xi;
+    } else {
+      eloc[walker] = divide ? ar / xr : ar;
+      psi_x[walker] = xr;
+    }
+  }
+}
+
 // the prologue of pynqs_reduce_onepass as ONE launch: the de-duplication table to "empty" (all bits set: n16 16-byte stores, grid-stride) and
 // the four counter words to 0 -- instead of two memsets
 __global__ __launch_bounds__(kBlock) void reduce_clear_kernel(uint4 *__restrict__ table, size_t n16, uint32_t *__restrict__ counters) {
@@ -872,14 +992,15 @@ extern "C" int pynqs_reduce_onepass(const uint64_t *bra, int64_t nbatch, int sor
   return check_launch("reduce_onepass");
 }
 
-extern "C" int pynqs_reduce_contract(int64_t nbatch, int sorb, int nele, int noA, int noB, int dtype, int eps_sample,
-                                     const pynqs_reduce_io *io, const double *psi_unique, const double *psi_table, int psi_is_complex,
-                                     int divide, double *eloc, double *psi_x, void *stream) {
+extern "C" int pynqs_reduce_contract_form(int64_t nbatch, int sorb, int nele, int noA, int noB, int dtype, int eps_sample,
+                                          const pynqs_reduce_io *io, const double *psi_unique, const double *psi_table, int psi_is_complex,
+                                          int divide, double *eloc, double *psi_x, int form, void *stream) {
   pynqs::DeviceScope device_scope_(eloc);
   SDParams p;
   if (!make_sd_params(sorb, nele, noA, noB, &p)) return set_error(PYNQS_EINVAL, "bad sorb/noA/noB");
   if (nbatch < 0 || nbatch > 0x7fffffffll || (dtype != PYNQS_F32 && dtype != PYNQS_F64) || eps_sample < 0 || eps_sample > 65535)
     return set_error(PYNQS_EINVAL, "bad nbatch/dtype/eps_sample");
+  if (form != PYNQS_CONTRACT_BATCHED && form != PYNQS_CONTRACT_SERIAL) return set_error(PYNQS_EINVAL, "bad form");
   if (nbatch == 0) return PYNQS_OK;
   if (!io || !io->rec_col || !io->rec_w || !io->rec_link || !io->seg_count || !psi_unique || !eloc || !psi_x ||
       (eps_sample > 0 && (!io->srec_col || !io->srec_w || !io->srec_link)) || (io->lut_table && !psi_table))
@@ -889,15 +1010,28 @@ extern "C" int pynqs_reduce_contract(int64_t nbatch, int sorb, int nele, int noA
   const int len = (sorb - 1) / 64 + 1;
   hipStream_t st = (hipStream_t)stream;
   const uint32_t grid = (uint32_t)((nbatch + kBlock / 64 - 1) / (kBlock / 64));
-#define PYNQS_CT_LAUNCH(TT, CX)                                                                                                          \
-  hipLaunchKernelGGL((reduce_contract_kernel<TT, CX>), dim3(grid), dim3(kBlock), 0, st, nbatch, nchunks, fixed, (uint32_t)io->cap_doubles, \
-                     (uint32_t)eps_sample, io->rec_col, (const TT *)io->rec_w, io->rec_link, io->seg_count, io->srec_col,                \
-                     (const TT *)io->srec_w, io->srec_link, (const int32_t *)io->dedup_table, dedup_slot_words(len) * 2,                 \
-                     dedup_row_offset(len), (uint32_t)io->cap_unique, psi_unique, psi_table, divide, eloc, psi_x)
+#define PYNQS_CT_ARGS(TT)                                                                                                           \
+  dim3(grid), dim3(kBlock), 0, st, nbatch, nchunks, fixed, (uint32_t)io->cap_doubles, (uint32_t)eps_sample, io->rec_col,            \
+      (const TT *)io->rec_w, io->rec_link, io->seg_count, io->srec_col, (const TT *)io->srec_w, io->srec_link,                      \
+      (const int32_t *)io->dedup_table, dedup_slot_words(len) * 2, dedup_row_offset(len), (uint32_t)io->cap_unique, psi_unique,     \
+      psi_table, divide, eloc, psi_x
+#define PYNQS_CT_LAUNCH(TT, CX)                                                                             \
+  do {                                                                                                      \
+    if (form == PYNQS_CONTRACT_SERIAL) hipLaunchKernelGGL((reduce_contract_kernel<TT, CX>), PYNQS_CT_ARGS(TT)); \
+    else hipLaunchKernelGGL((reduce_contract_batched_kernel<TT, CX, kContractBatch>), PYNQS_CT_ARGS(TT));   \
+  } while (0)
   if (dtype == PYNQS_F64) { if (psi_is_complex) PYNQS_CT_LAUNCH(double, true); else PYNQS_CT_LAUNCH(double, false); }
   else { if (psi_is_complex) PYNQS_CT_LAUNCH(float, true); else PYNQS_CT_LAUNCH(float, false); }
 #undef PYNQS_CT_LAUNCH
+#undef PYNQS_CT_ARGS
   return check_launch("reduce_contract");
+}
+
+extern "C" int pynqs_reduce_contract(int64_t nbatch, int sorb, int nele, int noA, int noB, int dtype, int eps_sample,
+                                     const pynqs_reduce_io *io, const double *psi_unique, const double *psi_table, int psi_is_complex,
+                                     int divide, double *eloc, double *psi_x, void *stream) {
+  return pynqs_reduce_contract_form(nbatch, sorb, nele, noA, noB, dtype, eps_sample, io, psi_unique, psi_table, psi_is_complex, divide, eloc,
+                                    psi_x, PYNQS_CONTRACT_BATCHED, stream);
 }
 
 #ifdef PYNQS_OP_STAMPS

@@ -195,6 +195,8 @@ class FusedRbmGrad:
         self.loss = self.flat[o:o + 1]
         self.work = None
         self.events = None
+        # pynqs_rbm_grad_loss_form's schedule (0: one pass over 64 hidden units at a time, 1: passes of 32) and workgroup size (0: default)
+        self.schedule, self.block = 0, 0
 
     @property
     def params(self):
@@ -232,11 +234,12 @@ class FusedRbmGrad:
         # one rank: the kernel leaves the loss a second time in a fresh tensor for the caller (torch.empty launches nothing; a clone of
         # self.loss would be a copy launch)
         loss_out = torch.empty(1, dtype=torch.float64, device=dev) if ws == 1 else None
-        N.check(N.lib().pynqs_rbm_grad_loss(onv.contiguous().data_ptr(), n, self.sorb, W.data_ptr(), hb.data_ptr(), vb.data_ptr(), self.H,
-                                            self.flavour, prob.data_ptr(), el.data_ptr(), int(cplx), et.data_ptr(),
-                                            pw.data_ptr() if pw is not None else None, gw.data_ptr(), ghb.data_ptr(), gvb.data_ptr(),
-                                            self.loss.data_ptr(), loss_out.data_ptr() if loss_out is not None else None, self.work.data_ptr(),
-                                            torch.cuda.current_stream(dev).cuda_stream), "pynqs_rbm_grad_loss")
+        N.check(N.lib().pynqs_rbm_grad_loss_form(onv.contiguous().data_ptr(), n, self.sorb, W.data_ptr(), hb.data_ptr(), vb.data_ptr(), self.H,
+                                                 self.flavour, prob.data_ptr(), el.data_ptr(), int(cplx), et.data_ptr(),
+                                                 pw.data_ptr() if pw is not None else None, gw.data_ptr(), ghb.data_ptr(), gvb.data_ptr(),
+                                                 self.loss.data_ptr(), loss_out.data_ptr() if loss_out is not None else None,
+                                                 self.work.data_ptr(), self.schedule, self.block,
+                                                 torch.cuda.current_stream(dev).cuda_stream), "pynqs_rbm_grad_loss_form")
         ev = None
         if self.events is not None:
             ev = [torch.cuda.Event(enable_timing=True) for _ in range(2)]

@@ -196,9 +196,10 @@ class ReduceFrontEnd:
                 "pynqs_reduce_onepass")
 
     def contract(self, values_unique: Tensor, values_table: Optional[Tensor] = None, divide: bool = True,
-                 rec_w: Optional[Tensor] = None, srec_w: Optional[Tensor] = None) -> Tuple[Tensor, Tensor]:
+                 rec_w: Optional[Tensor] = None, srec_w: Optional[Tensor] = None, form: int = 0) -> Tuple[Tensor, Tensor]:
         """(sum_records w A(x') [/ A(x)], A(x)) per walker; A = `values_unique` on the distinct rows, `values_table` on the
-        wave-function table's positions.  rec_w / srec_w replace the records' weights (same slot layout)."""
+        wave-function table's positions.  rec_w / srec_w replace the records' weights (same slot layout).  form: the kernel,
+        pynqs_reduce_contract_form's (0: batched loads, 1: a slot at a time; the same bits)."""
         cplx = values_unique.is_complex()
         vt = torch.complex128 if cplx else torch.float64
         vu = values_unique.to(vt).contiguous()
@@ -211,9 +212,9 @@ class ReduceFrontEnd:
         ax = torch.empty(self.n, dtype=vt, device=self.device)
         code = N.PYNQS_F64 if (rec_w if rec_w is not None else self.rec_w).dtype == torch.float64 else N.PYNQS_F32
         st = torch.cuda.current_stream(self.device).cuda_stream
-        N.check(N.lib().pynqs_reduce_contract(self.n, self.sorb, self.nele, self.noa, self.nob, code, self.eps_sample, C.byref(io),
-                                              vu.data_ptr(), tb.data_ptr() if tb is not None else None, int(cplx), int(divide),
-                                              out.data_ptr(), ax.data_ptr(), st), "pynqs_reduce_contract")
+        N.check(N.lib().pynqs_reduce_contract_form(self.n, self.sorb, self.nele, self.noa, self.nob, code, self.eps_sample, C.byref(io),
+                                                   vu.data_ptr(), tb.data_ptr() if tb is not None else None, int(cplx), int(divide),
+                                                   out.data_ptr(), ax.data_ptr(), int(form), st), "pynqs_reduce_contract_form")
         return out, ax
 
     # ---- what came back -------------------------------------------------------------------------------------------------
