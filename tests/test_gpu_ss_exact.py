@@ -225,7 +225,8 @@ def _onv(bits: np.ndarray, sorb: int) -> np.ndarray:
 class Device:
     """A case on the GPU: walkers, plan, the keys sorted (with their hash table) and shuffled (with their block index)."""
 
-    def __init__(self, name: str, table: str) -> None:
+    def __init__(self, name: str, table: str, key_bits=None) -> None:
+        """key_bits: the keys (0/1 [nk, sorb]) of a table that table_keys does not construct (tests/test_gpu_key_tables.py)"""
         from pynqs_amd import C_extension as cx, public_function as pf
 
         s = SHAPES[name]
@@ -234,7 +235,7 @@ class Device:
         self.h1, self.h2 = _dev(h1), _dev(h2)
         self.plan = cx.plan_for(self.h1, self.h2, s.sorb, dev)
         self.x = _dev(_onv(walkers(name), s.sorb))
-        keys = _dev(_onv(table_keys(name, table), s.sorb))
+        keys = _dev(_onv(table_keys(name, table) if key_bits is None else key_bits, s.sorb))
         self.nk = keys.size(0)
         self.lut = pf.WavefunctionLUT(keys, torch.zeros(self.nk, dtype=torch.float64, device=dev), s.sorb, device=dev)
         assert self.lut.hashtable is not None
