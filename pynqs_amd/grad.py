@@ -64,6 +64,14 @@ def grad(nqs: nn.Module, states: Tensor, state_prob: Tensor, eloc: Tensor, e_tot
     return all_reduce_packed([loss_sum], get_world_size())[0]
 
 
+def _scalar(e_total) -> Tensor:
+    """<E> as a tensor.  A Python number keeps its double precision whatever the default dtype is: torch.as_tensor(-100.3) alone is
+    float32 under torch's own default, and <E> rounded to 4e-6 biases every f_n = p_n (E_n - <E> c_n)."""
+    if isinstance(e_total, Tensor):
+        return e_total
+    return torch.as_tensor(e_total, dtype=torch.complex128 if isinstance(e_total, complex) else torch.float64)
+
+
 class GraphedGrad:
     """The same estimator as grad() with the forward + backward of ONE fixed-shape batch captured in a HIP graph.
 
@@ -133,7 +141,7 @@ class GraphedGrad:
         self.states.copy_(states)
         self.prob.copy_(state_prob.real if state_prob.is_complex() else state_prob)
         self.eloc.copy_(eloc)
-        self.e_total.copy_((e_total if isinstance(e_total, Tensor) else torch.as_tensor(e_total)).reshape(()))
+        self.e_total.copy_(_scalar(e_total).reshape(()))
         if self.pow is not None:
             self.pow.copy_(extra_psi_pow)
         self.graph.replay()
@@ -216,7 +224,7 @@ class FusedRbmGrad:
         cplx = eloc.is_complex()
         prob = (state_prob.real if state_prob.is_complex() else state_prob).to(torch.float64).contiguous()
         el = eloc.to(torch.complex128 if cplx else torch.float64).contiguous()
-        et = (e_total if isinstance(e_total, Tensor) else torch.as_tensor(e_total)).to(device=dev, dtype=el.dtype).reshape(1).contiguous()
+        et = _scalar(e_total).to(device=dev, dtype=el.dtype).reshape(1).contiguous()
         pw = None
         if isinstance(extra_psi_pow, Tensor):
             if extra_psi_pow.is_complex():
@@ -312,7 +320,7 @@ class FusedJastrowRbmGrad:
             raise ValueError("FusedJastrowRbmGrad: the amplitude is real: a real local energy")
         prob = (state_prob.real if state_prob.is_complex() else state_prob).to(torch.float64).contiguous()
         el = eloc.to(torch.float64).contiguous()
-        et = (e_total if isinstance(e_total, Tensor) else torch.as_tensor(e_total)).to(device=dev, dtype=torch.float64).reshape(1).contiguous()
+        et = _scalar(e_total).to(device=dev, dtype=torch.float64).reshape(1).contiguous()
         pw = None
         if isinstance(extra_psi_pow, Tensor):
             if extra_psi_pow.is_complex():

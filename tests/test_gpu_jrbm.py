@@ -42,6 +42,7 @@ CASES = (
 ROUTE_CASE = CASES[-1]          # through energy.local_energy, with <S-S+> (the shipped S-S+ integrals are Fe2S2's)
 FALLBACK_CASE = CASES[4]        # 12, 3 + 3, fe2s2 x j-asym: the module route
 FORWARD_RANDOM = (66, 40, 300, "fe2s2", "j-asym")  # sorb, H, determinants, regimes
+FORWARD_SHAPES = [FORWARD_RANDOM[:3], (130, 9, 257), (192, 8, 65)]  # sorb, H, determinants: two words, three words, the largest sorb
 GRAD_CASES = [(12, 20, 64, "fe2s2", "j-asym"), (40, 80, 32, "fe2s2", "j-asym")]  # sorb, H, n, regimes
 
 # seeds of rbm_exact.regime_params / jrbm_exact.jastrow_params where seed 0 fails a condition of tests/test_jrbm_exact.py (on the reference
@@ -148,10 +149,11 @@ def test_pair_factors_read_from_the_table_meet_the_same_bound(case, monkeypatch)
     assert bool((re_ <= 1.0).all()) and bool((rp <= 1.0).all()), msg
 
 
-def test_forward_on_random_determinants_of_two_words():
+@pytest.mark.parametrize("sorb,H,n", FORWARD_SHAPES)
+def test_forward_on_random_determinants_of_two_and_three_words(sorb, H, n):
     from pynqs_amd import C_extension as cx
 
-    sorb, H, n, regime, jreg = FORWARD_RANDOM
+    regime, jreg = FORWARD_RANDOM[3:]
     rbm, M = params(sorb, H, regime, jreg)
     words = R.rand_words(n, sorb, seed=5)
     ex = J.exact_ld(rbm, M, R.pm1(words, sorb))

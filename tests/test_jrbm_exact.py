@@ -159,9 +159,11 @@ def test_gpu_cases_are_finite_well_conditioned_and_cannot_pass_without_the_jastr
     homes = {(T.pairs_in_lds(c), c.sorb) for c in T.CASES}
     assert {(True, 12), (True, 40), (True, 66), (False, 130)} <= homes, homes
     # the other references of the GPU tests: finite amplitudes
-    sorb, H, n, regime, jreg = T.FORWARD_RANDOM
-    rbm, M = T.params(sorb, H, regime, jreg)
-    assert float(np.abs(J.exact_ld(rbm, M, R.pm1(R.rand_words(n, sorb, seed=5), sorb)).re).max()) <= R.LN_MAX
+    regime, jreg = T.FORWARD_RANDOM[3:]
+    assert T.FORWARD_SHAPES[0] == T.FORWARD_RANDOM[:3] and {(s - 1) // 64 + 1 for s, _, _ in T.FORWARD_SHAPES} == {2, 3}
+    for sorb, H, n in T.FORWARD_SHAPES:
+        rbm, M = T.params(sorb, H, regime, jreg)
+        assert float(np.abs(J.exact_ld(rbm, M, R.pm1(R.rand_words(n, sorb, seed=5), sorb)).re).max()) <= R.LN_MAX, (sorb, H, n)
     dt = time.time() - t0
     print(f"references of tests/test_gpu_jrbm.py: {dt:.1f} s")
     assert dt < 120.0
