@@ -9,7 +9,8 @@ pynqs_reduce_tiles over a grid of systems, table sizes and batch sizes.  No GPU 
                          nothing else); tests/test_host_logic.py::test_ss_launch_decisions_are_unchanged compares every value, with
                          no tolerance.
 
-The grid holds every (sorb, noA, noB, nkeys) of tests/test_gpu_ss_exact.py (SHAPES x its tables), of
+The grid holds every (sorb, noA, noB, nkeys) of tests/test_gpu_ss_exact.py (SHAPES x its tables, but for the two many-electron shapes
+added later, whose values are held to tests/ss_exact.py instead), of
 tests/test_gpu_energy.py::test_sample_space_kernel_filter_levels (nominal and actual table sizes) and of the benchmark's SAMPLE_SPACE
 workloads (Fe2S2 with 18 496 keys; sorb 56, 120, 184 with 65 536), and the sizes around the LDS filter's limit of 2^18 keys.
 

@@ -35,7 +35,7 @@ def _oracle_rows(occ, sorb, noA, noB, h1, h2):
 
 
 @pytest.mark.parametrize("sorb,noA,noB,ints", [(12, 3, 3, "syn"), (12, 2, 4, "syn"), (4, 1, 0, "syn"), (2, 1, 1, "syn"), (66, 3, 4, "syn"),
-                                               (130, 3, 2, "syn"), (40, 15, 15, "fe2s2")])
+                                               (130, 3, 2, "syn"), (40, 15, 15, "fe2s2"), (40, 17, 16, "syn"), (72, 33, 32, "syn")])
 def test_matrix_elements_match_the_oracle_column_by_column(sorb, noA, noB, ints):
     h1, h2 = T.integrals(ints, sorb)
     occ = rand_occ(2, sorb, noA, noB, seed=3)
@@ -153,6 +153,15 @@ def test_gpu_cases_are_finite_visible_and_take_the_form_they_name():
     for k in ("tanh", "pRBM"):
         assert {r for kk, r in regimes_reached if kk == k} >= {"small", "alt30", "chunk-50", "cross"}, k
     assert words >= {("rbm", 1), ("rbm", 2), ("rbm", 3), ("crbm", 1), ("crbm", 2), ("green", 1), ("green", 2)}
+    # beyond 30 electrons: both kernels at 33 electrons on one word and at 65 on two (fast_diag's second round of lanes), in a regime of
+    # small parameters and in one with saturated hidden units; the library serves these shapes with its fused kernels
+    from pynqs_amd import _native as N
+
+    many = {(c.kernel, c.noA + c.noB, (c.sorb - 1) // 64 + 1, c.regime) for c in T.MANY_ELECTRON}
+    assert many == {(k, ne, w, r) for k in ("rbm", "crbm") for ne, w in ((33, 1), (65, 2)) for r in ("small", "chunk-50")}
+    for c in T.MANY_ELECTRON:
+        assert c.H == 20 and c.n == 2 and len({w.st.occ.tobytes() for w in T.reference(c).walkers}) == 2
+        assert getattr(N.lib(), f"pynqs_eloc_{c.kernel}_supported")(c.sorb, c.noA + c.noB, c.noA, c.noB, c.H) == 1
 
 
 def test_greens_rows_have_a_margin_on_every_decision():

@@ -51,7 +51,13 @@ ELOC_CASES = (
         Case("crbm", "complex", 16, 5, 3, 24, 4, "fe2s2", "syn", R1), Case("crbm", "complex", 16, 5, 3, 24, 4, "imb1000", "syn", R1),
         Case("crbm", "complex", 66, 3, 4, 40, 2, "chunk-50", "syn", RC), Case("crbm", "complex", 66, 3, 4, 40, 2, "cross", "syn", RC),
         Case("crbm", "complex", 66, 3, 4, 160, 2, "fe2s2", "syn", WC),  # windows by itself: 67 x 161 complex rows are 169 KiB
-        Case("crbm", "cos", 12, 3, 3, 20, 4, "small", "syn", R1)])
+        Case("crbm", "cos", 12, 3, 3, 20, 4, "small", "syn", R1)] +
+    # beyond the 30 electrons of Fe2S2: 33 on one word (the order-free fast_single walks 33 terms, fast_diag one lane per electron) and 65
+    # on two (fast_diag's lanes come round a second time); the form is what pynqs_eloc_rbm_form / _crbm_form give these shapes
+    [Case("rbm", "real", 40, 17, 16, 20, 2, reg, "syn", R1) for reg in ("small", "chunk-50")] +
+    [Case("crbm", "complex", 40, 17, 16, 20, 2, reg, "syn", RC) for reg in ("small", "chunk-50")] +
+    [Case(k, kind, 72, 33, 32, 20, 2, reg, "syn", RC) for k, kind in (("rbm", "real"), ("crbm", "complex")) for reg in ("small", "chunk-50")])
+MANY_ELECTRON = [c for c in ELOC_CASES if c.noA + c.noB > 30]
 # (kind "cos": prod_h cos(theta_h) with the real parameters of the regime, through the complex kernel and the complex reference with (i W, i b))
 
 # the complex kernel with a forced window of 6 hidden units: a window boundary INSIDE the saturated chunk of eight (the real kernel's
@@ -243,6 +249,10 @@ def _check(c: Case, what: str, e, p):
 @pytest.mark.parametrize("case", ELOC_CASES, ids=case_id)
 def test_local_energy_meets_the_rounding_bound(case):
     assert form_of(case) == case.form
+    if case in MANY_ELECTRON:   # the fused kernel serves the shape: the energy layer would not fall back to the generic path for it
+        from pynqs_amd import _native as N
+
+        assert getattr(N.lib(), f"pynqs_eloc_{case.kernel}_supported")(case.sorb, case.noA + case.noB, case.noA, case.noB, case.H) == 1
     _check(case, "eloc", *run_kernel(case, reference(case)))
 
 

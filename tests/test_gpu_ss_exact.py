@@ -34,7 +34,11 @@ SHAPES = {s.name: s for s in (
     Shape("s12one", 12, 3, 2, 1, "syn"),       # n = 1
     Shape("s66", 66, 3, 4, 3, "syn"),          # two words, flipped orbitals on both sides of bit 64
     Shape("s130", 130, 3, 2, 2, "syn"),        # three words
-    Shape("fe2s2", 40, 15, 15, 4, "fe2s2"))}   # plan_chunks gives several chunks per walker: atomics and the separate divide kernel
+    Shape("fe2s2", 40, 15, 15, 4, "fe2s2"),    # plan_chunks gives several chunks per walker: atomics and the separate divide kernel
+    # beyond the 30 electrons of Fe2S2 (the order-free sums fast_diag / fast_single and the key-major kernel's diagonal() under every
+    # entry point): 33 electrons on one word, and 65 on two, where fast_diag's 64 lanes come round a second time
+    Shape("s40e33", 40, 17, 16, 2, "syn"),
+    Shape("s72e65", 72, 33, 32, 2, "syn"))}
 # tables: "all": every walker, every connected determinant and their spin-flip partners (for unequal spins those lie in the other sector:
 # the plain sums must pass them over, the flip passes find them); "half": the walkers and a random half of the others; "walkers":
 # the walkers only; "far": the walkers and keys that connect to nothing; "one": one key, the first walker; "absent2": "all" without the
@@ -42,7 +46,7 @@ SHAPES = {s.name: s for s in (
 # nchunks > 1 there.
 CASES = [("s12", t) for t in ("all", "half", "walkers", "one", "absent2")] + [("s12one", "all"), ("s12one", "walkers")] + \
         [("s66", t) for t in ("all", "half", "far", "absent2")] + [("s130", "all"), ("s130", "half")] + \
-        [("fe2s2", t) for t in ("all", "half", "absent2")]
+        [("fe2s2", t) for t in ("all", "half", "absent2")] + [(name, t) for name in ("s40e33", "s72e65") for t in ("all", "half")]
 VALUES = ("real", "complex", "real-spread", "complex-spread")
 # entry point, flip pass, keys sorted (binary search / hash table) or shuffled (key-major), adds in a fixed order
 Form = namedtuple("Form", "name entry flip shuffled fixed")

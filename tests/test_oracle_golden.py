@@ -143,3 +143,25 @@ def test_eloc_end_to_end_against_reference_python(fe2s2):
     np.testing.assert_allclose(p0, d["psi_sample_space"], rtol=1e-14)
     e, p0 = O.eloc_sample_space(d["x"], f["h1e"], f["h2e"], 40, 30, 15, 15, keys, d["psi_lut_c"][order])
     np.testing.assert_allclose(e, d["eloc_sample_space_c"], rtol=0, atol=1e-8)
+
+
+def test_many_electron_shapes():
+    """32 to 40 electrons on one word -- all that the reference as shipped accepts above the 30 of Fe2S2 (tests/golden/
+    make_golden_many_electron.py): every row's hash of comb and of Hmat, float64 and float32, and 64 sampled columns."""
+    import many_electron_cases as M
+
+    d = golden("many_electron.npz")
+    assert [(c.sorb, c.noA, c.noB) for c in M.GOLDEN] == [(40, 16, 16), (40, 17, 16), (40, 20, 18), (40, 20, 20)]
+    for c in M.GOLDEN:
+        key, nele = M.case_id(c), c.noA + c.noB
+        h1, h2 = M.integrals(c.sorb)
+        onv = O.pm01_to_onv(M.occupations(c), c.sorb)
+        assert np.array_equal(onv, d[key + "_onv"]), key
+        ranks = d[key + "_ranks"]
+        comb, hm = O.comb_hij_fused(onv, h1, h2, c.sorb, nele, c.noA, c.noB)
+        assert comb.shape[:2] == (c.n, M.ncomb(c))
+        assert [sha(r) for r in comb] == d[key + "_comb_sha"].tolist() and [sha(r) for r in hm] == d[key + "_hmat_sha"].tolist(), key
+        assert np.array_equal(comb[:, ranks], d[key + "_comb"]) and np.array_equal(hm[:, ranks], d[key + "_hmat"]), key
+        _, hm32 = O.comb_hij_fused(onv, h1.astype(np.float32), h2.astype(np.float32), c.sorb, nele, c.noA, c.noB)
+        assert [sha(r) for r in hm32] == d[key + "_hmat_f32_sha"].tolist() and np.array_equal(hm32[:, ranks], d[key + "_hmat_f32"]), key
+        assert np.array_equal(O.hij(onv, comb, h1, h2, c.sorb, nele), hm), key

@@ -36,7 +36,8 @@ def _oracle_inputs(name, table, values):
 
 
 @pytest.mark.parametrize("values", ["real", "complex"])
-@pytest.mark.parametrize("name,table", [("s12", "half"), ("s12", "absent2"), ("s66", "half"), ("s130", "half"), ("fe2s2", "half")])
+@pytest.mark.parametrize("name,table", [("s12", "half"), ("s12", "absent2"), ("s66", "half"), ("s130", "half"), ("fe2s2", "half"),
+                                         ("s40e33", "half"), ("s72e65", "half")])
 def test_yardstick_matches_the_oracle_at_scale_one(name, table, values):
     O, s, h1, h2, bra, keys, wf = _oracle_inputs(name, table, values)
     e, p0 = O.eloc_sample_space(bra, h1, h2, s.sorb, s.noA + s.noB, s.noA, s.noB, keys, wf)
@@ -121,6 +122,24 @@ def test_two_word_walkers_cross_bit_64_and_large_tables_stream_in_chunks():
     assert chunks["s12"] == chunks["s12one"] == 1 and min(chunks["fe2s2"], chunks["s66"], chunks["s130"]) > 1, chunks
     far = T.table_keys("s66", "far")[3:]
     assert all((np.bitwise_xor(r[None, :], occ).sum(1) >= 6).all() for r in far)
+
+
+def test_many_electron_shapes_reach_the_second_round_of_the_diagonals_lanes():
+    """33 electrons on one word, 65 on two (fast_diag strides its 64 lanes over the electrons: 65 is the first count with a second round);
+    two distinct walkers each, the tables "all" and "half", every amplitude set; the diagonal is a sum of nele (nele + 1) / 2 terms and
+    each single one of nele, which is what the bound's t_k counts"""
+    for name, sorb, nele in (("s40e33", 40, 33), ("s72e65", 72, 65)):
+        s = T.SHAPES[name]
+        assert (s.sorb, s.noA + s.noB, s.n, s.ints) == (sorb, nele, 2, "syn") and {t for n, t in T.CASES if n == name} == {"all", "half"}
+        occ = T.walkers(name)
+        assert len({r.tobytes() for r in occ}) == 2
+        for st in T.structures(name):
+            assert st.t0 == nele * (nele + 1) // 2 and set(np.unique(st.t).tolist()) == {1, nele}
+        tab, cols, colsf = T.neighbourhoods(name, "half")
+        for c in cols:   # about half of a walker's columns are found, singles and doubles among them
+            found = c.pos[1:] >= 0
+            assert c.pos[0] >= 0 and 0.4 < found.mean() < 0.6 and (c.st.t[found] == nele).any() and (c.st.t[found] == 1).any()
+    assert max(s.noA + s.noB for n, s in T.SHAPES.items() if n not in ("s40e33", "s72e65")) == 30
 
 
 def test_reduce_cases_have_eps_inside_a_gap():
