@@ -616,9 +616,14 @@ int pynqs_rbm_forward(const uint64_t *onv, int64_t n, int sorb, const double *we
  *   pynqs_rbm_children_table_bytes : [host] size of the table for nwalkers parents (-1 on bad arguments)
  *   pynqs_rbm_children_prepare     : table <- the parents' q_h, sum_h theta_h, a.x and the parameters' factor table
  *   pynqs_rbm_forward_children     : psi[r] for r < min(*count_dev, n) (count_dev may be NULL: all n rows; rows past the count are left alone)
- *   pynqs_rbm_forward_children_supported : 1 for every valid (sorb, nhidden, flavour), else 0.  A factor table ((2 sorb + 1) x (nhidden + 2)
- *                                    entries) of at most 64 KB is kept in LDS, a thread per row; a larger one (sorb x nhidden above
- *                                    ~64 x 64) is read from the L2 by one wave per row, the lanes over the hidden units
+ *   pynqs_rbm_forward_children_supported : 1 for every valid (sorb, nhidden, flavour), else 0.  A factor table ((2 sorb + 1) x
+ *                                    ((nhidden + 2) | 1) entries of 8 bytes, 16 for complex parameters) of at most 64 KB is kept in LDS, a
+ *                                    thread per row; a larger one (sorb x nhidden above ~64 x 64) is read from the L2 by one wave per
+ *                                    row, the lanes over the hidden units
+ *   pynqs_rbm_forward_children_geometry : [host] the launch of pynqs_rbm_forward_children for n rows: out[0] = form (0: table in LDS,
+ *                                    1: a wave per row), out[1] = workgroups launched (capped: they stride over the rows), out[2] = rows
+ *                                    the grid covers per sweep on the table route, out[3] = rows per sweep on the from-scratch route (the
+ *                                    flag raised: a thread per row in both forms).  The expressions the launch itself uses.
  * Flavours and parameter layouts as pynqs_rbm_forward.  exp(-2 theta_h) is formed for the parents: if some Re theta_h < -340 the prepare
  * step raises a flag in the table and pynqs_rbm_forward_children computes every row from scratch instead (pynqs_rbm_forward's
  * algorithm inside the same kernel).  Below that, negative theta_h still make the factors 1 + q_h large (e^100 at theta_h = -50): a row
@@ -636,6 +641,7 @@ int pynqs_rbm_forward_children(const uint64_t *onv, int64_t n, const int32_t *co
                                const double *hidden_bias, const double *visible_bias, int nhidden, int flavour, double *psi,
                                void *stream);
 int pynqs_rbm_forward_children_supported(int sorb, int nhidden, int flavour);
+int pynqs_rbm_forward_children_geometry(int64_t n, int sorb, int nhidden, int flavour, int64_t *out4);
 /* The same pair with ONE launch for the prepare step (the same table bit for bit).  Within one launch the flag cannot be reset and then
  * raised, so a parent out of range stores the call's `stamp` there and pynqs_rbm_forward_children_stamped takes the flag for raised only if
  * it holds its own stamp: pass the same number in [1, 2^53) to both calls and a different one to every prepare call that may meet the same

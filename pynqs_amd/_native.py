@@ -107,6 +107,7 @@ SIGNATURES.update({
     "pynqs_rbm_children_prepare": (_int, [_vp, _i64, _int, _vp, _vp, _vp, _int, _int, _vp, _vp]),
     "pynqs_rbm_forward_children": (_int, [_vp, _i64, _vp, _vp, _vp, _i64, _vp, _int, _vp, _vp, _vp, _int, _int, _vp, _vp]),
     "pynqs_rbm_forward_children_supported": (_int, [_int, _int, _int]),
+    "pynqs_rbm_forward_children_geometry": (_int, [_i64, _int, _int, _int, C.POINTER(_i64)]),
     "pynqs_rbm_children_prepare_stamped": (_int, [_vp, _i64, _int, _vp, _vp, _vp, _int, _int, C.c_uint64, _vp, _vp]),
     "pynqs_rbm_forward_children_stamped": (_int, [_vp, _i64, _vp, _vp, _vp, _i64, _vp, _int, _vp, _vp, _vp, _int, _int, C.c_uint64, _vp, _vp]),
     "pynqs_rbm_grad_workspace": (_i64, [_i64, _int, _int, _int]),

@@ -380,6 +380,9 @@ __device__ __forceinline__ bool children_flag_raised(double word, double stamp) 
 #define PYNQS_CHILD_BLOCK 1024
 #endif
 constexpr int kChildBlock = PYNQS_CHILD_BLOCK;  // the factor table (up to 64 KB of LDS) is shared by the workgroup's waves: large workgroups, more waves per CU
+constexpr int kChildWaveRows = 16;            // the wave form: consecutive rows a wave takes at a time
+constexpr int64_t kChildMaxBlocks = 1024;     // the LDS form's grid (a workgroup copies the factor table once and strides over the rows)
+constexpr int64_t kChildMaxWaveBlocks = 256 * 32;  // the wave form's grid
 
 template <int LEN, int FLAVOUR>
 __global__ __launch_bounds__(kChildBlock) void rbm_forward_children_kernel(const uint64_t *__restrict__ onv, int64_t n, const int32_t *__restrict__ count_dev,
@@ -537,7 +540,7 @@ __global__ __launch_bounds__(kBlock) void rbm_forward_children_wave_kernel(const
   const int64_t nwaves = (int64_t)gridDim.x * (kBlock / 64);
   // a wave takes kWaveRows consecutive rows at a time (the children of a walker follow each other in the distinct list: the parent's row and
   // the factor rows of its occupied orbitals stay in the CU's L1)
-  constexpr int kWaveRows = 16;
+  constexpr int kWaveRows = kChildWaveRows;
   for (int64_t i0 = ((int64_t)blockIdx.x * (kBlock / 64) + wave) * kWaveRows; i0 < cnt; i0 += nwaves * kWaveRows)
   for (int64_t i = i0; i < min(i0 + kWaveRows, cnt); ++i) {  // (wave-uniform)
     int64_t p = parent[i];
@@ -771,6 +774,42 @@ extern "C" int pynqs_rbm_children_prepare_stamped(const uint64_t *walkers, int64
   return check_launch("rbm_children_prepare_stamped");
 }
 
+// The grid of pynqs_rbm_forward_children and the rows it covers before a workgroup strides on: the one source of the launch below and of
+// pynqs_rbm_forward_children_geometry.  LDS form: a thread per row on both routes.  Wave form: a wave per kChildWaveRows consecutive rows
+// on the table route, a thread per row on the from-scratch route (the flag raised).
+struct ChildrenGeometry {
+  bool in_lds;
+  int64_t blocks, table_rows, scratch_rows;
+};
+static ChildrenGeometry children_geometry(int64_t n, int sorb, int nhidden, int flavour) {
+  ChildrenGeometry g;
+  g.in_lds = children_table_in_lds(sorb, nhidden, flavour);
+  if (g.in_lds) {
+    g.blocks = (n + kChildBlock - 1) / kChildBlock;
+    if (g.blocks > kChildMaxBlocks) g.blocks = kChildMaxBlocks;
+    g.table_rows = g.scratch_rows = g.blocks * kChildBlock;
+  } else {
+    constexpr int64_t rows = (kBlock / 64) * kChildWaveRows;  // per workgroup
+    g.blocks = (n + rows - 1) / rows;
+    if (g.blocks > kChildMaxWaveBlocks) g.blocks = kChildMaxWaveBlocks;
+    g.table_rows = g.blocks * rows;
+    g.scratch_rows = g.blocks * kBlock;
+  }
+  return g;
+}
+
+extern "C" int pynqs_rbm_forward_children_geometry(int64_t n, int sorb, int nhidden, int flavour, int64_t *out4) {
+  if (!out4) return set_error(PYNQS_EINVAL, "null pointer");
+  if (n < 0 || n > 0x7fffffffll * kBlock || !pynqs_rbm_forward_children_supported(sorb, nhidden, flavour))
+    return set_error(PYNQS_EINVAL, "rbm_forward_children_geometry: bad n/sorb/nhidden/flavour");
+  const ChildrenGeometry g = children_geometry(n, sorb, nhidden, flavour);
+  out4[0] = g.in_lds ? 0 : 1;
+  out4[1] = g.blocks;
+  out4[2] = g.table_rows;
+  out4[3] = g.scratch_rows;
+  return PYNQS_OK;
+}
+
 static int forward_children_launch(const uint64_t *onv, int64_t n, const int32_t *count_dev, const int32_t *parent, const uint64_t *walkers,
                                    int64_t nwalkers, const void *table, int sorb, const double *weights, const double *hidden_bias,
                                    const double *visible_bias, int nhidden, int flavour, double stamp, double *psi, void *stream) {
@@ -781,23 +820,20 @@ static int forward_children_launch(const uint64_t *onv, int64_t n, const int32_t
   if (n == 0) return PYNQS_OK;
   if (!onv || !parent || !walkers || !table || !psi || !weights || !hidden_bias || nwalkers == 0) return set_error(PYNQS_EINVAL, "null pointer");
   const int len = (sorb - 1) / 64 + 1;
-  int64_t blocks = (n + kChildBlock - 1) / kChildBlock;
-  if (blocks > 1024) blocks = 1024;  // (a workgroup copies the factor table once and strides over the rows)
-  const uint32_t grid = (uint32_t)blocks;
+  const ChildrenGeometry geo = children_geometry(n, sorb, nhidden, flavour);
+  const uint32_t grid = (uint32_t)geo.blocks;
   const size_t lds = children_lds_bytes(sorb, nhidden, flavour);
   const double *parents = (const double *)table;
   const double *factors = parents + (size_t)nwalkers * (size_t)(nhidden + 2) * (flavour == PYNQS_RBM_COMPLEX ? 2 : 1);
   hipStream_t st = (hipStream_t)stream;
-  const bool in_lds = children_table_in_lds(sorb, nhidden, flavour);
-  int64_t wblocks = (n + (kBlock / 64) * 16 - 1) / ((kBlock / 64) * 16);   // the wave form: a wave per 16 consecutive rows, strided
-  if (wblocks > 256 * 32) wblocks = 256 * 32;
+  const bool in_lds = geo.in_lds;
 #define PYNQS_RC(F)                                                                                                                          \
   do {                                                                                                                                       \
     if (in_lds)                                                                                                                              \
       hipLaunchKernelGGL((rbm_forward_children_kernel<LEN, F>), dim3(grid), dim3(kChildBlock), lds, st, onv, n, count_dev, parent, walkers,  \
                          nwalkers, parents, factors, sorb, nhidden, weights, hidden_bias, visible_bias, psi, stamp);                         \
     else                                                                                                                                     \
-      hipLaunchKernelGGL((rbm_forward_children_wave_kernel<LEN, F>), dim3((uint32_t)wblocks), dim3(kBlock), 0, st, onv, n, count_dev,        \
+      hipLaunchKernelGGL((rbm_forward_children_wave_kernel<LEN, F>), dim3(grid), dim3(kBlock), 0, st, onv, n, count_dev,                     \
                          parent, walkers, nwalkers, parents, factors, sorb, nhidden, weights, hidden_bias, visible_bias, psi, stamp);        \
   } while (0)
   DISPATCH_LEN(len, {

@@ -529,10 +529,13 @@ def children_form(sorb: int, H: int, kind: str) -> str:
     return "lds" if (2 * sorb + 1) * ((H + 2) | 1) * (16 if kind == "complex" else 8) <= 64 * 1024 else "wave"
 
 
-def checked_case(kind: str, sorb: int, H: int, regime: str, words: np.ndarray, seed: int = 0, nspot: int = 2):
+def checked_case(kind: str, sorb: int, H: int, regime: str, words: np.ndarray, seed: int = 0, nspot: int = 2, rbm=None):
     """(rbm, x, Exact) of a case with the conditions that keep a comparison from passing vacuously asserted on the reference alone: every
-    row's psi is a finite normal double (|Re ln psi| <= LN_MAX), no row is left out, and for complex parameters max cond(x) <= 1e4."""
-    rbm = regime_params(regime, kind, sorb, H, seed)
+    row's psi is a finite normal double (|Re ln psi| <= LN_MAX), no row is left out, and for complex parameters max cond(x) <= 1e4.
+    rbm: the regime's parameters with a caller's changes (tests/children_cases.py), else regime_params(regime, ...)."""
+    if rbm is None:
+        rbm = regime_params(regime, kind, sorb, H, seed)
+    assert rbm.kind == kind and rbm.W.shape == (H, sorb)
     x = pm1(words, sorb)
     ex = exact(rbm, x, np.random.default_rng(seed), nspot)
     assert x.shape[0] == words.shape[0] and np.isfinite(ex.cond).all()
