@@ -642,6 +642,23 @@ int pynqs_rbm_forward_children(const uint64_t *onv, int64_t n, const int32_t *co
                                void *stream);
 int pynqs_rbm_forward_children_supported(int sorb, int nhidden, int flavour);
 int pynqs_rbm_forward_children_geometry(int64_t n, int sorb, int nhidden, int flavour, int64_t *out4);
+/* the same with the schedule of the LDS kernel chosen per call (pynqs_rbm_forward_children and ..._stamped take PYNQS_CHILDREN_CHUNKED):
+ *   PYNQS_CHILDREN_CHUNKED : eight hidden units at a time -- the parent's q_h of a chunk loaded together, the factors read a slot at a
+ *                            time for the chunk, the eight q_h chains side by side; the nhidden % 8 units left over one by one.  REAL,
+ *                            TANH and PHASE also request the next chunk's q_h before this chunk's arithmetic; PYNQS_RBM_COMPLEX does not
+ *                            (a second buffer of q_h does not fit its registers: it spilled and ran slower);
+ *   PYNQS_CHILDREN_PER_UNIT: one hidden unit after the other, each waiting for its own loads.
+ * The same operations on the same operands in the same order (q_h times its four factors in slot order, the product *= 1 + q_h in ascending
+ * h, renormalised after every eight): psi is the same bit for bit.  The wave form (a table beyond the LDS) has one schedule and ignores
+ * `form`; any other value is PYNQS_EINVAL.
+ * In the LDS form (both schedules) a row that has to be computed from scratch is marked in `psi` by a first loop and computed by a second:
+ * `psi` serves as scratch for the length of the launch and must not be read concurrently; rows at and past the count stay untouched. */
+#define PYNQS_CHILDREN_CHUNKED 0
+#define PYNQS_CHILDREN_PER_UNIT 1
+int pynqs_rbm_forward_children_form(const uint64_t *onv, int64_t n, const int32_t *count_dev, const int32_t *parent,
+                                    const uint64_t *walkers, int64_t nwalkers, const void *table, int sorb, const double *weights,
+                                    const double *hidden_bias, const double *visible_bias, int nhidden, int flavour, int form, double *psi,
+                                    void *stream);
 /* The same pair with ONE launch for the prepare step (the same table bit for bit).  Within one launch the flag cannot be reset and then
  * raised, so a parent out of range stores the call's `stamp` there and pynqs_rbm_forward_children_stamped takes the flag for raised only if
  * it holds its own stamp: pass the same number in [1, 2^53) to both calls and a different one to every prepare call that may meet the same
@@ -655,6 +672,10 @@ int pynqs_rbm_forward_children_stamped(const uint64_t *onv, int64_t n, const int
                                        const uint64_t *walkers, int64_t nwalkers, const void *table, int sorb, const double *weights,
                                        const double *hidden_bias, const double *visible_bias, int nhidden, int flavour, uint64_t stamp,
                                        double *psi, void *stream);
+int pynqs_rbm_forward_children_stamped_form(const uint64_t *onv, int64_t n, const int32_t *count_dev, const int32_t *parent,
+                                            const uint64_t *walkers, int64_t nwalkers, const void *table, int sorb, const double *weights,
+                                            const double *hidden_bias, const double *visible_bias, int nhidden, int flavour, uint64_t stamp,
+                                            int form, double *psi, void *stream);
 
 int64_t pynqs_rbm_grad_workspace(int64_t n, int sorb, int nhidden, int flavour);
 int pynqs_rbm_grad(const uint64_t *onv, int64_t n, int sorb, const double *weights, const double *hidden_bias,

@@ -825,12 +825,17 @@ _CHILDREN_STAMP = itertools.count(1)  # process-wide call counter of rbm_forward
 
 
 def rbm_forward_children(onv: Tensor, parent: Tensor, walkers: Tensor, weights: Tensor, hidden_bias: Tensor, visible_bias: "Tensor | None",
-                         sorb: int, rbm_type: str = "real", count: "Tensor | None" = None, out: "Tensor | None" = None) -> Tensor:
+                         sorb: int, rbm_type: str = "real", count: "Tensor | None" = None, out: "Tensor | None" = None,
+                         form: "int | None" = None) -> Tensor:
     """psi of the reference's RBM amplitudes (vmc/ansatz/rbm/rbm.py:186-211) on the DISTINCT x' of a REDUCE front end, each from its parent
     walker: onv[r] is walkers[parent[r]] with at most four orbitals flipped (ReduceFrontEnd.uniq_onv / .uniq_parent), so the factors
     1 + exp(-2 theta_h(x')) follow from the walker's by 4 table multiplications per hidden unit -- no exponential, no loop over the orbitals
     (pynqs_rbm_children_prepare on the walkers + pynqs_rbm_forward_children).  count: int32 device tensor whose
-    first element is the number of valid rows (the front end's counters; rows past it are not computed), or None for all rows."""
+    first element is the number of valid rows (the front end's counters; rows past it are not computed), or None for all rows.
+    form: the schedule of the LDS kernel, pynqs_rbm_forward_children_form's (0: eight hidden units at a time, 1: one by one; the same
+    bits); None: 0, unless the environment says PYNQS_RBM_CHILDREN_FORM=1 (read per call, for A/B runs of an unchanged caller)."""
+    if form is None:
+        form = N.CHILDREN_PER_UNIT if os.environ.get("PYNQS_RBM_CHILDREN_FORM") == "1" else N.CHILDREN_CHUNKED
     _check_onv(onv, "onv", sorb, (2,))
     _check_onv(walkers, "walkers", sorb, (2,))
     flav, W, hb, vb, H = _rbm_params(weights, hidden_bias, visible_bias, sorb, rbm_type)
@@ -848,10 +853,11 @@ def rbm_forward_children(onv: Tensor, parent: Tensor, walkers: Tensor, weights: 
     N.check(N.lib().pynqs_rbm_children_prepare_stamped(wk.data_ptr(), nw, sorb, W.data_ptr(), hb.data_ptr(), vb.data_ptr() if vb is not None else None,
                                                        H, flav, stamp, table.data_ptr(), st), "pynqs_rbm_children_prepare_stamped")
     psi = out if out is not None else torch.empty(n, dtype=_rbm_dtype(rbm_type), device=dev)
-    N.check(N.lib().pynqs_rbm_forward_children_stamped(onv.contiguous().data_ptr(), n, count.data_ptr() if count is not None else None,
-                                                       parent.data_ptr(), wk.data_ptr(), nw, table.data_ptr(), sorb, W.data_ptr(), hb.data_ptr(),
-                                                       vb.data_ptr() if vb is not None else None, H, flav, stamp, psi.data_ptr(), st),
-            "pynqs_rbm_forward_children_stamped")
+    N.check(N.lib().pynqs_rbm_forward_children_stamped_form(onv.contiguous().data_ptr(), n, count.data_ptr() if count is not None else None,
+                                                            parent.data_ptr(), wk.data_ptr(), nw, table.data_ptr(), sorb, W.data_ptr(),
+                                                            hb.data_ptr(), vb.data_ptr() if vb is not None else None, H, flav, stamp, int(form),
+                                                            psi.data_ptr(), st),
+            "pynqs_rbm_forward_children_stamped_form")
     return psi
 
 

@@ -15,6 +15,7 @@ LIB_PATH = os.environ.get("PYNQS_AMD_LIB") or os.path.join(_HERE, "csrc", "libpy
 
 PYNQS_F32, PYNQS_F64 = 0, 1
 RBM_REAL, RBM_TANH, RBM_PHASE, RBM_COMPLEX = 0, 1, 2, 4
+CHILDREN_CHUNKED, CHILDREN_PER_UNIT = 0, 1  # pynqs_rbm_forward_children_form's schedules
 OK, EINVAL, ELAUNCH, ELENGTH, EOVERFLOW = 0, -1, -2, -3, -4
 
 _i64, _int, _vp, _dbl = C.c_int64, C.c_int, C.c_void_p, C.c_double
@@ -110,6 +111,8 @@ SIGNATURES.update({
     "pynqs_rbm_forward_children_geometry": (_int, [_i64, _int, _int, _int, C.POINTER(_i64)]),
     "pynqs_rbm_children_prepare_stamped": (_int, [_vp, _i64, _int, _vp, _vp, _vp, _int, _int, C.c_uint64, _vp, _vp]),
     "pynqs_rbm_forward_children_stamped": (_int, [_vp, _i64, _vp, _vp, _vp, _i64, _vp, _int, _vp, _vp, _vp, _int, _int, C.c_uint64, _vp, _vp]),
+    "pynqs_rbm_forward_children_form": (_int, [_vp, _i64, _vp, _vp, _vp, _i64, _vp, _int, _vp, _vp, _vp, _int, _int, _int, _vp, _vp]),
+    "pynqs_rbm_forward_children_stamped_form": (_int, [_vp, _i64, _vp, _vp, _vp, _i64, _vp, _int, _vp, _vp, _vp, _int, _int, C.c_uint64, _int, _vp, _vp]),
     "pynqs_rbm_grad_workspace": (_i64, [_i64, _int, _int, _int]),
     "pynqs_rbm_grad": (_int, [_vp, _i64, _int, _vp, _vp, _vp, _int, _int, _vp, _vp, _int, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp]),
     "pynqs_rbm_grad_loss": (_int, [_vp, _i64, _int, _vp, _vp, _vp, _int, _int, _vp, _vp, _int, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp]),

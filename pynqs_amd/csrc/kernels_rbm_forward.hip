@@ -58,9 +58,12 @@ struct Prod {
   }
 };
 
-// psi from the product of the hidden units' factors and a.x = axr + i axi
+// psi from the product of the hidden units' factors and a.x = axr + i axi.  Contraction is off in here and the two fused multiply-adds are
+// written out: which product a compiler contracts with which sum depends on the code around the call (ln 2 e2 is one such product), and
+// the kernels that share this function must share its bits
 template <int FLAVOUR>
 __device__ __forceinline__ void write_psi(double *__restrict__ psi, int64_t i, const Prod &P, double axr, double axi) {
+#pragma clang fp contract(off)
   const double kLn2 = 0.693147180559945309417;
   if constexpr (FLAVOUR == PYNQS_RBM_REAL) {
     psi[i] = P.re * exp(axr + P.lin + kLn2 * (double)P.e2);
@@ -74,8 +77,8 @@ __device__ __forceinline__ void write_psi(double *__restrict__ psi, int64_t i, c
     const double m = exp(axr + P.lin + kLn2 * (double)P.e2);
     double sn, cs;
     sincos(axi + P.ang, &sn, &cs);
-    psi[2 * i] = m * (P.re * cs - P.im * sn);
-    psi[2 * i + 1] = m * (P.re * sn + P.im * cs);
+    psi[2 * i] = m * fma(P.re, cs, -(P.im * sn));
+    psi[2 * i + 1] = m * fma(P.re, sn, P.im * cs);
   }
 }
 
@@ -381,10 +384,213 @@ __device__ __forceinline__ bool children_flag_raised(double word, double stamp) 
 #endif
 constexpr int kChildBlock = PYNQS_CHILD_BLOCK;  // the factor table (up to 64 KB of LDS) is shared by the workgroup's waves: large workgroups, more waves per CU
 constexpr int kChildWaveRows = 16;            // the wave form: consecutive rows a wave takes at a time
-constexpr int64_t kChildMaxBlocks = 1024;     // the LDS form's grid (a workgroup copies the factor table once and strides over the rows)
+#ifndef PYNQS_CHILD_MAX_BLOCKS
+#define PYNQS_CHILD_MAX_BLOCKS 256
+#endif
+// the LDS form's grid: a workgroup copies the factor table once and strides over the rows.  One workgroup per CU of an MI355X (its 16 waves are
+// all the registers of the chunked schedule allow on a CU); measured at 256, 512 and 1024 (profiles/children_chunked_trace.txt)
+constexpr int64_t kChildMaxBlocks = PYNQS_CHILD_MAX_BLOCKS;
 constexpr int64_t kChildMaxWaveBlocks = 256 * 32;  // the wave form's grid
 
+// The arithmetic of one hidden unit of a child, shared by the two schedules of the LDS kernel below.  Every fused multiply-add is an fma()
+// and every product that is left (__dmul_rn: a plain product here) feeds an fma or another product, never a sum, so floating-point
+// contraction finds nothing to fuse differently in one schedule than in the other: the sequence is the one the compiler chose for the
+// per-unit loop before the schedules were two.
+//   q *= f  (slots 0..2, and slot 3 with complex parameters)
+template <bool CPLX>
+__device__ __forceinline__ void children_times_factor(double &qr, double &qi, double fr, double fi) {
+  if constexpr (CPLX) {
+    const double t = __dmul_rn(qi, fi);
+    const double nr = fma(qr, fr, -t);
+    qi = fma(qr, fi, __dmul_rn(qi, fr));
+    qr = nr;
+  } else {
+    qr = __dmul_rn(qr, fr);
+  }
+}
+//   the last slot and P *= 1 + q  (real parameters: 1 + q f is ONE fma)
+template <bool CPLX>
+__device__ __forceinline__ void children_times_one_plus(Prod &P, double qr, double qi, double fr, double fi) {
+  if constexpr (CPLX) {
+    children_times_factor<true>(qr, qi, fr, fi);
+    const double u = __dadd_rn(qr, 1.0);
+    const double t = __dmul_rn(P.im, qi);
+    const double nr = fma(P.re, u, -t);
+    P.im = fma(P.re, qi, __dmul_rn(P.im, u));
+    P.re = nr;
+  } else {
+    P.re = __dmul_rn(P.re, fma(qr, fr, 1.0));
+  }
+}
+
+constexpr int kChildGroupCplx = 4;  // complex parameters: factors of a slot read at a time (8: the kernel spills; real parameters take all 8)
+// q_h of the parent's row tp for the kHChunk hidden units from h0 on (all of them below H: the caller's business), kept as the table has
+// them, re next to im: a 16-byte load lands where it is used
+template <bool CPLX>
+struct ChildQ {
+  double v[kHChunk][CPLX ? 2 : 1];
+};
+template <bool CPLX>
+__device__ __forceinline__ void children_load_q(const double *__restrict__ tp, int h0, ChildQ<CPLX> &q) {
+  constexpr int C = CPLX ? 2 : 1;
+#pragma unroll
+  for (int j = 0; j < kHChunk; ++j)
+#pragma unroll
+    for (int c = 0; c < C; ++c) q.v[j][c] = tp[(size_t)(h0 + j) * C + c];
+}
+
+// one full chunk of the chunked schedule: the factors of a slot are read for all kHChunk units (consecutive LDS words per lane), the kHChunk
+// chains advance side by side, and the last slot feeds P in ascending h; renorm() as after every chunk
+template <bool CPLX>
+__device__ __forceinline__ void children_chunk(Prod &P, ChildQ<CPLX> &q, const double *__restrict__ wl, const int (&at)[4], int h0) {
+  constexpr int C = CPLX ? 2 : 1;
+  constexpr int G = CPLX ? kChildGroupCplx : kHChunk;  // factors read at a time
+#pragma unroll
+  for (int s = 0; s < 4; ++s) {
+#pragma unroll
+    for (int g = 0; g < kHChunk; g += G) {
+      double f[G][C];
+#pragma unroll
+      for (int j = 0; j < G; ++j)
+#pragma unroll
+        for (int c = 0; c < C; ++c) f[j][c] = wl[(size_t)(at[s] + h0 + g + j) * C + c];
+#pragma unroll
+      for (int j = 0; j < G; ++j) {
+        double zero = 0.0;
+        double &qi = CPLX ? q.v[g + j][C - 1] : zero;
+        const double fi = CPLX ? f[j][C - 1] : 0.0;
+        if (s < 3) children_times_factor<CPLX>(q.v[g + j][0], qi, f[j][0], fi);
+        else children_times_one_plus<CPLX>(P, q.v[g + j][0], qi, f[j][0], fi);
+      }
+    }
+  }
+  P.renorm();
+}
+
+// the from-scratch evaluation of the LDS kernel's rare paths (the raised flag, a wave with a stranger)
 template <int LEN, int FLAVOUR>
+__device__ __forceinline__ void children_row_from_scratch(const uint64_t *__restrict__ onv, int64_t row, int sorb, int H,
+                                                       const double *__restrict__ W, const double *__restrict__ hb,
+                                                       const double *__restrict__ vb, Prod &P, double &axr, double &axi) {
+  uint64_t ket[LEN];
+#pragma unroll
+  for (int w = 0; w < LEN; ++w) ket[w] = onv[row * LEN + w];
+  P = Prod();
+  rbm_forward_row<LEN, FLAVOUR>(ket, sorb, H, W, hb, vb, P, axr, axi);
+}
+
+// Row i of the LDS kernel from its parent's row of the table and the factor table wl in LDS: P and a.x, and whether the row has to be
+// computed from scratch instead (a stranger, or a product that left the range of a double).
+// FORM 0 (PYNQS_CHILDREN_CHUNKED): kHChunk hidden units at a time -- their q_h(parent) loaded together, the factors read a slot at a time
+// for the chunk, eight q_h chains side by side, P *= 1 + q_h in ascending h; the H % kHChunk units left over one by one.  With REAL / TANH /
+// PHASE parameters the next chunk's q_h are requested into a second buffer before this chunk's arithmetic.  With COMPLEX parameters they
+// are NOT: two chunks of q_h (64 registers) next to the factors and the row's own state do not fit the 128 registers of a 1024-thread
+// workgroup -- built that way the kernel spilled 32 of them and ran slower than form 1 (115 against 103 us on the flagship; 91 us as it is,
+// at the same grid: DESIGN 8, "The children kernel") -- so a chunk's eight loads go out together and the CU's other waves cover their one
+// round trip.  FORM 1 (PYNQS_CHILDREN_PER_UNIT): one hidden unit after the other, each waiting for its own loads (the schedule before there
+// were two).  The same operations on the same operands in the same order: the same bits.
+template <int LEN, bool CPLX, int FORM>
+__device__ __forceinline__ bool children_row_from_table(const uint64_t *__restrict__ onv, int64_t i, const int32_t *__restrict__ parent,
+                                                        const uint64_t *__restrict__ walkers, int64_t nwalkers,
+                                                        const double *__restrict__ table, const double *__restrict__ wl, int sorb, int H,
+                                                        Prod &P, double &axr, double &axi) {
+  constexpr int C = CPLX ? 2 : 1;
+  const int HP = children_hp(H);
+  int64_t p = parent[i];
+  // a row that is NOT its parent with at most four orbitals flipped (a parent index out of range, a row the caller put there itself) is
+  // computed from scratch instead of being truncated to four flips silently
+  bool stranger = p < 0 || p >= nwalkers;
+  p = stranger ? 0 : p;
+  const double *__restrict__ tp = table + (size_t)p * (size_t)(H + 2) * C;
+  constexpr bool kChunked = FORM == PYNQS_CHILDREN_CHUNKED;
+  const int hfull = kChunked ? H - H % kHChunk : 0;  // hidden units the chunked schedule takes
+  // the first chunk is requested as soon as the parent is known, ahead of the comparison with the parent's determinant
+  ChildQ<CPLX> qa;
+  if (hfull > 0) children_load_q<CPLX>(tp, 0, qa);
+  // the rows of the factor table for the flipped orbitals ("no flip" for the unused slots)
+  int at[4];
+#pragma unroll
+  for (int q = 0; q < 4; ++q) at[q] = 2 * sorb * HP;
+  int k = 0, nflip = 0;
+#pragma unroll
+  for (int w = 0; w < LEN; ++w) {
+    const uint64_t xc = onv[i * LEN + w];
+    uint64_t d = xc ^ walkers[p * LEN + w];
+    nflip += __popcll(d);
+#pragma unroll
+    for (int t = 0; t < 4; ++t) {
+      if (d && k < 4) {
+        const int b = __builtin_ctzll(d);
+        d &= d - 1;
+        const int r = (2 * (64 * w + b) + (((xc >> b) & 1ull) ? 0 : 1)) * HP;
+        // (k is a small per-lane counter: the slots are selected, not indexed)
+#pragma unroll
+        for (int q = 0; q < 4; ++q)
+          if (q == k) at[q] = r;
+        ++k;
+      }
+    }
+  }
+  P = Prod();
+  if constexpr (!CPLX) {
+    // two buffers taking turns (no copy between them): while one chunk is worked on, the next one's q_h are on their way into the other
+    ChildQ<CPLX> qb;
+    for (int h0 = 0; h0 < hfull; h0 += 2 * kHChunk) {
+      if (h0 + kHChunk < hfull) children_load_q<CPLX>(tp, h0 + kHChunk, qb);
+      children_chunk<CPLX>(P, qa, wl, at, h0);
+      if (h0 + kHChunk >= hfull) break;
+      if (h0 + 2 * kHChunk < hfull) children_load_q<CPLX>(tp, h0 + 2 * kHChunk, qa);
+      children_chunk<CPLX>(P, qb, wl, at, h0 + kHChunk);
+    }
+  } else {
+    for (int h0 = 0; h0 < hfull; h0 += kHChunk) {
+      if (h0 > 0) children_load_q<CPLX>(tp, h0, qa);
+      children_chunk<CPLX>(P, qa, wl, at, h0);
+    }
+  }
+  for (int h0 = hfull; h0 < H; h0 += kHChunk) {
+#pragma unroll
+    for (int j = 0; j < kHChunk; ++j) {
+      const int h = h0 + j;
+      if (h < H) {
+        double qr = tp[(size_t)h * C], qi = CPLX ? tp[(size_t)h * C + 1] : 0.0;
+#pragma unroll
+        for (int q = 0; q < 3; ++q)
+          children_times_factor<CPLX>(qr, qi, wl[(size_t)(at[q] + h) * C], CPLX ? wl[(size_t)(at[q] + h) * C + 1] : 0.0);
+        children_times_one_plus<CPLX>(P, qr, qi, wl[(size_t)(at[3] + h) * C], CPLX ? wl[(size_t)(at[3] + h) * C + 1] : 0.0);
+      }
+    }
+    P.renorm();
+  }
+  axr = tp[(size_t)(H + 1) * C];
+  axi = CPLX ? tp[(size_t)(H + 1) * C + 1] : 0.0;
+  P.lin = tp[(size_t)H * C];
+  P.ang = CPLX ? tp[(size_t)H * C + 1] : 0.0;
+#pragma unroll
+  for (int q = 0; q < 4; ++q) {
+    P.lin += wl[(size_t)(at[q] + H) * C];
+    axr += wl[(size_t)(at[q] + H + 1) * C];
+    if constexpr (CPLX) {
+      P.ang += wl[(size_t)(at[q] + H) * C + 1];
+      axi += wl[(size_t)(at[q] + H + 1) * C + 1];
+    }
+  }
+  return stranger || nflip > 4 || !P.finite();  // (a product that overflowed: see the table's description)
+}
+
+constexpr int kChildStage = 4;  // 16-byte loads a thread has in flight while the factor table is copied into LDS (64 KB / 1024 threads)
+// what a row that has to be computed from scratch holds between the two loops of the LDS kernel: a nan no arithmetic produces.  (Were
+// an ordinary row ever to end on these bits it would be computed from scratch as well, which is right for every row.)
+constexpr long long kChildAgainBits = 0x7ff8c41d5eedc41dll;
+
+// A thread per row, in two loops.  The first takes every row from the tables and leaves a mark in psi where that will not do (strangers,
+// overflowed products); the second, entered only by waves that left a mark -- or by all of them when the flag is raised: then there is no
+// first loop -- computes the marked rows from scratch (the whole wave walks the parameters, the marked rows keep the result).  So the
+// from-scratch code and its constants exist once and outside the hot loop.  The mark lives in the caller's psi between the two loops (a
+// marked row costs one more store and load): the thread that wrote it reads it and only rows below the count are touched, but psi is
+// scratch for the length of the launch and NOTHING MAY READ IT CONCURRENTLY.  Both forms share the staging, this tail and write_psi: form 1
+// is the earlier kernel's schedule of the hidden units, not that kernel instruction for instruction.
+template <int LEN, int FLAVOUR, int FORM>
 __global__ __launch_bounds__(kChildBlock) void rbm_forward_children_kernel(const uint64_t *__restrict__ onv, int64_t n, const int32_t *__restrict__ count_dev,
                                                                       const int32_t *__restrict__ parent, const uint64_t *__restrict__ walkers,
                                                                       int64_t nwalkers, const double *__restrict__ table,
@@ -393,112 +599,54 @@ __global__ __launch_bounds__(kChildBlock) void rbm_forward_children_kernel(const
                                                                       const double *__restrict__ vb, double *__restrict__ psi, double stamp) {
   constexpr bool CPLX = FLAVOUR == PYNQS_RBM_COMPLEX;
   constexpr int C = CPLX ? 2 : 1;
+  constexpr int CO = (CPLX || FLAVOUR == PYNQS_RBM_PHASE) ? 2 : 1;  // doubles of psi per row
   extern __shared__ __attribute__((aligned(16))) double wl[];
   const int HP = children_hp(H);
   int64_t cnt = n;
   if (count_dev) cnt = min((int64_t)max(*count_dev, 0), n);
-  if (children_flag_raised(factors[(size_t)(2 * sorb + 1) * HP * C], stamp)) {  // (grid-uniform) parents out of range: every row from scratch
-    const int64_t rounds = (cnt + (int64_t)gridDim.x * kChildBlock - 1) / ((int64_t)gridDim.x * kChildBlock);
-    for (int64_t r = 0; r < rounds; ++r) {  // (whole waves iterate together: the parameter loads are wave-uniform)
-      const int64_t i = ((int64_t)r * gridDim.x + blockIdx.x) * kChildBlock + threadIdx.x;
-      const int64_t row = i < cnt ? i : cnt - 1;
-      uint64_t ket[LEN];
+  const int64_t first = (int64_t)blockIdx.x * kChildBlock + threadIdx.x, stride = (int64_t)gridDim.x * kChildBlock;
+  // (grid-uniform) parents out of range: every row from scratch
+  const bool raised = children_flag_raised(factors[(size_t)(2 * sorb + 1) * HP * C], stamp);
+  bool again = raised;  // some row of this thread is for the second loop
+  if (!raised) {
+    // the factor table into LDS, the same image either way: 16-byte loads from the first 16-byte boundary on, all of a thread's loads in
+    // flight before its stores; the double before that boundary (a table that starts 8 bytes off) and the odd one at the end by themselves
+    const int total = (2 * sorb + 1) * HP * C;
+    const int head = (int)(((uintptr_t)factors >> 3) & 1);
+    const int nvec = (total - head) >> 1;  // (total >= 9: never 0)
+    const double2 *__restrict__ src = reinterpret_cast<const double2 *>(factors + head);
+    for (int base = threadIdx.x; base < nvec; base += kChildBlock * kChildStage) {
+      double2 v[kChildStage];
 #pragma unroll
-      for (int w = 0; w < LEN; ++w) ket[w] = onv[row * LEN + w];
+      for (int b = 0; b < kChildStage; ++b) v[b] = src[min(base + b * kChildBlock, nvec - 1)];
+#pragma unroll
+      for (int b = 0; b < kChildStage; ++b) {
+        const int idx = base + b * kChildBlock;
+        if (idx < nvec) { wl[head + 2 * idx] = v[b].x; wl[head + 2 * idx + 1] = v[b].y; }
+      }
+    }
+    if (threadIdx.x == 0 && head) wl[0] = factors[0];
+    if (threadIdx.x == 64 % kChildBlock && head + 2 * nvec < total) wl[total - 1] = factors[total - 1];
+    __syncthreads();
+    for (int64_t i = first; i < cnt; i += stride) {
       Prod P;
       double axr, axi;
-      rbm_forward_row<LEN, FLAVOUR>(ket, sorb, H, W, hb, vb, P, axr, axi);
-      if (i < cnt) write_psi<FLAVOUR>(psi, i, P, axr, axi);
+      if (children_row_from_table<LEN, CPLX, FORM>(onv, i, parent, walkers, nwalkers, table, wl, sorb, H, P, axr, axi)) {
+        again = true;
+        psi[CO * i] = __longlong_as_double(kChildAgainBits);
+      } else {
+        write_psi<FLAVOUR>(psi, i, P, axr, axi);
+      }
     }
-    return;
   }
-  for (int idx = threadIdx.x; idx < (2 * sorb + 1) * HP * C; idx += kChildBlock) wl[idx] = factors[idx];
-  __syncthreads();
-  for (int64_t i = (int64_t)blockIdx.x * kChildBlock + threadIdx.x; i < cnt; i += (int64_t)gridDim.x * kChildBlock) {
-    int64_t p = parent[i];
-    // a row that is NOT its parent with at most four orbitals flipped (a parent index out of range, a row the caller put there itself) is
-    // computed from scratch below instead of being truncated to four flips silently
-    bool stranger = p < 0 || p >= nwalkers;
-    p = stranger ? 0 : p;
-    // the rows of the factor table for the flipped orbitals ("no flip" for the unused slots)
-    int at[4];
-#pragma unroll
-    for (int q = 0; q < 4; ++q) at[q] = 2 * sorb * HP;
-    int k = 0, nflip = 0;
-#pragma unroll
-    for (int w = 0; w < LEN; ++w) {
-      const uint64_t xc = onv[i * LEN + w];
-      uint64_t d = xc ^ walkers[p * LEN + w];
-      nflip += __popcll(d);
-#pragma unroll
-      for (int t = 0; t < 4; ++t) {
-        if (d && k < 4) {
-          const int b = __builtin_ctzll(d);
-          d &= d - 1;
-          const int r = (2 * (64 * w + b) + (((xc >> b) & 1ull) ? 0 : 1)) * HP;
-          // (k is a small per-lane counter: the slots are selected, not indexed)
-#pragma unroll
-          for (int q = 0; q < 4; ++q)
-            if (q == k) at[q] = r;
-          ++k;
-        }
-      }
-    }
-    const double *__restrict__ tp = table + (size_t)p * (size_t)(H + 2) * C;
+  if (!__ballot(again)) return;
+  for (int64_t i = first; i < cnt; i += stride) {
+    const bool mine = raised || (again && __double_as_longlong(psi[CO * i]) == kChildAgainBits);
+    if (!__ballot(mine)) continue;
     Prod P;
-    for (int h0 = 0; h0 < H; h0 += kHChunk) {
-#pragma unroll
-      for (int j = 0; j < kHChunk; ++j) {
-        const int h = h0 + j;
-        if (h < H) {
-          double qr = tp[(size_t)h * C], qi = CPLX ? tp[(size_t)h * C + 1] : 0.0;
-#pragma unroll
-          for (int q = 0; q < 4; ++q) {
-            const double fr = wl[(size_t)(at[q] + h) * C];
-            if constexpr (CPLX) {
-              const double fi = wl[(size_t)(at[q] + h) * C + 1];
-              const double nr = qr * fr - qi * fi;
-              qi = fma(qr, fi, qi * fr);
-              qr = nr;
-            } else {
-              qr *= fr;
-            }
-          }
-          if constexpr (CPLX) {  // P *= 1 + q
-            const double u = 1.0 + qr;
-            const double nr = P.re * u - P.im * qi;
-            P.im = fma(P.re, qi, P.im * u);
-            P.re = nr;
-          } else {
-            P.re *= 1.0 + qr;
-          }
-        }
-      }
-      P.renorm();
-    }
-    double axr = tp[(size_t)(H + 1) * C], axi = CPLX ? tp[(size_t)(H + 1) * C + 1] : 0.0;
-    P.lin = tp[(size_t)H * C];
-    P.ang = CPLX ? tp[(size_t)H * C + 1] : 0.0;
-#pragma unroll
-    for (int q = 0; q < 4; ++q) {
-      P.lin += wl[(size_t)(at[q] + H) * C];
-      axr += wl[(size_t)(at[q] + H + 1) * C];
-      if constexpr (CPLX) {
-        P.ang += wl[(size_t)(at[q] + H) * C + 1];
-        axi += wl[(size_t)(at[q] + H + 1) * C + 1];
-      }
-    }
-    stranger = stranger || nflip > 4 || !P.finite();  // (a product that overflowed: see the table's description)
-    if (__ballot(stranger)) {  // (rare: the whole wave walks the parameters, the strangers keep the result)
-      uint64_t ket[LEN];
-#pragma unroll
-      for (int w = 0; w < LEN; ++w) ket[w] = onv[i * LEN + w];
-      Prod P2;
-      double a2r, a2i;
-      rbm_forward_row<LEN, FLAVOUR>(ket, sorb, H, W, hb, vb, P2, a2r, a2i);
-      if (stranger) { P = P2; axr = a2r; axi = a2i; }
-    }
-    write_psi<FLAVOUR>(psi, i, P, axr, axi);
+    double axr, axi;
+    children_row_from_scratch<LEN, FLAVOUR>(onv, i, sorb, H, W, hb, vb, P, axr, axi);
+    if (mine) write_psi<FLAVOUR>(psi, i, P, axr, axi);
   }
 }
 
@@ -812,8 +960,9 @@ extern "C" int pynqs_rbm_forward_children_geometry(int64_t n, int sorb, int nhid
 
 static int forward_children_launch(const uint64_t *onv, int64_t n, const int32_t *count_dev, const int32_t *parent, const uint64_t *walkers,
                                    int64_t nwalkers, const void *table, int sorb, const double *weights, const double *hidden_bias,
-                                   const double *visible_bias, int nhidden, int flavour, double stamp, double *psi, void *stream) {
+                                   const double *visible_bias, int nhidden, int flavour, double stamp, int form, double *psi, void *stream) {
   pynqs::DeviceScope device_scope_(onv);
+  if (form != PYNQS_CHILDREN_CHUNKED && form != PYNQS_CHILDREN_PER_UNIT) return set_error(PYNQS_EINVAL, "rbm_forward_children: bad form");
   if (n < 0 || n > 0x7fffffffll * kBlock || nwalkers < 0 || sorb < 1 || sorb > kMaxSorb || nhidden < 1) return set_error(PYNQS_EINVAL, "bad n/sorb/nhidden");
   if (!pynqs_rbm_forward_children_supported(sorb, nhidden, flavour))
     return set_error(PYNQS_EINVAL, "rbm_forward_children: bad flavour");
@@ -829,9 +978,14 @@ static int forward_children_launch(const uint64_t *onv, int64_t n, const int32_t
   const bool in_lds = geo.in_lds;
 #define PYNQS_RC(F)                                                                                                                          \
   do {                                                                                                                                       \
-    if (in_lds)                                                                                                                              \
-      hipLaunchKernelGGL((rbm_forward_children_kernel<LEN, F>), dim3(grid), dim3(kChildBlock), lds, st, onv, n, count_dev, parent, walkers,  \
-                         nwalkers, parents, factors, sorb, nhidden, weights, hidden_bias, visible_bias, psi, stamp);                         \
+    if (in_lds && form == PYNQS_CHILDREN_CHUNKED)                                                                                            \
+      hipLaunchKernelGGL((rbm_forward_children_kernel<LEN, F, PYNQS_CHILDREN_CHUNKED>), dim3(grid), dim3(kChildBlock), lds, st, onv, n,      \
+                         count_dev, parent, walkers, nwalkers, parents, factors, sorb, nhidden, weights, hidden_bias, visible_bias, psi,     \
+                         stamp);                                                                                                             \
+    else if (in_lds)                                                                                                                         \
+      hipLaunchKernelGGL((rbm_forward_children_kernel<LEN, F, PYNQS_CHILDREN_PER_UNIT>), dim3(grid), dim3(kChildBlock), lds, st, onv, n,     \
+                         count_dev, parent, walkers, nwalkers, parents, factors, sorb, nhidden, weights, hidden_bias, visible_bias, psi,     \
+                         stamp);                                                                                                             \
     else                                                                                                                                     \
       hipLaunchKernelGGL((rbm_forward_children_wave_kernel<LEN, F>), dim3(grid), dim3(kBlock), 0, st, onv, n, count_dev,                     \
                          parent, walkers, nwalkers, parents, factors, sorb, nhidden, weights, hidden_bias, visible_bias, psi, stamp);        \
@@ -848,19 +1002,37 @@ static int forward_children_launch(const uint64_t *onv, int64_t n, const int32_t
   return check_launch("rbm_forward_children");
 }
 
+// form: the LDS kernel's schedule, PYNQS_CHILDREN_CHUNKED or PYNQS_CHILDREN_PER_UNIT (the same bits; the wave form has one schedule and
+// ignores it).  Per call: one process can run both.
+extern "C" int pynqs_rbm_forward_children_form(const uint64_t *onv, int64_t n, const int32_t *count_dev, const int32_t *parent,
+                                               const uint64_t *walkers, int64_t nwalkers, const void *table, int sorb, const double *weights,
+                                               const double *hidden_bias, const double *visible_bias, int nhidden, int flavour, int form,
+                                               double *psi, void *stream) {
+  return forward_children_launch(onv, n, count_dev, parent, walkers, nwalkers, table, sorb, weights, hidden_bias, visible_bias, nhidden, flavour,
+                                 0.0, form, psi, stream);
+}
+
 extern "C" int pynqs_rbm_forward_children(const uint64_t *onv, int64_t n, const int32_t *count_dev, const int32_t *parent,
                                           const uint64_t *walkers, int64_t nwalkers, const void *table, int sorb, const double *weights,
                                           const double *hidden_bias, const double *visible_bias, int nhidden, int flavour, double *psi,
                                           void *stream) {
+  return pynqs_rbm_forward_children_form(onv, n, count_dev, parent, walkers, nwalkers, table, sorb, weights, hidden_bias, visible_bias, nhidden,
+                                         flavour, PYNQS_CHILDREN_CHUNKED, psi, stream);
+}
+
+extern "C" int pynqs_rbm_forward_children_stamped_form(const uint64_t *onv, int64_t n, const int32_t *count_dev, const int32_t *parent,
+                                                       const uint64_t *walkers, int64_t nwalkers, const void *table, int sorb,
+                                                       const double *weights, const double *hidden_bias, const double *visible_bias,
+                                                       int nhidden, int flavour, uint64_t stamp, int form, double *psi, void *stream) {
+  if (!children_stamp_ok(stamp)) return set_error(PYNQS_EINVAL, "rbm_forward_children_stamped: stamp must be in [1, 2^53)");
   return forward_children_launch(onv, n, count_dev, parent, walkers, nwalkers, table, sorb, weights, hidden_bias, visible_bias, nhidden, flavour,
-                                 0.0, psi, stream);
+                                 (double)stamp, form, psi, stream);
 }
 
 extern "C" int pynqs_rbm_forward_children_stamped(const uint64_t *onv, int64_t n, const int32_t *count_dev, const int32_t *parent,
                                                   const uint64_t *walkers, int64_t nwalkers, const void *table, int sorb, const double *weights,
                                                   const double *hidden_bias, const double *visible_bias, int nhidden, int flavour,
                                                   uint64_t stamp, double *psi, void *stream) {
-  if (!children_stamp_ok(stamp)) return set_error(PYNQS_EINVAL, "rbm_forward_children_stamped: stamp must be in [1, 2^53)");
-  return forward_children_launch(onv, n, count_dev, parent, walkers, nwalkers, table, sorb, weights, hidden_bias, visible_bias, nhidden, flavour,
-                                 (double)stamp, psi, stream);
+  return pynqs_rbm_forward_children_stamped_form(onv, n, count_dev, parent, walkers, nwalkers, table, sorb, weights, hidden_bias, visible_bias,
+                                                 nhidden, flavour, stamp, PYNQS_CHILDREN_CHUNKED, psi, stream);
 }
