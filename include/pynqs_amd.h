@@ -226,6 +226,11 @@ int pynqs_eloc_rbm_supported(int sorb, int nele, int noA, int noB, int nhidden);
  * very rule the launch uses: -1 if unsupported, else bit 0 = the windowed kernel (sorb x nhidden beyond the LDS), bit 1 = a walker's
  * tiles are cut over several workgroups that add their parts with atomics (fewer than 1024 walkers). */
 int pynqs_eloc_rbm_form(int64_t nbatch, int sorb, int nele, int noA, int noB, int nhidden, int green);
+/* [host] the whole launch behind that form, and behind pynqs_eloc_jrbm (jastrow = 1, green = 0) and pynqs_green_jrbm (jastrow = 1,
+ * green = 1; their signed and flip passes launch alike): out6[0] = workgroups, [1] = threads per workgroup, [2] = bytes of dynamic LDS,
+ * [3] = hidden units resident in LDS, [4] = workgroups per walker, [5] = 1 if the walker's Jastrow pair factors are kept in LDS.
+ * Returns 0, or -1 (out6 untouched) where the launch is not served or nbatch is outside [1, 2^31 - 1]. */
+int pynqs_eloc_rbm_geometry(int64_t nbatch, int sorb, int nele, int noA, int noB, int nhidden, int green, int jastrow, int64_t *out6);
 int64_t pynqs_rbm_table_bytes(int sorb, int nhidden);
 int pynqs_rbm_table_build(const double *weights, const double *hidden_bias, const double *visible_bias, int sorb,
                           int nhidden, void *table, void *stream);

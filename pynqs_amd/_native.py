@@ -55,6 +55,7 @@ SIGNATURES = {
     "pynqs_eloc_sample_space_keys_form": (_int, [_i64, _int, _i64, _int, C.POINTER(_i64)]),
     "pynqs_eloc_rbm_supported": (_int, [_int, _int, _int, _int, _int]),
     "pynqs_eloc_rbm_form": (_int, [_i64, _int, _int, _int, _int, _int, _int]),
+    "pynqs_eloc_rbm_geometry": (_int, [_i64, _int, _int, _int, _int, _int, _int, _int, C.POINTER(_i64)]),
     "pynqs_rbm_table_bytes": (_i64, [_int, _int]),
     "pynqs_rbm_table_build": (_int, [_vp, _vp, _vp, _int, _int, _vp, _vp]),
     "pynqs_eloc_rbm": (_int, [_vp, _i64, _int, _int, _int, _int, _vp, _vp, _int, _vp, _vp, _vp]),

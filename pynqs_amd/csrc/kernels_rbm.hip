@@ -45,16 +45,16 @@
 //   single, six for a double, read in the tile epilogue and multiplied onto the running products: a lane's 4 x 4 block takes 4 + 4
 //   loads for the pairs inside its fast and slow entries and 64 for the crossed pairs, 4.5 loads and 6 products per column.  They come
 //   from a per-walker triangle P[i > j] = exp(4 S_ij x_i x_j) in LDS behind the trailer (4 sorb (sorb - 1) bytes, built from the table
-//   next to C(o); `lambda` != 0) where three workgroups still fit a CU with it, else from the table itself (L2-resident, 16 sorb^2
+//   next to C(o); `pairs_in_lds`) where three workgroups still fit a CU with it, else from the table itself (L2-resident, 16 sorb^2
 //   bytes).  Fe2S2, 8192 walkers: 0.97-1.13 ms from LDS, 1.00-1.17 ms from L2, pynqs_eloc_rbm 0.77 ms in the same run.
-// tr M scales psi(x) only.  Every statement of it stands under `if constexpr (JASTROW)`; without GREEN the table comes in the slot of
-// `green`, which that form does not use, and `lambda` != 0 says that the pair factors are in LDS.
+// tr M scales psi(x) only.  Every statement of it stands under `if constexpr (JASTROW)`.
 //
 // GREEN and JASTROW together (pynqs_green_jrbm): the pair factors join the running products in the tile epilogue BEFORE add_column, so
-// the row, v_sf and the diagonal see the full ratio.  `green`, `lambda` and `clamped` keep their meaning; the table comes in the trailing
-// argument `jastrow` (nullptr in every other form) and the LDS flag in bit 1 of the chunk count, which is 1 in this form by construction
-// (one workgroup per walker: the row finishes its diagonal in the kernel).  The other instantiations' registers are what they were
-// (DESIGN 4.8).
+// the row, v_sf and the diagonal see the full ratio.
+//
+// The arguments mean the same in all 57 instantiations: `green`, `lambda`, `clamped` are the row's (nullptr, 0, nullptr without GREEN),
+// `jastrow` is the Jastrow table (nullptr without JASTROW), `pairs_in_lds` the home of the walker's pair factors, `chunks` the workgroups
+// per walker (1 with GREEN: the row finishes its diagonal in the kernel).
 //
 // SIGNED (no GREEN form): every column's matrix element times sigma_k = eta_m(x'_k) eta_m(x), eta_m(y) = (-1)^(doubly occupied spatial
 // orbitals of y): the second pass of the spin-flip-projected local energy (vmc/energy/flip.py, _simple_flip; pynqs_eloc_rbm_flip /
@@ -126,26 +126,19 @@ enum : int { kRbmReal = 0, kRbmTanh = 1, kRbmPhase = 2 };
 
 template <int LEN, bool WINDOWED, int FLAVOUR, bool GREEN, bool JASTROW = false, bool SIGNED = false>
 __global__ __launch_bounds__(1024, 4) void eloc_rbm_kernel(const uint64_t *__restrict__ bra, SDParams p, PlanLayout pl, RbmLayout rl,
-                                                          RbmBlocks<kRbmFB> B, uint32_t nchunks_arg, uint32_t hw, const double *__restrict__ plan,
+                                                          RbmBlocks<kRbmFB> B, uint32_t chunks, uint32_t hw, const double *__restrict__ plan,
                                                           const double *__restrict__ rbm, double *__restrict__ eloc,
                                                           double *__restrict__ psi, double lambda, double *__restrict__ green,
-                                                          uint8_t *__restrict__ clamped, const double *__restrict__ jastrow) {
+                                                          uint8_t *__restrict__ clamped, const double *__restrict__ jastrow, bool pairs_in_lds) {
   static_assert(!GREEN || FLAVOUR != kRbmPhase, "the fixed-node row needs a real-valued amplitude");
   static_assert(!JASTROW || (FLAVOUR == kRbmReal && !WINDOWED), "the Jastrow factor: real flavour, resident form");
   static_assert(!SIGNED || !GREEN, "the signed sum is the second pass of the spin-flip-projected energy: no row");
-  // GREEN and JASTROW together (pynqs_green_jrbm): `green`, `lambda` and `clamped` are the row's, so the Jastrow table comes in `jastrow`
-  // and the "pair factors in LDS" flag in bit 1 of `nchunks_arg` -- the row is launched with one workgroup per walker, so the chunk
-  // count is the constant 1 in that form.  Every other instantiation reads what it read before.
-  constexpr bool kGreenJastrow = GREEN && JASTROW;
-  const uint32_t nchunks = kGreenJastrow ? 1u : nchunks_arg;
-  [[maybe_unused]] auto jas_table = [&]() -> const double * {
-    if constexpr (kGreenJastrow) return jastrow;
-    else return green;
-  };
-  [[maybe_unused]] auto jas_pairs_in_lds = [&]() -> bool {
-    if constexpr (kGreenJastrow) return (nchunks_arg & 2u) != 0u;
-    else return lambda != 0.0;
-  };
+  // `chunks` = workgroups per walker; 1 whenever GREEN.  Only the row with the Jastrow factor takes the 1 at compile time: a run-time count
+  // costs that form 6-9 spilled SGPRs, a compile-time 1 in every GREEN form costs <3, true, 0, true> 14 spilled VGPRs
+  // (profiles/eloc_rbm_args_resource_usage.txt).
+  // `pairs_in_lds` is a `bool`, read where it is used, by measurement too: as a `uint32_t`, in another place of the list, or taken into a
+  // local at the top, the JASTROW forms compile with fewer spills and pynqs_eloc_jrbm runs 1-1.4 % slower (same file).
+  const uint32_t nchunks = (GREEN && JASTROW) ? 1u : chunks;
   // no static __shared__ here: with the dynamic region at LDS address 0 the row offsets below are the addresses and
   // the ds_read immediates carry the rest (a static in front costs one v_add per read)
   extern __shared__ __attribute__((aligned(16))) unsigned char smem[];
@@ -305,7 +298,7 @@ __global__ __launch_bounds__(1024, 4) void eloc_rbm_kernel(const uint64_t *__res
         da = exp(-4.0 * x * a);
       } else if constexpr (JASTROW) {
         // r_o = sum_j S_jo x_j (S is symmetric: column o, so that consecutive lanes read consecutive words; S_oo = 0), 16 loads in flight
-        const double *__restrict__ S = jas_table();
+        const double *__restrict__ S = jastrow;
         double r = 0.0;
 #pragma unroll 16
         for (int j = 0; j < sorb; ++j) {
@@ -324,17 +317,17 @@ __global__ __launch_bounds__(1024, 4) void eloc_rbm_kernel(const uint64_t *__res
     if constexpr (FLAVOUR == kRbmTanh) R.Aq[o] = da;
   }
   if constexpr (JASTROW) {
-    // the walker's pair factors in LDS (jas_pairs_in_lds), behind the kernel's own layout (where they are is worked out again at each use:
+    // the walker's pair factors in LDS (pairs_in_lds), behind the kernel's own layout (where they are is worked out again at each use:
     // nothing of it lives across the hidden-unit loop)
     // (one and two words only: at three the triangle is 66 KiB and more and never chosen, and the branch alone costs that
     // instantiation a spill inside the hidden-unit loop)
     double *jP = reinterpret_cast<double *>(smem + lds_bytes_rbm(p, rl, hw));
-    if (LEN < 3 && jas_pairs_in_lds()) {  // P[a (a - 1) / 2 + b] = exp(4 S_ab x_a x_b), b < a: a wave per row, consecutive lanes read consecutive words
+    if (LEN < 3 && pairs_in_lds) {  // P[a (a - 1) / 2 + b] = exp(4 S_ab x_a x_b), b < a: a wave per row, consecutive lanes read consecutive words
       const uint32_t n2 = (uint32_t)jastrow_pairs(sorb);
       for (int a = 1 + wave; a < sorb; a += nwaves) {
         const uint32_t xa = bit_of<LEN>(wk.w, a);
         for (int b = lane; b < a; b += 64)
-          jP[(uint32_t)(a * (a - 1) / 2 + b)] = jas_table()[(bit_of<LEN>(wk.w, b) == xa ? n2 : 2u * n2) + (uint32_t)a * (uint32_t)sorb + (uint32_t)b];
+          jP[(uint32_t)(a * (a - 1) / 2 + b)] = jastrow[(bit_of<LEN>(wk.w, b) == xa ? n2 : 2u * n2) + (uint32_t)a * (uint32_t)sorb + (uint32_t)b];
       }
     }
   }
@@ -525,7 +518,7 @@ __global__ __launch_bounds__(1024, 4) void eloc_rbm_kernel(const uint64_t *__res
             }
           }
         };
-        if (LEN < 3 && jas_pairs_in_lds()) {  // (workgroup-uniform)
+        if (LEN < 3 && pairs_in_lds) {  // (workgroup-uniform)
           const double *jP = reinterpret_cast<const double *>(smem + lds_bytes_rbm(p, rl, hw));
           join_pairs([&](uint32_t a, uint32_t b, int, int) {
             const uint32_t hi = max(a, b), lo = min(a, b);
@@ -540,7 +533,7 @@ __global__ __launch_bounds__(1024, 4) void eloc_rbm_kernel(const uint64_t *__res
           }
           const uint32_t n2 = (uint32_t)jastrow_pairs(sorb);
           join_pairs([&](uint32_t a, uint32_t b, int ka, int kb) {
-            return jas_table()[((((occ >> ka) ^ (occ >> kb)) & 1u) ? 2u * n2 : n2) + a * (uint32_t)sorb + b];
+            return jastrow[((((occ >> ka) ^ (occ >> kb)) & 1u) ? 2u * n2 : n2) + a * (uint32_t)sorb + b];
           });
         }
       }
@@ -641,7 +634,7 @@ __global__ __launch_bounds__(1024, 4) void eloc_rbm_kernel(const uint64_t *__res
     if constexpr (JASTROW) {  // x^T M x = tr M + sum_{i<j} S_ij x_i x_j, the sum apart from lnpsi: at most sorb - 1 of its additions round
 #pragma unroll
       for (int o = 32; o > 0; o >>= 1) xsx += __shfl_xor(xsx, o);
-      xmx = rbm_over_waves(xsx, T.red, tid, nwaves) + jas_table()[3 * jastrow_pairs(sorb)];
+      xmx = rbm_over_waves(xsx, T.red, tid, nwaves) + jastrow[3 * jastrow_pairs(sorb)];
     }
     if (tid == 0) {
       if constexpr (JASTROW) psi[walker] = exp(s + xmx);
@@ -681,35 +674,84 @@ static RbmShape rbm_windowed_shape(uint32_t ntiles) {
   return s;
 }
 
+// whether all hidden units of q' fit the LDS: the resident form (the only one with the Jastrow factor: pynqs_eloc_jrbm_supported)
+static bool rbm_resident(const SDParams &p, const RbmLayout &rl) { return lds_bytes_rbm(p, rl, (uint32_t)rl.Hloop) <= kRbmMaxLds; }
+
 // hidden units resident in LDS: all of them (rl.Hloop) when that fits, else the largest multiple of 8 that keeps the
 // workgroup within window_lds (at least 8); 0 if not even that fits
 static uint32_t rbm_window(const SDParams &p, const RbmLayout &rl, size_t window_lds) {
-  if (lds_bytes_rbm(p, rl, (uint32_t)rl.Hloop) <= kRbmMaxLds) return (uint32_t)rl.Hloop;
+  if (rbm_resident(p, rl)) return (uint32_t)rl.Hloop;
   const size_t other = lds_bytes_rbm(p, rl, 0u) - rbm_region_bytes(p, 0u);
   for (uint32_t hw = 256; hw >= 8; hw -= 8)
     if (other + rbm_region_bytes(p, hw) <= (hw > 8 ? window_lds : kRbmMaxLds)) return hw;
   return 0;
 }
 
-// The form a launch takes: workgroups per walker (rbm_chunks), the windowed kernel's shape, the hidden units resident in LDS.
-struct RbmForm {
-  uint32_t nchunks, hw;
-  RbmShape shape;
-};
-static RbmForm rbm_form(const SDParams &p, const RbmLayout &rl, const RbmBlocks<kRbmFB> &B, int64_t nbatch, bool green) {
-  RbmForm f;
-  f.nchunks = green ? 1 : rbm_chunks(B.ntiles, nbatch);  // (the Green's-function row finishes its diagonal in the kernel: one workgroup per walker)
-  f.shape = rbm_windowed_shape(B.ntiles / f.nchunks);
-  f.hw = rbm_window(p, rl, f.shape.window_lds);
-  return f;
+// JASTROW: the walker's pair factors as a triangle in LDS behind the kernel's own layout (4 sorb (sorb - 1) bytes) as long as three
+// workgroups still fit a CU (or as many as fitted without it, if fewer), else read from the table in L2.  Fe2S2: 35 + 6.1 KiB, three
+// workgroups per CU instead of four (12 of the 16 waves the registers allow).  PYNQS_JRBM_PAIRS=lds / l2 (read at every call) forces
+// one of them where it fits.
+static size_t jrbm_pairs_bytes(const SDParams &p) { return 8 * ((size_t)p.sorb * (size_t)(p.sorb - 1) / 2); }
+static bool jrbm_pairs_in_lds(const SDParams &p, const RbmLayout &rl) {
+  const char *env = getenv("PYNQS_JRBM_PAIRS");
+  const size_t base = lds_bytes_rbm(p, rl, (uint32_t)rl.Hloop), with = base + jrbm_pairs_bytes(p);
+  if (p.sorb > 128 || with > kRbmMaxLds || (env && !strcmp(env, "l2"))) return false;  // (the kernel has the LDS form for one and two words)
+  if (env && !strcmp(env, "lds")) return true;
+  const size_t per_cu = 160 * 1024 / (base + 256), per_cu_with = 160 * 1024 / (with + 256);
+  return per_cu_with >= (per_cu < 3 ? per_cu : 3);
 }
 
-extern "C" int pynqs_eloc_rbm_form(int64_t nbatch, int sorb, int nele, int noA, int noB, int nhidden, int green) {
+// A launch of eloc_rbm_kernel on nbatch walkers, worked out here and nowhere else: the launcher launches it and the host entries
+// (pynqs_eloc_rbm_form, pynqs_eloc_jrbm_form, pynqs_eloc_rbm_geometry) report it.
+struct RbmLaunch {
+  uint32_t nchunks;   // workgroups per walker (rbm_chunks)
+  uint32_t hw;        // hidden units resident in LDS
+  bool windowed;      // hw < all of them: the windowed kernel, in rbm_windowed_shape's shape
+  bool pairs_in_lds;  // JASTROW: the walker's pair factors behind the kernel's own LDS layout
+  size_t lds;         // bytes of dynamic LDS
+  uint32_t threads;
+  uint64_t grid;
+};
+// false where the launch is not served: the walker tables leave no LDS for the RBM rows, or, with the Jastrow factor (resident form
+// only), sorb x num_hidden is beyond the LDS
+static bool rbm_launch_form(const RbmSystem<RbmLayout> &s, int64_t nbatch, bool green, bool jastrow, RbmLaunch *f) {
+  const uint32_t ntiles = make_rbm_blocks<kRbmFB>(s.p).ntiles;
+  f->nchunks = green ? 1 : rbm_chunks(ntiles, nbatch);  // (the Green's-function row finishes its diagonal in the kernel: one workgroup per walker)
+  const RbmShape shape = rbm_windowed_shape(ntiles / f->nchunks);
+  f->hw = rbm_window(s.p, s.rl, shape.window_lds);
+  f->windowed = !rbm_resident(s.p, s.rl);
+  if (f->hw == 0 || (jastrow && f->windowed)) return false;
+  f->pairs_in_lds = jastrow && jrbm_pairs_in_lds(s.p, s.rl);
+  f->lds = lds_bytes_rbm(s.p, s.rl, f->hw) + (f->pairs_in_lds ? jrbm_pairs_bytes(s.p) : 0);
+  // (3-wave workgroups divide Fe2S2's 9 tiles evenly but leave only 12 waves per CU -- LDS allows 4 workgroups --
+  // and were 8 % slower at 80 hidden units; the kernel itself runs with any multiple of 64 threads >= 128)
+  f->threads = f->windowed ? shape.threads : rbm_resident_threads(f->lds, ntiles / f->nchunks, 1024, rbm_block_env());
+  f->grid = (uint64_t)nbatch * f->nchunks;
+  return true;
+}
+
+// the same from an entry point's arguments; the form as the _form entries report it: bit 0 = windowed, bit 1 = chunked, bit 2 = pairs in LDS
+static bool rbm_launch_query(int64_t nbatch, int sorb, int nele, int noA, int noB, int nhidden, bool green, bool jastrow, RbmLaunch *f) {
   RbmSystem<RbmLayout> s;
-  if (nbatch < 1 || rbm_system(sorb, nele, noA, noB, nhidden, make_rbm_layout, &s)) return -1;
-  const RbmForm f = rbm_form(s.p, s.rl, make_rbm_blocks<kRbmFB>(s.p), nbatch, green != 0);
-  if (f.hw == 0) return -1;
-  return (f.hw < (uint32_t)s.rl.Hloop ? 1 : 0) | (f.nchunks > 1 ? 2 : 0);
+  return nbatch >= 1 && !rbm_system(sorb, nele, noA, noB, nhidden, make_rbm_layout, &s) && rbm_launch_form(s, nbatch, green, jastrow, f);
+}
+static int rbm_form_bits(const RbmLaunch &f) { return (f.windowed ? 1 : 0) | (f.nchunks > 1 ? 2 : 0) | (f.pairs_in_lds ? 4 : 0); }
+
+extern "C" int pynqs_eloc_rbm_form(int64_t nbatch, int sorb, int nele, int noA, int noB, int nhidden, int green) {
+  RbmLaunch f;
+  return rbm_launch_query(nbatch, sorb, nele, noA, noB, nhidden, green != 0, false, &f) ? rbm_form_bits(f) : -1;
+}
+
+extern "C" int pynqs_eloc_jrbm_form(int64_t nbatch, int sorb, int nele, int noA, int noB, int nhidden) {
+  RbmLaunch f;
+  return rbm_launch_query(nbatch, sorb, nele, noA, noB, nhidden, false, true, &f) ? rbm_form_bits(f) : -1;
+}
+
+extern "C" int pynqs_eloc_rbm_geometry(int64_t nbatch, int sorb, int nele, int noA, int noB, int nhidden, int green, int jastrow, int64_t *out6) {
+  RbmLaunch f;
+  if (!out6 || nbatch > 0x7fffffffll || !rbm_launch_query(nbatch, sorb, nele, noA, noB, nhidden, green != 0, jastrow != 0, &f)) return -1;
+  out6[0] = (int64_t)f.grid, out6[1] = f.threads, out6[2] = (int64_t)f.lds, out6[3] = f.hw, out6[4] = f.nchunks, out6[5] = f.pairs_in_lds ? 1 : 0;
+  return 0;
 }
 
 extern "C" int64_t pynqs_rbm_table_bytes(int sorb, int nhidden) {
@@ -737,145 +779,128 @@ extern "C" int pynqs_rbm_table_build(const double *weights, const double *hidden
   return check_launch("rbm_table_build");
 }
 
-static int eloc_rbm_impl(const uint64_t *bra, int64_t nbatch, int sorb, int nele, int noA, int noB, const void *plan,
-                         const void *rbm_table, int nhidden, int flavour, double *eloc, double *psi, double lambda, double *green,
-                         uint8_t *clamped, void *stream, bool sgn = false) {  // sgn: the SIGNED form (every column times sigma_k; never with green)
-  pynqs::DeviceScope device_scope_(bra);
-  if (flavour < PYNQS_RBM_REAL || flavour > PYNQS_RBM_PHASE) return set_error(PYNQS_EINVAL, "unknown RBM flavour");
-  if (green && (flavour == PYNQS_RBM_PHASE || !clamped)) return set_error(PYNQS_EINVAL, "the Green's-function row needs a real-valued flavour");
+extern "C" int pynqs_eloc_jrbm_supported(int sorb, int nele, int noA, int noB, int nhidden) {  // the resident form only
+  RbmSystem<RbmLayout> s;
+  if (rbm_system(sorb, nele, noA, noB, nhidden, make_rbm_layout, &s)) return 0;
+  return rbm_resident(s.p, s.rl) ? 1 : 0;
+}
+
+// ---- the one launcher of eloc_rbm_kernel.  RbmCall: an entry point's pointers and scalars; RbmMode: which amplitude and which sums.
+struct RbmCall {  // (in the order of the entry points' own arguments)
+  const uint64_t *bra;
+  int64_t nbatch;
+  int sorb, nele, noA, noB;
+  const void *plan, *rbm_table, *jastrow_table;  // jastrow_table: read with kRbmJastrow only
+  int nhidden;
+  double *eloc, *psi;
+  void *stream;
+  double lambda = 0.0;  // the row's three, read with kRbmGreen only
+  double *green = nullptr;
+  uint8_t *clamped = nullptr;
+};
+enum : unsigned { kRbmSigned = 1, kRbmGreen = 2, kRbmJastrow = 4 };
+struct RbmMode {
+  int flavour;    // PYNQS_RBM_REAL / _TANH / _PHASE (the kernel's kRbmReal / kRbmTanh / kRbmPhase)
+  unsigned what;  // kRbmSigned: every column times sigma_k; kRbmGreen: the fixed-node row; kRbmJastrow: the two-body factor
+};
+
+// The 57 instantiations: three word counts x (resident, windowed) x (three flavours plain and SIGNED, two real-valued ones with GREEN),
+// and three word counts x (plain, SIGNED, GREEN) with JASTROW (real flavour, resident).  nullptr for every other combination.
+using RbmKernel = decltype(&eloc_rbm_kernel<1, false, kRbmReal, false>);
+template <int LEN, bool WINDOWED, int FLAVOUR>
+static RbmKernel rbm_kernel_of(unsigned what) {
+  constexpr bool kCanJastrow = FLAVOUR == kRbmReal && !WINDOWED, kCanGreen = FLAVOUR != kRbmPhase;
+  switch (what) {
+    case 0: return eloc_rbm_kernel<LEN, WINDOWED, FLAVOUR, false>;
+    case kRbmSigned: return eloc_rbm_kernel<LEN, WINDOWED, FLAVOUR, false, false, true>;
+    case kRbmGreen: if constexpr (kCanGreen) return eloc_rbm_kernel<LEN, WINDOWED, FLAVOUR, true>; break;
+    case kRbmJastrow: if constexpr (kCanJastrow) return eloc_rbm_kernel<LEN, false, kRbmReal, false, true>; break;
+    case kRbmJastrow | kRbmSigned: if constexpr (kCanJastrow) return eloc_rbm_kernel<LEN, false, kRbmReal, false, true, true>; break;
+    case kRbmJastrow | kRbmGreen: if constexpr (kCanJastrow) return eloc_rbm_kernel<LEN, false, kRbmReal, true, true>; break;
+  }
+  return nullptr;
+}
+template <int LEN, bool WINDOWED>
+static RbmKernel rbm_kernel_of(const RbmMode &m) {
+  return m.flavour == PYNQS_RBM_REAL   ? rbm_kernel_of<LEN, WINDOWED, kRbmReal>(m.what)
+         : m.flavour == PYNQS_RBM_TANH ? rbm_kernel_of<LEN, WINDOWED, kRbmTanh>(m.what)
+                                       : rbm_kernel_of<LEN, WINDOWED, kRbmPhase>(m.what);
+}
+static RbmKernel rbm_kernel(int len, bool windowed, const RbmMode &m) {
+  DISPATCH_LEN(len, return windowed ? rbm_kernel_of<LEN, true>(m) : rbm_kernel_of<LEN, false>(m));
+  return nullptr;
+}
+
+static int eloc_rbm_launch(const RbmCall &c, const RbmMode &m) {
+  pynqs::DeviceScope device_scope_(c.bra);
+  const bool green = m.what & kRbmGreen, jastrow = m.what & kRbmJastrow;
+  if (m.flavour < PYNQS_RBM_REAL || m.flavour > PYNQS_RBM_PHASE) return set_error(PYNQS_EINVAL, "unknown RBM flavour");
+  if (green && (m.flavour == PYNQS_RBM_PHASE || !c.green || !c.clamped))
+    return set_error(PYNQS_EINVAL, "the Green's-function row needs a real-valued flavour, green and clamped");
   RbmSystem<RbmLayout> sys;
-  if (const char *bad = rbm_system(sorb, nele, noA, noB, nhidden, make_rbm_layout, &sys)) return set_error(PYNQS_EINVAL, bad);
-  if (const int rc = rbm_batch(nbatch, 0x7fffffffll, bra, plan, rbm_table, eloc)) return rc;
-  if (nbatch == 0) return PYNQS_OK;
+  if (const char *bad = rbm_system(c.sorb, c.nele, c.noA, c.noB, c.nhidden, make_rbm_layout, &sys)) return set_error(PYNQS_EINVAL, bad);
+  if (const int rc = rbm_batch(c.nbatch, 0x7fffffffll, c.bra, c.plan, c.rbm_table, c.eloc)) return rc;
+  if (c.nbatch == 0) return PYNQS_OK;
+  if (jastrow && !c.jastrow_table) return set_error(PYNQS_EINVAL, "null pointer");
+  RbmLaunch f;
+  if (!rbm_launch_form(sys, c.nbatch, green, jastrow, &f))
+    return set_error(PYNQS_EINVAL, "eloc_rbm: no LDS for the RBM rows of this system (pynqs_eloc_rbm_supported / pynqs_eloc_jrbm_supported)");
+  const RbmKernel kernel = rbm_kernel((c.sorb - 1) / 64 + 1, f.windowed, m);
+  if (!kernel) return set_error(PYNQS_EINVAL, "eloc_rbm: no kernel for this flavour and mode");
+  hipStream_t st = (hipStream_t)c.stream;
+  uint32_t checked;  // (rbm_grid: f.grid within the range of a launch, and eloc cleared for a chunked one)
+  if (const int rc = rbm_grid(c.nbatch, f.nchunks, c.eloc, m.flavour == PYNQS_RBM_PHASE ? 16 : 8, st, &checked)) return rc;
   const auto &[p, pl, rl] = sys;
-  const RbmBlocks<kRbmFB> B = make_rbm_blocks<kRbmFB>(p);
-  const RbmForm form = rbm_form(p, rl, B, nbatch, green != nullptr);
-  const uint32_t nchunks = form.nchunks, hw = form.hw;
-  if (hw == 0) return set_error(PYNQS_EINVAL, "the walker tables of this system leave no LDS for the RBM rows");
-  const bool windowed = hw < (uint32_t)rl.Hloop;
-  const size_t lds = lds_bytes_rbm(p, rl, hw);
-  hipStream_t st = (hipStream_t)stream;
-  uint32_t grid;
-  if (const int rc = rbm_grid(nbatch, nchunks, eloc, flavour == PYNQS_RBM_PHASE ? 16 : 8, st, &grid)) return rc;
-  const int len = (sorb - 1) / 64 + 1;
-  // (3-wave workgroups divide Fe2S2's 9 tiles evenly but leave only 12 waves per CU -- LDS allows 4 workgroups --
-  // and were 8 % slower at 80 hidden units; the kernel itself runs with any multiple of 64 threads >= 128)
-  const uint32_t threads = windowed ? form.shape.threads : rbm_resident_threads(lds, B.ntiles / nchunks, 1024, rbm_block_env());
-  int rc = PYNQS_OK;
-#define PYNQS_RBM_LAUNCH(W, F, G)                                                                                                            \
-  rc = rbm_launch("eloc_rbm", eloc_rbm_kernel<LEN, W, F, G>, grid, threads, lds, st, bra, p, pl, rl, B, nchunks, hw, (const double *)plan, \
-                  (const double *)rbm_table, eloc, psi, lambda, green, clamped, (const double *)nullptr)
-#define PYNQS_RBM_LAUNCH_SIGNED(W, F)                                                                                                        \
-  rc = rbm_launch("eloc_rbm_signed", eloc_rbm_kernel<LEN, W, F, false, false, true>, grid, threads, lds, st, bra, p, pl, rl, B, nchunks, hw, \
-                  (const double *)plan, (const double *)rbm_table, eloc, psi, 0.0, (double *)nullptr, (uint8_t *)nullptr, (const double *)nullptr)
-#define PYNQS_RBM_FLAVOURS(W)                                                \
-  do {                                                                       \
-    if (sgn && flavour == PYNQS_RBM_REAL) PYNQS_RBM_LAUNCH_SIGNED(W, kRbmReal);  \
-    else if (sgn && flavour == PYNQS_RBM_TANH) PYNQS_RBM_LAUNCH_SIGNED(W, kRbmTanh);  \
-    else if (sgn) PYNQS_RBM_LAUNCH_SIGNED(W, kRbmPhase);                     \
-    else if (green && flavour == PYNQS_RBM_REAL) PYNQS_RBM_LAUNCH(W, kRbmReal, true);  \
-    else if (green) PYNQS_RBM_LAUNCH(W, kRbmTanh, true);                     \
-    else if (flavour == PYNQS_RBM_REAL) PYNQS_RBM_LAUNCH(W, kRbmReal, false); \
-    else if (flavour == PYNQS_RBM_TANH) PYNQS_RBM_LAUNCH(W, kRbmTanh, false); \
-    else PYNQS_RBM_LAUNCH(W, kRbmPhase, false);                              \
-  } while (0)
-  DISPATCH_LEN(len, {
-    if (windowed) PYNQS_RBM_FLAVOURS(true);
-    else PYNQS_RBM_FLAVOURS(false);
-  });
-#undef PYNQS_RBM_FLAVOURS
-#undef PYNQS_RBM_LAUNCH_SIGNED
-#undef PYNQS_RBM_LAUNCH
-  return rc;
+  return rbm_launch("eloc_rbm", kernel, (uint32_t)f.grid, f.threads, f.lds, st, c.bra, p, pl, rl, make_rbm_blocks<kRbmFB>(p), f.nchunks, f.hw,
+                    (const double *)c.plan, (const double *)c.rbm_table, c.eloc, c.psi, green ? c.lambda : 0.0, green ? c.green : nullptr,
+                    green ? c.clamped : nullptr, jastrow ? (const double *)c.jastrow_table : nullptr, f.pairs_in_lds);
 }
 
 extern "C" int pynqs_eloc_rbm_flavour(const uint64_t *bra, int64_t nbatch, int sorb, int nele, int noA, int noB, const void *plan,
                                       const void *rbm_table, int nhidden, int flavour, double *eloc, double *psi, void *stream) {
-  return eloc_rbm_impl(bra, nbatch, sorb, nele, noA, noB, plan, rbm_table, nhidden, flavour, eloc, psi, 0.0, nullptr, nullptr, stream);
+  return eloc_rbm_launch({bra, nbatch, sorb, nele, noA, noB, plan, rbm_table, nullptr, nhidden, eloc, psi, stream}, {flavour, 0});
 }
 
 extern "C" int pynqs_eloc_rbm(const uint64_t *bra, int64_t nbatch, int sorb, int nele, int noA, int noB, const void *plan,
                               const void *rbm_table, int nhidden, double *eloc, double *psi, void *stream) {
-  return eloc_rbm_impl(bra, nbatch, sorb, nele, noA, noB, plan, rbm_table, nhidden, PYNQS_RBM_REAL, eloc, psi, 0.0, nullptr, nullptr, stream);
+  return eloc_rbm_launch({bra, nbatch, sorb, nele, noA, noB, plan, rbm_table, nullptr, nhidden, eloc, psi, stream}, {PYNQS_RBM_REAL, 0});
+}
+
+extern "C" int pynqs_eloc_rbm_signed(const uint64_t *bra, int64_t nbatch, int sorb, int nele, int noA, int noB, const void *plan,
+                                     const void *rbm_table, int nhidden, int flavour, double *eloc, double *psi, void *stream) {
+  return eloc_rbm_launch({bra, nbatch, sorb, nele, noA, noB, plan, rbm_table, nullptr, nhidden, eloc, psi, stream}, {flavour, kRbmSigned});
 }
 
 extern "C" int pynqs_green_rbm(const uint64_t *bra, int64_t nbatch, int sorb, int nele, int noA, int noB, const void *plan,
                                const void *rbm_table, int nhidden, int flavour, double lambda, double *eloc, double *psi, double *green,
                                uint8_t *clamped, void *stream) {
-  if (!green || !clamped) return set_error(PYNQS_EINVAL, "null pointer");
-  return eloc_rbm_impl(bra, nbatch, sorb, nele, noA, noB, plan, rbm_table, nhidden, flavour, eloc, psi, lambda, green, clamped, stream);
+  return eloc_rbm_launch({bra, nbatch, sorb, nele, noA, noB, plan, rbm_table, nullptr, nhidden, eloc, psi, stream, lambda, green, clamped},
+                         {flavour, kRbmGreen});
 }
 
-// ---- the same with the two-body Jastrow factor exp(x^T M x) on the real RBM (JASTROW): the resident form only, one workgroup per walker
-// or chunked by the shared rules of rbm_tiles.h; the LDS, the cut into chunks and the workgroup size are those of pynqs_eloc_rbm
-static bool jrbm_resident(const RbmSystem<RbmLayout> &s) { return lds_bytes_rbm(s.p, s.rl, (uint32_t)s.rl.Hloop) <= kRbmMaxLds; }
-
-// The walker's pair factors as a triangle in LDS behind the kernel's own layout (4 sorb (sorb - 1) bytes) as long as three workgroups
-// still fit a CU (or as many as fitted without it, if fewer), else read from the table in L2.  Fe2S2: 35 + 6.1 KiB, three workgroups
-// per CU instead of four (12 of the 16 waves the registers allow).  PYNQS_JRBM_PAIRS=lds / l2 forces one of them where it fits.
-static size_t jrbm_pairs_bytes(const SDParams &p) { return 8 * ((size_t)p.sorb * (size_t)(p.sorb - 1) / 2); }
-static bool jrbm_pairs_in_lds(const RbmSystem<RbmLayout> &s) {
-  const char *env = getenv("PYNQS_JRBM_PAIRS");
-  const size_t base = lds_bytes_rbm(s.p, s.rl, (uint32_t)s.rl.Hloop), with = base + jrbm_pairs_bytes(s.p);
-  if (s.p.sorb > 128 || with > kRbmMaxLds || (env && !strcmp(env, "l2"))) return false;  // (the kernel has the LDS form for one and two words)
-  if (env && !strcmp(env, "lds")) return true;
-  const size_t per_cu = 160 * 1024 / (base + 256), per_cu_with = 160 * 1024 / (with + 256);
-  return per_cu_with >= (per_cu < 3 ? per_cu : 3);
-}
-
-extern "C" int pynqs_eloc_jrbm_supported(int sorb, int nele, int noA, int noB, int nhidden) {
-  RbmSystem<RbmLayout> s;
-  if (rbm_system(sorb, nele, noA, noB, nhidden, make_rbm_layout, &s)) return 0;
-  return jrbm_resident(s) ? 1 : 0;
-}
-
-extern "C" int pynqs_eloc_jrbm_form(int64_t nbatch, int sorb, int nele, int noA, int noB, int nhidden) {
-  RbmSystem<RbmLayout> s;
-  if (nbatch < 1 || rbm_system(sorb, nele, noA, noB, nhidden, make_rbm_layout, &s) || !jrbm_resident(s)) return -1;
-  return (rbm_chunks(make_rbm_blocks<kRbmFB>(s.p).ntiles, nbatch) > 1 ? 2 : 0) | (jrbm_pairs_in_lds(s) ? 4 : 0);
-}
-
-static int eloc_jrbm_impl(const uint64_t *bra, int64_t nbatch, int sorb, int nele, int noA, int noB, const void *plan, const void *rbm_table,
-                          const void *jastrow_table, int nhidden, double *eloc, double *psi, void *stream, bool sgn) {
-  pynqs::DeviceScope device_scope_(bra);
-  RbmSystem<RbmLayout> sys;
-  if (const char *bad = rbm_system(sorb, nele, noA, noB, nhidden, make_rbm_layout, &sys)) return set_error(PYNQS_EINVAL, bad);
-  if (const int rc = rbm_batch(nbatch, 0x7fffffffll, bra, plan, rbm_table, eloc)) return rc;
-  if (nbatch == 0) return PYNQS_OK;
-  if (!jastrow_table) return set_error(PYNQS_EINVAL, "null pointer");
-  if (!jrbm_resident(sys)) return set_error(PYNQS_EINVAL, "eloc_jrbm: sorb x nhidden beyond the LDS (pynqs_eloc_jrbm_supported)");
-  const auto &[p, pl, rl] = sys;
-  const RbmBlocks<kRbmFB> B = make_rbm_blocks<kRbmFB>(p);
-  const uint32_t nchunks = rbm_chunks(B.ntiles, nbatch), hw = (uint32_t)rl.Hloop;
-  const bool pairs_in_lds = jrbm_pairs_in_lds(sys);
-  const size_t lds = lds_bytes_rbm(p, rl, hw) + (pairs_in_lds ? jrbm_pairs_bytes(p) : 0);
-  hipStream_t st = (hipStream_t)stream;
-  uint32_t grid;
-  if (const int rc = rbm_grid(nbatch, nchunks, eloc, 8, st, &grid)) return rc;
-  const int len = (sorb - 1) / 64 + 1;
-  const uint32_t threads = rbm_resident_threads(lds, B.ntiles / nchunks, 1024, rbm_block_env());
-  // (the table travels in the kernel's `green` argument, which it only reads in this form, and `lambda` says where the pair factors are)
-  double *jas = const_cast<double *>(static_cast<const double *>(jastrow_table));
-  int rc = PYNQS_OK;
-#define PYNQS_JRBM_LAUNCH                                                                                                                  \
-  rc = rbm_launch("eloc_jrbm", eloc_rbm_kernel<LEN, false, kRbmReal, false, true>, grid, threads, lds, st, bra, p, pl, rl, B, nchunks, hw, \
-                  (const double *)plan, (const double *)rbm_table, eloc, psi, pairs_in_lds ? 1.0 : 0.0, jas, (uint8_t *)nullptr, (const double *)nullptr)
-#define PYNQS_JRBM_LAUNCH_SIGNED                                                                                                            \
-  rc = rbm_launch("eloc_jrbm_signed", eloc_rbm_kernel<LEN, false, kRbmReal, false, true, true>, grid, threads, lds, st, bra, p, pl, rl, B, nchunks, \
-                  hw, (const double *)plan, (const double *)rbm_table, eloc, psi, pairs_in_lds ? 1.0 : 0.0, jas, (uint8_t *)nullptr,           \
-                  (const double *)nullptr)
-  DISPATCH_LEN(len, {
-    if (sgn) PYNQS_JRBM_LAUNCH_SIGNED;
-    else PYNQS_JRBM_LAUNCH;
-  });
-#undef PYNQS_JRBM_LAUNCH_SIGNED
-#undef PYNQS_JRBM_LAUNCH
-  return rc;
-}
-
+// ---- the same with the two-body Jastrow factor exp(x^T M x) on the real RBM (JASTROW): the resident form only; the LDS (plus the
+// walker's triangle), the cut into chunks and the workgroup size are those of pynqs_eloc_rbm
 extern "C" int pynqs_eloc_jrbm(const uint64_t *bra, int64_t nbatch, int sorb, int nele, int noA, int noB, const void *plan,
                                const void *rbm_table, const void *jastrow_table, int nhidden, double *eloc, double *psi, void *stream) {
-  return eloc_jrbm_impl(bra, nbatch, sorb, nele, noA, noB, plan, rbm_table, jastrow_table, nhidden, eloc, psi, stream, false);
+  return eloc_rbm_launch({bra, nbatch, sorb, nele, noA, noB, plan, rbm_table, jastrow_table, nhidden, eloc, psi, stream}, {PYNQS_RBM_REAL, kRbmJastrow});
+}
+
+extern "C" int pynqs_eloc_jrbm_signed(const uint64_t *bra, int64_t nbatch, int sorb, int nele, int noA, int noB, const void *plan,
+                                      const void *rbm_table, const void *jastrow_table, int nhidden, double *eloc, double *psi, void *stream) {
+  return eloc_rbm_launch({bra, nbatch, sorb, nele, noA, noB, plan, rbm_table, jastrow_table, nhidden, eloc, psi, stream},
+                         {PYNQS_RBM_REAL, kRbmJastrow | kRbmSigned});
+}
+
+// The fixed-node Green's row with the Jastrow factor (GREEN and JASTROW): pynqs_green_rbm's row for pynqs_eloc_jrbm's amplitude, one
+// workgroup per walker.  A missing table and a system that is not served are refused for an empty batch too, which the launcher
+// (empty batch: PYNQS_OK before it looks at the form) does not do: hence the check here, by the launcher's own rule (rbm_resident).
+extern "C" int pynqs_green_jrbm(const uint64_t *bra, int64_t nbatch, int sorb, int nele, int noA, int noB, const void *plan,
+                                const void *rbm_table, const void *jastrow_table, int nhidden, double lambda, double *eloc, double *psi,
+                                double *green, uint8_t *clamped, void *stream) {
+  if (!jastrow_table || !pynqs_eloc_jrbm_supported(sorb, nele, noA, noB, nhidden))
+    return set_error(PYNQS_EINVAL, "green_jrbm: null pointer, or sorb x nhidden beyond the LDS (pynqs_eloc_jrbm_supported)");
+  return eloc_rbm_launch({bra, nbatch, sorb, nele, noA, noB, plan, rbm_table, jastrow_table, nhidden, eloc, psi, stream, lambda, green, clamped},
+                         {PYNQS_RBM_REAL, kRbmJastrow | kRbmGreen});
 }
 
 // ---- the spin-flip-projected local energy (vmc/energy/flip.py, _simple_flip; formula and mirrored-table convention: include/pynqs_amd.h):
@@ -913,13 +938,25 @@ static int flip_combine(const uint64_t *bra, int64_t nbatch, int sorb, bool phas
   const int len = (sorb - 1) / 64 + 1;
   const int64_t k = phase ? 2 : 1;
   const uint32_t grid = (uint32_t)((nbatch + kBlock - 1) / kBlock);
-  if (phase)
-    hipLaunchKernelGGL(flip_combine_kernel<true>, dim3(grid), dim3(kBlock), 0, (hipStream_t)stream, bra, nbatch, len, eta, extra_norm, extra_norm_dev,
-                       psi, work, work + k * nbatch, eloc);
-  else
-    hipLaunchKernelGGL(flip_combine_kernel<false>, dim3(grid), dim3(kBlock), 0, (hipStream_t)stream, bra, nbatch, len, eta, extra_norm, extra_norm_dev,
-                       psi, work, work + k * nbatch, eloc);
+  hipLaunchKernelGGL((phase ? flip_combine_kernel<true> : flip_combine_kernel<false>), dim3(grid), dim3(kBlock), 0, (hipStream_t)stream, bra, nbatch,
+                     len, eta, extra_norm, extra_norm_dev, psi, work, work + k * nbatch, eloc);
   return check_launch("flip_combine");
+}
+
+// both flip entries: the plain pass, the SIGNED pass on the mirrored tables into work (Em, behind it psim), then the combine
+static int eloc_flip(const RbmCall &c, RbmMode m, const void *rbm_table_mirror, const void *jastrow_table_mirror, double eta, double extra_norm,
+                     const double *extra_norm_dev, double *work) {
+  const bool jastrow = m.what & kRbmJastrow;
+  if (c.nbatch > 0 && (!rbm_table_mirror || (jastrow && !jastrow_table_mirror) || !c.psi || !work)) return set_error(PYNQS_EINVAL, "null pointer");
+  if (int rc = eloc_rbm_launch(c, m)) return rc;
+  if (c.nbatch == 0) return PYNQS_OK;
+  const int64_t k = m.flavour == PYNQS_RBM_PHASE ? 2 : 1;
+  RbmCall mirror = c;
+  mirror.rbm_table = rbm_table_mirror, mirror.jastrow_table = jastrow_table_mirror, mirror.eloc = work, mirror.psi = work + k * c.nbatch;
+  m.what |= kRbmSigned;
+  if (int rc = eloc_rbm_launch(mirror, m)) return rc;
+  pynqs::DeviceScope device_scope_(c.bra);
+  return flip_combine(c.bra, c.nbatch, c.sorb, k == 2, eta, extra_norm, extra_norm_dev, c.psi, work, c.eloc, c.stream);
 }
 
 extern "C" int pynqs_eloc_rbm_flip_supported(int sorb, int nele, int noA, int noB, int nhidden) {
@@ -930,23 +967,11 @@ extern "C" int pynqs_eloc_rbm_flip_form(int64_t nbatch, int sorb, int nele, int 
   return pynqs_eloc_rbm_form(nbatch, sorb, nele, noA, noB, nhidden, 0);
 }
 
-extern "C" int pynqs_eloc_rbm_signed(const uint64_t *bra, int64_t nbatch, int sorb, int nele, int noA, int noB, const void *plan,
-                                     const void *rbm_table, int nhidden, int flavour, double *eloc, double *psi, void *stream) {
-  return eloc_rbm_impl(bra, nbatch, sorb, nele, noA, noB, plan, rbm_table, nhidden, flavour, eloc, psi, 0.0, nullptr, nullptr, stream, true);
-}
-
 extern "C" int pynqs_eloc_rbm_flip(const uint64_t *bra, int64_t nbatch, int sorb, int nele, int noA, int noB, const void *plan,
                                    const void *rbm_table, const void *rbm_table_mirror, int nhidden, int flavour, double eta, double extra_norm,
                                    const double *extra_norm_dev, double *eloc, double *psi, double *work, void *stream) {
-  if (nbatch > 0 && (!rbm_table_mirror || !psi || !work)) return set_error(PYNQS_EINVAL, "null pointer");
-  if (int rc = eloc_rbm_impl(bra, nbatch, sorb, nele, noA, noB, plan, rbm_table, nhidden, flavour, eloc, psi, 0.0, nullptr, nullptr, stream)) return rc;
-  if (nbatch == 0) return PYNQS_OK;
-  const int64_t k = flavour == PYNQS_RBM_PHASE ? 2 : 1;
-  if (int rc = eloc_rbm_impl(bra, nbatch, sorb, nele, noA, noB, plan, rbm_table_mirror, nhidden, flavour, work, work + k * nbatch, 0.0, nullptr,
-                             nullptr, stream, true))
-    return rc;
-  pynqs::DeviceScope device_scope_(bra);
-  return flip_combine(bra, nbatch, sorb, k == 2, eta, extra_norm, extra_norm_dev, psi, work, eloc, stream);
+  return eloc_flip({bra, nbatch, sorb, nele, noA, noB, plan, rbm_table, nullptr, nhidden, eloc, psi, stream}, {flavour, 0}, rbm_table_mirror, nullptr,
+                   eta, extra_norm, extra_norm_dev, work);
 }
 
 extern "C" int pynqs_eloc_jrbm_flip_supported(int sorb, int nele, int noA, int noB, int nhidden) {
@@ -957,52 +982,10 @@ extern "C" int pynqs_eloc_jrbm_flip_form(int64_t nbatch, int sorb, int nele, int
   return pynqs_eloc_jrbm_form(nbatch, sorb, nele, noA, noB, nhidden);
 }
 
-extern "C" int pynqs_eloc_jrbm_signed(const uint64_t *bra, int64_t nbatch, int sorb, int nele, int noA, int noB, const void *plan,
-                                      const void *rbm_table, const void *jastrow_table, int nhidden, double *eloc, double *psi, void *stream) {
-  return eloc_jrbm_impl(bra, nbatch, sorb, nele, noA, noB, plan, rbm_table, jastrow_table, nhidden, eloc, psi, stream, true);
-}
-
 extern "C" int pynqs_eloc_jrbm_flip(const uint64_t *bra, int64_t nbatch, int sorb, int nele, int noA, int noB, const void *plan,
                                     const void *rbm_table, const void *jastrow_table, const void *rbm_table_mirror,
                                     const void *jastrow_table_mirror, int nhidden, double eta, double extra_norm, const double *extra_norm_dev,
                                     double *eloc, double *psi, double *work, void *stream) {
-  if (nbatch > 0 && (!rbm_table_mirror || !jastrow_table_mirror || !psi || !work)) return set_error(PYNQS_EINVAL, "null pointer");
-  if (int rc = eloc_jrbm_impl(bra, nbatch, sorb, nele, noA, noB, plan, rbm_table, jastrow_table, nhidden, eloc, psi, stream, false)) return rc;
-  if (nbatch == 0) return PYNQS_OK;
-  if (int rc = eloc_jrbm_impl(bra, nbatch, sorb, nele, noA, noB, plan, rbm_table_mirror, jastrow_table_mirror, nhidden, work, work + nbatch, stream, true))
-    return rc;
-  pynqs::DeviceScope device_scope_(bra);
-  return flip_combine(bra, nbatch, sorb, false, eta, extra_norm, extra_norm_dev, psi, work, eloc, stream);
-}
-
-// ---- the fixed-node Green's row with the Jastrow factor (GREEN and JASTROW): pynqs_green_rbm's row for pynqs_eloc_jrbm's amplitude.
-// Resident form, one workgroup per walker; the LDS is the kernel's own layout plus, where jrbm_pairs_in_lds says so, the walker's triangle.
-extern "C" int pynqs_green_jrbm(const uint64_t *bra, int64_t nbatch, int sorb, int nele, int noA, int noB, const void *plan,
-                                const void *rbm_table, const void *jastrow_table, int nhidden, double lambda, double *eloc, double *psi,
-                                double *green, uint8_t *clamped, void *stream) {
-  pynqs::DeviceScope device_scope_(bra);
-  if (!jastrow_table || !green || !clamped) return set_error(PYNQS_EINVAL, "null pointer");
-  RbmSystem<RbmLayout> sys;
-  if (const char *bad = rbm_system(sorb, nele, noA, noB, nhidden, make_rbm_layout, &sys)) return set_error(PYNQS_EINVAL, bad);
-  if (const int rc = rbm_batch(nbatch, 0x7fffffffll, bra, plan, rbm_table, eloc)) return rc;
-  if (!jrbm_resident(sys)) return set_error(PYNQS_EINVAL, "green_jrbm: sorb x nhidden beyond the LDS (pynqs_eloc_jrbm_supported)");
-  if (nbatch == 0) return PYNQS_OK;
-  const auto &[p, pl, rl] = sys;
-  const RbmBlocks<kRbmFB> B = make_rbm_blocks<kRbmFB>(p);
-  const uint32_t hw = (uint32_t)rl.Hloop;
-  const bool pairs_in_lds = jrbm_pairs_in_lds(sys);
-  const size_t lds = lds_bytes_rbm(p, rl, hw) + (pairs_in_lds ? jrbm_pairs_bytes(p) : 0);
-  hipStream_t st = (hipStream_t)stream;
-  uint32_t grid;
-  if (const int rc = rbm_grid(nbatch, 1u, eloc, 8, st, &grid)) return rc;
-  const int len = (sorb - 1) / 64 + 1;
-  const uint32_t threads = rbm_resident_threads(lds, B.ntiles, 1024, rbm_block_env());
-  const uint32_t chunks_and_flag = 1u | (pairs_in_lds ? 2u : 0u);  // (eloc_rbm_kernel: bit 1 = pair factors in LDS; the chunk count is 1)
-  int rc = PYNQS_OK;
-#define PYNQS_GJRBM_LAUNCH                                                                                                                      \
-  rc = rbm_launch("green_jrbm", eloc_rbm_kernel<LEN, false, kRbmReal, true, true>, grid, threads, lds, st, bra, p, pl, rl, B, chunks_and_flag, \
-                  hw, (const double *)plan, (const double *)rbm_table, eloc, psi, lambda, green, clamped, (const double *)jastrow_table)
-  DISPATCH_LEN(len, { PYNQS_GJRBM_LAUNCH; });
-#undef PYNQS_GJRBM_LAUNCH
-  return rc;
+  return eloc_flip({bra, nbatch, sorb, nele, noA, noB, plan, rbm_table, jastrow_table, nhidden, eloc, psi, stream}, {PYNQS_RBM_REAL, kRbmJastrow},
+                   rbm_table_mirror, jastrow_table_mirror, eta, extra_norm, extra_norm_dev, work);
 }

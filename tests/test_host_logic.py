@@ -68,13 +68,16 @@ def test_rbm_launch_decisions_are_unchanged(monkeypatch):
     """Window, chunks, refusal and table sizes of the two fused RBM local-energy kernels (pynqs_eloc_rbm_form / _supported,
     pynqs_eloc_crbm_form / _supported, pynqs_rbm_table_bytes / pynqs_crbm_table_bytes: host logic, no GPU) over systems x hidden units x
     batch sizes x green, against the values recorded before the two kernels' host code was merged (tests/golden/rbm_launch_forms.json,
-    written by tests/golden/make_golden_rbm_launch.py): every value equal, no tolerance."""
+    written by tests/golden/make_golden_rbm_launch.py): every value equal, no tolerance.  The same for the whole launch of the
+    real-parameter kernel (pynqs_eloc_rbm_geometry: workgroups, threads, LDS bytes, resident hidden units, chunks, pair factors in LDS, for
+    green x jastrow) and pynqs_eloc_jrbm_form / _supported, against the values recorded from the three launch paths the kernel had before
+    they became one launcher (tests/golden/rbm_launch_geometry.json)."""
     import importlib.util
     import json
 
     from pynqs_amd import _native as N
 
-    for k in [k for k in os.environ if k.startswith(("PYNQS_RBM_", "PYNQS_CRBM_"))]:
+    for k in [k for k in os.environ if k.startswith(("PYNQS_RBM_", "PYNQS_CRBM_", "PYNQS_JRBM_"))]:
         monkeypatch.delenv(k)
     spec = importlib.util.spec_from_file_location("make_golden_rbm_launch", os.path.join(ROOT, "tests", "golden", "make_golden_rbm_launch.py"))
     rec = importlib.util.module_from_spec(spec)
@@ -86,6 +89,19 @@ def test_rbm_launch_decisions_are_unchanged(monkeypatch):
     for key in ("rbm_table_bytes", "crbm_table_bytes", "rbm_supported", "crbm_supported", "rbm_form", "crbm_form"):
         diff = [i for i, (a, b) in enumerate(zip(got[key], want[key])) if a != b]
         assert len(got[key]) == len(want[key]) and not diff, (key, diff[:10])
+    want = json.load(open(os.path.join(ROOT, "tests", "golden", "rbm_launch_geometry.json")))
+    got = json.loads(json.dumps(rec.record_geometry(N.lib())))
+    assert (got["systems"], got["hidden"], got["nbatch"]) == (want["systems"], want["hidden"], want["nbatch"])
+    assert len(want["jrbm_supported"]) == 6 * 6 and len(want["jrbm_form"]) == 6 * 6 * 5 and len(want["geometry"]) == 6 * 6 * 5 * 2 * 2
+    # the record is not trivial: refusals, every workgroup size, chunked launches and both homes of the pair factors occur in it
+    assert {g[0] for g in want["geometry"]} == {0, -1} and {g[2] for g in want["geometry"]} == {0, 256, 512, 1024}
+    assert {g[6] for g in want["geometry"]} == {0, 1} and any(g[5] > 1 for g in want["geometry"]) and {-1, 0, 2, 4, 6} == set(want["jrbm_form"])
+    for key in ("jrbm_supported", "jrbm_form", "geometry"):
+        diff = [i for i, (a, b) in enumerate(zip(got[key], want[key])) if a != b]
+        assert len(got[key]) == len(want[key]) and not diff, (key, diff[:10])
+    # the form bits are the geometry's: windowed = fewer resident hidden units than the table's, chunked, pairs in LDS
+    for f, g in zip(want["jrbm_form"], want["geometry"][1::4]):  # (green 0, jastrow 1)
+        assert (f == -1) == (g[0] == -1) and (f == -1 or f == (2 if g[5] > 1 else 0) | (4 if g[6] else 0)), (f, g)
 
 
 def test_ss_launch_decisions_are_unchanged(monkeypatch):
