@@ -340,6 +340,33 @@ int pynqs_jrbm_forward(const uint64_t *onv, int64_t n, int sorb, const double *w
 int64_t pynqs_jastrow_grad_workspace(int64_t n, int sorb);
 int pynqs_jastrow_grad(const uint64_t *onv, int64_t n, int sorb, const double *jastrow, const double *prob, const double *eloc,
                        const double *e_total, const double *pow, double *grad_jastrow, double *loss, void *workspace, void *stream);
+/* ---- the Jastrow factor on the DISTINCT x' of a REDUCE front end, from their parents (kernels_jastrow_children.hip): the second, streaming
+ * pass behind pynqs_rbm_forward_children (flavour PYNQS_RBM_REAL), which is neither changed nor aware of it.  Row r of the distinct list is
+ * walker p = parent[r] with the orbitals F flipped, and with q0[p] = x_p^T M x_p = tr M + 1/2 sum_o x_o r_o, r_o = sum_j S_oj x_j (S from the
+ * Jastrow table),
+ *     psi_JRBM(x'_r) = psi_RBM(x'_r) exp(q0[p] + Delta_r),   Delta_r = -2 sum_{i in F} x_i r_i + 4 sum_{i<j in F} S_ij x_i x_j   (x: the parent's).
+ *   pynqs_jastrow_children_table_bytes : [host] nwalkers x (sorb + 1) doubles (r_o for o < sorb, then q0, per parent); -1 on bad arguments
+ *   pynqs_jastrow_children_prepare     : table <- r and q0 of the parents (jastrow_table: pynqs_jastrow_table_build's).  Sums run in a fixed
+ *                                        order (fma chains over the orbitals ascending from 0), no atomics: two calls give the same bits.
+ *   pynqs_jastrow_children_apply       : psi[r] *= exp(q0[p] + Delta_r) for r < min(*count_dev, n) (count_dev may be NULL: all n rows); psi
+ *                                        double[n] as pynqs_rbm_forward_children left it.  F = onv[r] XOR walkers[p] (bits at and above
+ *                                        sorb ignored); the exponent is one sum, one exp per row; no flip: Delta = 0 exactly.  Rows at and
+ *                                        past the count are neither read nor written.  One thread per row, THE GRID IS NOT CAPPED (ceil(n /
+ *                                        256) workgroups, no stride loop), hence no geometry entry.
+ * Strangers, the contract of pynqs_rbm_forward_children's: a row whose parent is outside [0, nwalkers) or that differs from the named
+ * parent in more than four orbitals gets its exponent from scratch on its own bits, tr M + sum_{i<j} S_ij x'_i x'_j; it is never truncated
+ * to four flips and never clamped to walker 0.
+ * Limits: sorb <= 192 (the Jastrow table's), one to three words; the hidden layer is not seen.
+ * Range: the product is formed in double.  Where psi_RBM(x') and the product are both finite non-zero doubles the row obeys
+ *   |psi / psi_exact - 1| <= 2^-53 [(sorb + nhidden + 16) cond(x') + (2 sorb + 4) sum_ij |M_ij| + 2 (sorb + 3) sum_{o in F} R_o
+ *                                   + 28 sum_{i<j in F} |S_ij| + 16],   R_o = sum_j |S_oj|   (tests/jchildren_exact.py counts the roundings;
+ * a stranger: the first two terms + 16).  A row whose RBM amplitude alone is inf, 0 or nan stays so (it is not written): pynqs_jrbm_forward
+ * joins the exponents before the exponential and remains the route for such models. */
+int64_t pynqs_jastrow_children_table_bytes(int64_t nwalkers, int sorb);
+int pynqs_jastrow_children_prepare(const uint64_t *walkers, int64_t nwalkers, int sorb, const void *jastrow_table, void *table,
+                                   void *stream);
+int pynqs_jastrow_children_apply(const uint64_t *onv, int64_t n, const int32_t *count_dev, const int32_t *parent, const uint64_t *walkers,
+                                 int64_t nwalkers, const void *table, const void *jastrow_table, int sorb, double *psi, void *stream);
 
 /* ---- Green's-function Monte-Carlo move: gfmc/walker.py:260-279 (sample_update) in one kernel ---------------
  * green double[n][ncomb] (the fixed-node Green's function row of each walker, >= 0), rand_num double[n] in [0, 1),

@@ -34,7 +34,7 @@ USE_PLAN = True  # route get_comb_hij_fused through the cached integral plan (Fa
 
 __all__ = [
     "tensor_to_onv", "onv_to_tensor", "get_comb_tensor", "get_hij_torch", "get_comb_hij_fused",
-    "wavefunction_lut", "hash_build", "hash_lookup", "HashTable", "RBMTable", "eloc_rbm", "JastrowTable", "eloc_jrbm", "green_jrbm", "jrbm_forward", "eloc_jrbm_supported", "merge_rank_sample", "spin_flip_rand", "check_sorb", "compress_h1e_h2e", "decompress_h1e_h2e", "get_Num_SinglesDoubles",
+    "wavefunction_lut", "hash_build", "hash_lookup", "HashTable", "RBMTable", "eloc_rbm", "JastrowTable", "eloc_jrbm", "green_jrbm", "jrbm_forward", "jrbm_forward_children", "jrbm_forward_children_supported", "eloc_jrbm_supported", "merge_rank_sample", "spin_flip_rand", "check_sorb", "compress_h1e_h2e", "decompress_h1e_h2e", "get_Num_SinglesDoubles",
     "MAX_SORB", "MAX_SORB_LEN", "MAX_NELE",
 ]
 
@@ -858,6 +858,42 @@ def rbm_forward_children(onv: Tensor, parent: Tensor, walkers: Tensor, weights: 
                                                             hb.data_ptr(), vb.data_ptr() if vb is not None else None, H, flav, stamp, int(form),
                                                             psi.data_ptr(), st),
             "pynqs_rbm_forward_children_stamped_form")
+    return psi
+
+
+def jrbm_forward_children_supported(sorb: int, num_hidden: int) -> bool:
+    """whether jrbm_forward_children serves these sizes: the real RBM's children kernel does and the Jastrow table exists for sorb"""
+    return rbm_forward_children_supported(sorb, num_hidden, "real") and N.lib().pynqs_jastrow_table_bytes(sorb) >= 0
+
+
+def jrbm_forward_children(onv: Tensor, parent: Tensor, walkers: Tensor, weights: Tensor, hidden_bias: Tensor, visible_bias: "Tensor | None",
+                          jastrow: "Tensor | None", sorb: int, count: "Tensor | None" = None, out: "Tensor | None" = None,
+                          jastrow_table: "JastrowTable | None" = None) -> Tensor:
+    """psi(x') = exp(a.x' + x'^T M x') prod_h 2cosh(theta_h) on the DISTINCT x' of a REDUCE front end, each from its parent walker:
+    rbm_forward_children(..., "real", count=count, out=out) as it stands, then the Jastrow factor from the parents' r_o = sum_j S_oj x_j and
+    q0 = x^T M x in a second, streaming kernel on the same stream (pynqs_jastrow_children_prepare + _apply; include/pynqs_amd.h for the
+    strangers, the range and the rounding bound).  jastrow: M float64 [sorb, sorb]; jastrow_table: a JastrowTable of M to reuse (M is then
+    not read), else one is built.  count, out: as rbm_forward_children."""
+    psi = rbm_forward_children(onv, parent, walkers, weights, hidden_bias, visible_bias, sorb, "real", count=count, out=out)
+    if jastrow_table is None:
+        if jastrow is None or jastrow.shape != (sorb, sorb):
+            raise RuntimeError("jastrow must be [sorb, sorb]")
+        jastrow_table = JastrowTable(jastrow.detach().double())
+    dev = onv.device
+    if jastrow_table.sorb != sorb or jastrow_table.device != dev:
+        raise RuntimeError("jrbm_forward_children: the Jastrow table belongs to another sorb or device")
+    n, nw = onv.size(0), walkers.size(0)
+    nbytes = N.lib().pynqs_jastrow_children_table_bytes(nw, sorb)
+    if nbytes < 0:
+        raise RuntimeError(f"bad sizes: {nw} walkers, sorb = {sorb}")
+    table = torch.empty(max(nbytes // 8, 1), dtype=torch.float64, device=dev)
+    st = _stream(dev)
+    wk = walkers.contiguous()
+    N.check(N.lib().pynqs_jastrow_children_prepare(wk.data_ptr(), nw, sorb, jastrow_table.data_ptr(), table.data_ptr(), st),
+            "pynqs_jastrow_children_prepare")
+    N.check(N.lib().pynqs_jastrow_children_apply(onv.contiguous().data_ptr(), n, count.data_ptr() if count is not None else None, parent.data_ptr(),
+                                                 wk.data_ptr(), nw, table.data_ptr(), jastrow_table.data_ptr(), sorb, psi.data_ptr(), st),
+            "pynqs_jastrow_children_apply")
     return psi
 
 

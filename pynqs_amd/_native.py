@@ -153,6 +153,9 @@ SIGNATURES.update({
     "pynqs_mcmc_jrbm_form": (_int, [_int, _int]),
     "pynqs_mcmc_jrbm": (_int, [_vp, _i64, _int, _int, _int, _vp, _vp, _int, C.c_uint64, C.c_uint64, C.c_uint64, _int, _int, _vp, _vp, _vp, _vp]),
     "pynqs_jastrow_grad": (_int, [_vp, _i64, _int, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp]),
+    "pynqs_jastrow_children_table_bytes": (_i64, [_i64, _int]),
+    "pynqs_jastrow_children_prepare": (_int, [_vp, _i64, _int, _vp, _vp, _vp]),
+    "pynqs_jastrow_children_apply": (_int, [_vp, _i64, _vp, _vp, _vp, _i64, _vp, _vp, _int, _vp, _vp]),
 })
 
 _lib = None

@@ -19,7 +19,8 @@ What differs is where the work happens (all on the MI355X, through pynqs_amd.C_e
     Jastrow-RBM, as two passes of the same kernels and a combine kernel (pynqs_eloc_rbm_flip, pynqs_eloc_jrbm_flip);
   * REDUCE compacts the kept columns on chip (pynqs_reduce_count / _emit, and pynqs_reduce_sample for eps_sample > 0) instead of
     writing the whole (batch, ncomb) comb / Hmat and filtering afterwards; the projected / multi-psi / <S-S+> factors are evaluated on
-    the kept records.
+    the kept records.  With an RBM of the reference's family, or a Jastrow-RBM, the amplitudes of the distinct x' come from their parent
+    walkers (pynqs_rbm_forward_children; for the Jastrow-RBM followed by pynqs_jastrow_children_apply), not from the module.
 `FUSED = False` (and FUSED_RBM / FUSED_SAMPLED) force the generic tensor path (used by the tests to cross-check the fast paths).
 
 local_energy is a dispatcher over one function per path, asked in this order (each returns (eloc, sloc, psi, times); None: it declines):
@@ -712,12 +713,35 @@ def reduce_front(x: Tensor, h1e: Tensor, h2e: Tensor, sorb: int, nele: int, noa:
 def _rbm_forward_params(ansatz, dtype):
     """(weights, hidden bias, visible bias, kind) if the forward kernels (pynqs_rbm_forward[_children]) give this ansatz' amplitudes in
     `dtype`: a real RBM whose flavour matches dtype (pRBM is complex-valued, the others real), else an RBM with complex parameters -- not
-    "cos" -- with a complex dtype; else None.  THE place that decides it: once per local_energy call / per look-ahead of total_energy."""
+    "cos" -- with a complex dtype, else a Jastrow-RBM with a real dtype: kind "jastrow" and two more entries, M and its JastrowTable
+    (pynqs_jrbm_forward, pynqs_rbm_forward_children + pynqs_jastrow_children_apply); else None.  THE place that decides it: once per
+    local_energy call / per look-ahead of total_energy."""
     rp = _real_rbm_params(ansatz)
     if rp is not None and dtype.is_complex == (rp[3] == "pRBM"):
         return rp
     cp = _complex_rbm_params(ansatz) if rp is None and dtype.is_complex else None
-    return None if cp is None or cp[4] else (cp[0], cp[1], cp[2], "complex")
+    if cp is not None:
+        return None if cp[4] else (cp[0], cp[1], cp[2], "complex")
+    jp = _jastrow_rbm_params(ansatz) if rp is None and not dtype.is_complex else None
+    if jp is None or N.lib().pynqs_jastrow_table_bytes(jp[3].size(0)) < 0:
+        return None
+    return jp[0], jp[1], jp[2], "jastrow", jp[3], _jastrow_table_for(getattr(ansatz, "module", ansatz).jastrow, jp[3])
+
+
+_JTABLE = threading.local()  # .value: (total_energy call token, M's storage, M's version, JastrowTable): one table per total_energy call
+
+
+def _jastrow_table_for(param: Tensor, M: Tensor):
+    """The JastrowTable of M (float64, detached; param: the module's own tensor, whose version counter tells an update).  Inside a
+    total_energy call the table of the first chunk serves every chunk and the look-ahead; a direct local_energy call builds its own."""
+    token = _call_token()
+    key = (token, param.data_ptr(), CX._ver(param), str(param.device))
+    hit = getattr(_JTABLE, "value", None)
+    if token is not None and key[2] >= 0 and hit is not None and hit[0] == key:
+        return hit[1]
+    table = CX.JastrowTable(M)
+    _JTABLE.value = (key, table) if token is not None else None
+    return table
 
 
 def _reduce_front_options(ansatz, WF_LUT, dtype, use_multi_psi, use_spin_flip):
@@ -738,12 +762,17 @@ def _rbm_ahead(ticket, x, rbm, lut, dtype, sorb, other_stream: bool):
     contraction enqueued behind the front end of `ticket` without waiting for its counters; None when the sizes do not allow it.
     rbm: _rbm_forward_params of the ansatz."""
     fe = ticket.fe
-    W, hb, vb, kind = rbm
-    if not (RBM_FROM_PARENTS and CX.rbm_forward_children_supported(sorb, W.size(0), kind)):
+    W, hb, vb, kind = rbm[:4]
+    jastrow = kind == "jastrow"
+    if not (RBM_FROM_PARENTS and (CX.jrbm_forward_children_supported(sorb, W.size(0)) if jastrow
+                                  else CX.rbm_forward_children_supported(sorb, W.size(0), kind))):
         return None
     if other_stream:   # (total_energy's look-ahead enqueued the front end on its second stream)
         torch.cuda.current_stream(x.device).wait_event(ticket.ev)
-    psi_u = CX.rbm_forward_children(fe.uniq_onv, fe.uniq_parent, x, W, hb, vb, sorb, kind, count=fe.counters).to(dtype)
+    if jastrow:
+        psi_u = CX.jrbm_forward_children(fe.uniq_onv, fe.uniq_parent, x, W, hb, vb, rbm[4], sorb, count=fe.counters, jastrow_table=rbm[5]).to(dtype)
+    else:
+        psi_u = CX.rbm_forward_children(fe.uniq_onv, fe.uniq_parent, x, W, hb, vb, sorb, kind, count=fe.counters).to(dtype)
     eloc, psi_x = fe.contract(psi_u, lut.wf_value if lut is not None else None)
     return fe, eloc, psi_x
 
@@ -886,7 +915,11 @@ def _on_distinct(c, fe, nu, fn, lut) -> Tensor:
 def _rbm_on_distinct(c, fe, nu, rbm) -> Tensor:
     """psi on the distinct x' by one kernel (rbm: _rbm_forward_params).  Every distinct x' is its parent walker with <= 4 orbitals flipped
     (the front end notes the parent): theta(x') from theta(x) by 4 updates per hidden unit when the parameters fit the LDS, else from scratch"""
-    W, hb, vb, kind = rbm
+    W, hb, vb, kind = rbm[:4]
+    if kind == "jastrow":  # the RBM's children kernel, then the Jastrow factor from the parents; else both from scratch in one kernel
+        if RBM_FROM_PARENTS and CX.jrbm_forward_children_supported(c.sorb, W.size(0)):
+            return CX.jrbm_forward_children(fe.uniq_onv[:nu], fe.uniq_parent, c.x, W, hb, vb, rbm[4], c.sorb, jastrow_table=rbm[5]).to(c.dtype)
+        return CX.jrbm_forward(fe.uniq_onv[:nu], W, hb, vb, rbm[4], c.sorb).to(c.dtype)
     if RBM_FROM_PARENTS and CX.rbm_forward_children_supported(c.sorb, W.size(0), kind):
         return CX.rbm_forward_children(fe.uniq_onv[:nu], fe.uniq_parent, c.x, W, hb, vb, c.sorb, kind).to(c.dtype)
     return CX.rbm_forward(fe.uniq_onv[:nu], W, hb, vb, c.sorb, kind).to(c.dtype)

@@ -96,16 +96,18 @@ class ReduceFrontEnd:
         self.stride = self.fixed + self.cap_doubles
         dev, L = self.device, self.L
         slots = max(self.nseg * self.stride, 1)
-        self.rec_col = torch.empty(slots, dtype=torch.int32, device=dev)
+        # (columns and links start at -1, "no record": a launch whose kept list overflowed leaves slots unwritten, and the contraction that
+        # energy._rbm_ahead enqueues behind it before the counters are read would follow whatever link the allocator left there)
+        self.rec_col = torch.full((slots,), -1, dtype=torch.int32, device=dev)
         self.rec_w = torch.zeros(slots, dtype=h_dtype, device=dev)
         self.rec_onv = torch.zeros((slots, 8 * L), dtype=torch.uint8, device=dev) if keep_onv else None
-        self.rec_link = torch.empty(slots, dtype=torch.int32, device=dev)
+        self.rec_link = torch.full((slots,), -1, dtype=torch.int32, device=dev)
         self.seg_count = torch.zeros(max(self.nseg, 1), dtype=torch.int32, device=dev)
         ns = max(self.n * self.eps_sample, 1)
-        self.srec_col = torch.empty(ns, dtype=torch.int32, device=dev)
+        self.srec_col = torch.full((ns,), -1, dtype=torch.int32, device=dev)
         self.srec_w = torch.zeros(ns, dtype=h_dtype, device=dev)
         self.srec_onv = torch.zeros((ns, 8 * L), dtype=torch.uint8, device=dev) if keep_onv else None
-        self.srec_link = torch.empty(ns, dtype=torch.int32, device=dev)
+        self.srec_link = torch.full((ns,), -1, dtype=torch.int32, device=dev)
         self.row_sum = torch.zeros(max(self.n, 1), dtype=torch.float64, device=dev)
         # dedup = False: no de-duplication table -- every record gets its own row of the distinct list (uniq_onv then holds duplicates and
         # `counters[0]` counts records); for systems whose x' are nearly all distinct, where the table would be gigabytes of random probes
