@@ -577,11 +577,20 @@ int pynqs_reduce_onepass(const uint64_t *bra, int64_t nbatch, int sorb, int nele
 int pynqs_reduce_contract(int64_t nbatch, int sorb, int nele, int noA, int noB, int dtype, int eps_sample,
                           const pynqs_reduce_io *io, const double *psi_unique, const double *psi_table, int psi_is_complex,
                           int divide, double *eloc, double *psi_x, void *stream);
-/* the same with the kernel chosen per call (pynqs_reduce_contract takes PYNQS_CONTRACT_BATCHED): PYNQS_CONTRACT_BATCHED reads a slot's
+/* the same with the kernel chosen per call: PYNQS_CONTRACT_BATCHED reads a slot's
  * column first, loads weight and link of live slots only and keeps the loads of several slots per lane in flight; PYNQS_CONTRACT_SERIAL
  * visits a lane's slots one at a time.  Same additions in the same order: eloc and psi_x are the same bit for bit. */
 #define PYNQS_CONTRACT_BATCHED 0
 #define PYNQS_CONTRACT_SERIAL 1
+/* A flag beside the form, for either (form | PYNQS_CONTRACT_BY_XCD): which walkers a workgroup serves.  Without it workgroup b
+ * of B serves walker group b (a group: the walkers of one workgroup, consecutive).  With it, it serves group
+ * pynqs_reduce_contract_group(b, B): the workgroups b = j (mod 8) -- which the hardware has been seen to deal to one XCD, and with it one
+ * L2 -- share a contiguous range of groups, whose rows of psi_unique are neighbours.  Only speed may depend on that dealing: the map is a
+ * permutation of 0 .. B-1 for every B, and eloc and psi_x do not change by a bit. */
+#define PYNQS_CONTRACT_BY_XCD 0x100
+/* (pynqs_reduce_contract takes PYNQS_CONTRACT_BATCHED | PYNQS_CONTRACT_BY_XCD: profiles/contract_stream_ab.txt) */
+/* g = j (B >> 3) + min(j, B & 7) + (b >> 3) with j = b & 7, for 0 <= b < B (-1 outside); host code, no device needed */
+int64_t pynqs_reduce_contract_group(int64_t b, int64_t B);
 int pynqs_reduce_contract_form(int64_t nbatch, int sorb, int nele, int noA, int noB, int dtype, int eps_sample,
                                const pynqs_reduce_io *io, const double *psi_unique, const double *psi_table, int psi_is_complex,
                                int divide, double *eloc, double *psi_x, int form, void *stream);

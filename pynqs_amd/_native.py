@@ -16,6 +16,7 @@ LIB_PATH = os.environ.get("PYNQS_AMD_LIB") or os.path.join(_HERE, "csrc", "libpy
 PYNQS_F32, PYNQS_F64 = 0, 1
 RBM_REAL, RBM_TANH, RBM_PHASE, RBM_COMPLEX = 0, 1, 2, 4
 CHILDREN_CHUNKED, CHILDREN_PER_UNIT = 0, 1  # pynqs_rbm_forward_children_form's schedules
+CONTRACT_BATCHED, CONTRACT_SERIAL, CONTRACT_BY_XCD = 0, 1, 0x100  # pynqs_reduce_contract_form's forms and its placement flag
 OK, EINVAL, ELAUNCH, ELENGTH, EOVERFLOW = 0, -1, -2, -3, -4
 
 _i64, _int, _vp, _dbl = C.c_int64, C.c_int, C.c_void_p, C.c_double
@@ -120,6 +121,7 @@ SIGNATURES.update({
     "pynqs_rbm_grad_loss_form": (_int, [_vp, _i64, _int, _vp, _vp, _vp, _int, _int, _vp, _vp, _int, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _int, _int, _vp]),
     "pynqs_reduce_contract": (_int, [_i64, _int, _int, _int, _int, _int, _int, C.POINTER(ReduceIO), _vp, _vp, _int, _int, _vp, _vp, _vp]),
     "pynqs_reduce_contract_form": (_int, [_i64, _int, _int, _int, _int, _int, _int, C.POINTER(ReduceIO), _vp, _vp, _int, _int, _vp, _vp, _int, _vp]),
+    "pynqs_reduce_contract_group": (_i64, [_i64, _i64]),
     "pynqs_mcmc_rbm_supported": (_int, [_int, _int, _int]),
     "pynqs_mcmc_rbm": (_int, [_vp, _i64, _int, _int, _int, _vp, _int, _int, C.c_uint64, C.c_uint64, C.c_uint64, _int, _int, _vp, _vp, _vp, _vp]),
     "pynqs_rbm_sr_workspace": (_i64, [_i64, _int, _int, _int]),

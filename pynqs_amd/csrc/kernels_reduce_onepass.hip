@@ -517,6 +517,16 @@ __global__ __launch_bounds__(kBlock) void reduce_onepass_list_redraw_kernel(cons
 }
 
 // ---- contraction: E_loc(x) = sum_records w psi(x') / psi(x) ------------------------------------------------------------
+
+// Which walkers a workgroup of the contraction serves (by_xcd, PYNQS_CONTRACT_BY_XCD): not group b of kBlock / 64 consecutive walkers but
+// group contract_group(b, B) -- the workgroups b = j (mod 8), which share an XCD's L2 as far as the hardware has been seen to deal them,
+// take a contiguous range of groups, whose rows of psi_u are neighbours (a walker's rows are contiguous, eight to a line).  A permutation
+// of 0 .. B-1 for every B (the first B & 7 classes have one group more): only the speed depends on the dealing.
+__host__ __device__ __forceinline__ uint32_t contract_group(uint32_t b, uint32_t B) {
+  const uint32_t j = b & 7u, r = B & 7u;
+  return j * (B >> 3) + (j < r ? j : r) + (b >> 3);
+}
+
 // One wave per walker.  Slots are visited in their fixed order (fixed slots, compacted doubles, drawn records; chunk by chunk),
 // lane l takes slots l, l + 64, ...; the 64 partial sums meet in a butterfly: the result does not depend on anything but the
 // records' positions.  psi(x) is the amplitude of the record of column 0 (kept slot 0, else among the drawn ones; 0 if it is
@@ -529,9 +539,9 @@ __global__ __launch_bounds__(kBlock) void reduce_contract_kernel(int64_t nbatch,
                                                                  const T *__restrict__ srec_w, const int32_t *__restrict__ srec_link,
                                                                  const int32_t *__restrict__ dedup_i32, int slot_i32, int row_off, uint32_t ucap,
                                                                  const double *__restrict__ psi_u, const double *__restrict__ psi_t, int divide,
-                                                                 double *__restrict__ eloc, double *__restrict__ psi_x) {
+                                                                 double *__restrict__ eloc, double *__restrict__ psi_x, int by_xcd) {
   const int lane = threadIdx.x & 63;
-  const int64_t walker = (int64_t)blockIdx.x * (kBlock / 64) + (threadIdx.x >> 6);
+  const int64_t walker = (int64_t)(by_xcd ? contract_group(blockIdx.x, gridDim.x) : blockIdx.x) * (kBlock / 64) + (threadIdx.x >> 6);
   if (walker >= nbatch) return;
   double ar = 0.0, ai = 0.0, xr = 0.0, xi = 0.0;
   bool bad = false;
@@ -607,6 +617,13 @@ __device__ __forceinline__ void contract_add(double &ar, double &ai, double w, d
   ai = fma(w, im, ai);
 }
 
+// A record is read once, by one lane; an amplitude is read by every record that links to its row (6.4 M records on 1.5 M rows on the
+// flagship).  The records are loaded non-temporally, so that they pass through the L2 without taking the place of psi_u's lines.
+template <typename X>
+__device__ __forceinline__ X record_load(const X *p) {
+  return __builtin_nontemporal_load(p);
+}
+
 template <typename T, bool CPLX, int U>
 __global__ __launch_bounds__(kBlock) void reduce_contract_batched_kernel(int64_t nbatch, uint32_t nchunks, uint32_t fixed, uint32_t cap_d,
                                                                          uint32_t nsample, const int32_t *__restrict__ rec_col,
@@ -615,9 +632,9 @@ __global__ __launch_bounds__(kBlock) void reduce_contract_batched_kernel(int64_t
                                                                          const T *__restrict__ srec_w, const int32_t *__restrict__ srec_link,
                                                                          const int32_t *__restrict__ dedup_i32, int slot_i32, int row_off, uint32_t ucap,
                                                                          const double *__restrict__ psi_u, const double *__restrict__ psi_t, int divide,
-                                                                         double *__restrict__ eloc, double *__restrict__ psi_x) {
+                                                                         double *__restrict__ eloc, double *__restrict__ psi_x, int by_xcd) {
   const uint32_t lane = threadIdx.x & 63;
-  const int64_t walker = (int64_t)blockIdx.x * (kBlock / 64) + (threadIdx.x >> 6);
+  const int64_t walker = (int64_t)(by_xcd ? contract_group(blockIdx.x, gridDim.x) : blockIdx.x) * (kBlock / 64) + (threadIdx.x >> 6);
   if (walker >= nbatch) return;
   double ar = 0.0, ai = 0.0, xr = 0.0, xi = 0.0;
   bool bad = false;
@@ -627,7 +644,7 @@ __global__ __launch_bounds__(kBlock) void reduce_contract_batched_kernel(int64_t
 #pragma unroll
     for (int u = 0; u < U; ++u) {
       const uint32_t i = lane + 64u * u;
-      coln[u] = i < count ? colp[i] : -1;
+      coln[u] = i < count ? record_load(colp + i) : -1;
     }
     for (uint32_t i0 = lane; i0 < count; i0 += 64u * U) {
       int32_t col[U], link[U];
@@ -636,13 +653,13 @@ __global__ __launch_bounds__(kBlock) void reduce_contract_batched_kernel(int64_t
       for (int u = 0; u < U; ++u) {
         col[u] = coln[u];
         const uint32_t i = i0 + 64u * u;  // (col >= 0: i < count)
-        w[u] = col[u] >= 0 ? wp[i] : T(0);
-        link[u] = col[u] >= 0 ? lp[i] : -1;
+        w[u] = col[u] >= 0 ? record_load(wp + i) : T(0);
+        link[u] = col[u] >= 0 ? record_load(lp + i) : -1;
       }
 #pragma unroll
       for (int u = 0; u < U; ++u) {  // the next batch's columns
         const uint32_t i = i0 + 64u * (U + u);
-        coln[u] = i < count ? colp[i] : -1;
+        coln[u] = i < count ? record_load(colp + i) : -1;
       }
       // where the amplitude is: row of psi_u (>= 0), entry of psi_t (tab), or nowhere (at < 0 or at >= ucap: bad)
       int64_t at[U];
@@ -1000,6 +1017,8 @@ extern "C" int pynqs_reduce_contract_form(int64_t nbatch, int sorb, int nele, in
   if (!make_sd_params(sorb, nele, noA, noB, &p)) return set_error(PYNQS_EINVAL, "bad sorb/noA/noB");
   if (nbatch < 0 || nbatch > 0x7fffffffll || (dtype != PYNQS_F32 && dtype != PYNQS_F64) || eps_sample < 0 || eps_sample > 65535)
     return set_error(PYNQS_EINVAL, "bad nbatch/dtype/eps_sample");
+  const int by_xcd = (form & PYNQS_CONTRACT_BY_XCD) != 0;
+  form &= ~PYNQS_CONTRACT_BY_XCD;
   if (form != PYNQS_CONTRACT_BATCHED && form != PYNQS_CONTRACT_SERIAL) return set_error(PYNQS_EINVAL, "bad form");
   if (nbatch == 0) return PYNQS_OK;
   if (!io || !io->rec_col || !io->rec_w || !io->rec_link || !io->seg_count || !psi_unique || !eloc || !psi_x ||
@@ -1014,7 +1033,7 @@ extern "C" int pynqs_reduce_contract_form(int64_t nbatch, int sorb, int nele, in
   dim3(grid), dim3(kBlock), 0, st, nbatch, nchunks, fixed, (uint32_t)io->cap_doubles, (uint32_t)eps_sample, io->rec_col,            \
       (const TT *)io->rec_w, io->rec_link, io->seg_count, io->srec_col, (const TT *)io->srec_w, io->srec_link,                      \
       (const int32_t *)io->dedup_table, dedup_slot_words(len) * 2, dedup_row_offset(len), (uint32_t)io->cap_unique, psi_unique,     \
-      psi_table, divide, eloc, psi_x
+      psi_table, divide, eloc, psi_x, by_xcd
 #define PYNQS_CT_LAUNCH(TT, CX)                                                                             \
   do {                                                                                                      \
     if (form == PYNQS_CONTRACT_SERIAL) hipLaunchKernelGGL((reduce_contract_kernel<TT, CX>), PYNQS_CT_ARGS(TT)); \
@@ -1027,11 +1046,16 @@ extern "C" int pynqs_reduce_contract_form(int64_t nbatch, int sorb, int nele, in
   return check_launch("reduce_contract");
 }
 
+extern "C" int64_t pynqs_reduce_contract_group(int64_t b, int64_t B) {
+  if (b < 0 || b >= B || B > 0xffffffffll) return -1;
+  return (int64_t)pynqs::contract_group((uint32_t)b, (uint32_t)B);
+}
+
 extern "C" int pynqs_reduce_contract(int64_t nbatch, int sorb, int nele, int noA, int noB, int dtype, int eps_sample,
                                      const pynqs_reduce_io *io, const double *psi_unique, const double *psi_table, int psi_is_complex,
                                      int divide, double *eloc, double *psi_x, void *stream) {
   return pynqs_reduce_contract_form(nbatch, sorb, nele, noA, noB, dtype, eps_sample, io, psi_unique, psi_table, psi_is_complex, divide, eloc,
-                                    psi_x, PYNQS_CONTRACT_BATCHED, stream);
+                                    psi_x, PYNQS_CONTRACT_BATCHED | PYNQS_CONTRACT_BY_XCD, stream);
 }
 
 #ifdef PYNQS_OP_STAMPS

@@ -27,6 +27,9 @@ ROW_CACHE = True                  # semi-stochastic kernel: cache the row in glo
 ROW_CACHE_MAX_BYTES = 8 << 30
 ROW_F32 = os.environ.get("PYNQS_ROW_F32", "1") != "0"  # semi-stochastic calls on short rows: the two-kernel form (see ReduceFrontEnd)
 ROW_F32_MAX_BYTES = int(os.environ.get("PYNQS_ROW_F32_MAX_BYTES", str(16 << 30)))  # long rows: the float32 copy is 4 bytes per column and walker
+# the contraction kernel ReduceFrontEnd.contract takes when its caller names none: pynqs_reduce_contract_form's form, with or without
+# its placement flag (include/pynqs_amd.h; what each was worth on the flagship: profiles/contract_stream_ab.txt)
+CONTRACT_FORM = int(os.environ.get("PYNQS_CONTRACT_FORM", str(N.CONTRACT_BATCHED | N.CONTRACT_BY_XCD)), 0)
 TILE_SCRATCH_MIN_ROW = int(os.environ.get("PYNQS_TILE_SCRATCH_MIN_ROW", "65536"))  # columns per row from which the tile sums leave the LDS
 
 
@@ -198,10 +201,13 @@ class ReduceFrontEnd:
                 "pynqs_reduce_onepass")
 
     def contract(self, values_unique: Tensor, values_table: Optional[Tensor] = None, divide: bool = True,
-                 rec_w: Optional[Tensor] = None, srec_w: Optional[Tensor] = None, form: int = 0) -> Tuple[Tensor, Tensor]:
+                 rec_w: Optional[Tensor] = None, srec_w: Optional[Tensor] = None, form: Optional[int] = None) -> Tuple[Tensor, Tensor]:
         """(sum_records w A(x') [/ A(x)], A(x)) per walker; A = `values_unique` on the distinct rows, `values_table` on the
         wave-function table's positions.  rec_w / srec_w replace the records' weights (same slot layout).  form: the kernel,
-        pynqs_reduce_contract_form's (0: batched loads, 1: a slot at a time; the same bits)."""
+        pynqs_reduce_contract_form's (0: batched loads, 1: a slot at a time; | 0x100: the workgroups of an XCD on neighbouring walkers;
+        the same bits; None: CONTRACT_FORM)."""
+        if form is None:
+            form = CONTRACT_FORM
         cplx = values_unique.is_complex()
         vt = torch.complex128 if cplx else torch.float64
         vu = values_unique.to(vt).contiguous()
