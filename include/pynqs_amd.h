@@ -574,6 +574,20 @@ int pynqs_reduce_onepass_wants_row_f32(int64_t nbatch, int sorb, int nele, int n
 int64_t pynqs_reduce_onepass_row_f32_elements(int64_t nbatch, int sorb, int nele, int noA, int noB);
 int pynqs_reduce_onepass(const uint64_t *bra, int64_t nbatch, int sorb, int nele, int noA, int noB, const void *plan,
                          int dtype, double eps, int eps_sample, uint64_t seed, const pynqs_reduce_io *io, void *stream);
+/* the same with the tile loop of the short-row semi-stochastic kernel (the form that ..._wants_row_f32 answers 1 for) chosen per call; the
+ * other forms of the front end have one tile loop and ignore the choice.  PYNQS_ROWOUT_TILEWISE (what pynqs_reduce_onepass takes): the tile
+ * sums by cross-lane moves of a fixed pattern and formed behind the next tile's gathers, the kept columns of a full tile of doubles handed
+ * to the list together (one LDS atomic per tile).  PYNQS_ROWOUT_PER_COLUMN: __shfl_xor butterflies in front of the next tile, one hand-off
+ * per kept column.  Same additions in the same order, records
+ * placed by bitmap rank: every output is the same bit for bit (the distinct list's order follows the launch's timing under either). */
+#define PYNQS_ROWOUT_TILEWISE 0
+#define PYNQS_ROWOUT_PER_COLUMN 1
+int pynqs_reduce_onepass_form(const uint64_t *bra, int64_t nbatch, int sorb, int nele, int noA, int noB, const void *plan,
+                              int dtype, double eps, int eps_sample, uint64_t seed, const pynqs_reduce_io *io, int form, void *stream);
+/* the wave sums and scans of the front end on caller-supplied data, one wave per 64 values, every lane's result (for tests):
+ * what = 0: float64, the fixed-pattern butterfly; 1: float64, the __shfl_xor butterfly; 2 / 3: the same for uint32; 4: uint32 inclusive
+ * scan by fixed-pattern moves.  in / out: device pointers to nwaves * 64 values of 8 (what 0, 1) or 4 bytes. */
+int pynqs_debug_wave_sum(const void *in, void *out, int64_t nwaves, int what, void *stream);
 int pynqs_reduce_contract(int64_t nbatch, int sorb, int nele, int noA, int noB, int dtype, int eps_sample,
                           const pynqs_reduce_io *io, const double *psi_unique, const double *psi_table, int psi_is_complex,
                           int divide, double *eloc, double *psi_x, void *stream);

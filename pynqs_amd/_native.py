@@ -17,6 +17,7 @@ PYNQS_F32, PYNQS_F64 = 0, 1
 RBM_REAL, RBM_TANH, RBM_PHASE, RBM_COMPLEX = 0, 1, 2, 4
 CHILDREN_CHUNKED, CHILDREN_PER_UNIT = 0, 1  # pynqs_rbm_forward_children_form's schedules
 CONTRACT_BATCHED, CONTRACT_SERIAL, CONTRACT_BY_XCD = 0, 1, 0x100  # pynqs_reduce_contract_form's forms and its placement flag
+ROWOUT_TILEWISE, ROWOUT_PER_COLUMN = 0, 1  # pynqs_reduce_onepass_form's tile loops of the short-row semi-stochastic kernel
 OK, EINVAL, ELAUNCH, ELENGTH, EOVERFLOW = 0, -1, -2, -3, -4
 
 _i64, _int, _vp, _dbl = C.c_int64, C.c_int, C.c_void_p, C.c_double
@@ -105,6 +106,8 @@ SIGNATURES.update({
     "pynqs_reduce_onepass_wants_row_f32": (_int, [_i64, _int, _int, _int, _int, _int, _int, _i64, _int, _int]),
     "pynqs_reduce_onepass_row_f32_elements": (_i64, [_i64, _int, _int, _int, _int]),
     "pynqs_reduce_onepass": (_int, [_vp, _i64, _int, _int, _int, _int, _vp, _int, _dbl, _int, C.c_uint64, C.POINTER(ReduceIO), _vp]),
+    "pynqs_reduce_onepass_form": (_int, [_vp, _i64, _int, _int, _int, _int, _vp, _int, _dbl, _int, C.c_uint64, C.POINTER(ReduceIO), _int, _vp]),
+    "pynqs_debug_wave_sum": (_int, [_vp, _vp, _i64, _int, _vp]),
     "pynqs_rbm_forward": (_int, [_vp, _i64, _int, _vp, _vp, _vp, _int, _int, _vp, _vp]),
     "pynqs_rbm_children_table_bytes": (_i64, [_i64, _int, _int, _int]),
     "pynqs_rbm_children_prepare": (_int, [_vp, _i64, _int, _vp, _vp, _vp, _int, _int, _vp, _vp]),

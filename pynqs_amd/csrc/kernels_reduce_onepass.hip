@@ -149,7 +149,7 @@ struct KeepSink {
         __builtin_amdgcn_s_sleep(1);
         continue;
       }
-      excl += op_wave_sum(lane <= fp ? (s & kStatMask) : 0u);
+      excl += op_wave_sum_shfl(lane <= fp ? (s & kStatMask) : 0u);
       if (fp < 64) break;
       top -= 64;
     }
@@ -161,7 +161,7 @@ struct KeepSink {
     if (tile == 0xffffffffu) return;
     const int lane = threadIdx.x & 63;
     if constexpr (SAMPLED) {
-      const double s = op_wave_sum(sub);
+      const double s = op_wave_sum_shfl(sub);
       if (lane == 0) tsum[tile] = s;
     }
     wave_sync();
@@ -930,7 +930,13 @@ extern "C" int64_t pynqs_reduce_onepass_row_f32_elements(int64_t nbatch, int sor
 
 extern "C" int pynqs_reduce_onepass(const uint64_t *bra, int64_t nbatch, int sorb, int nele, int noA, int noB, const void *plan, int dtype,
                                     double eps, int eps_sample, uint64_t seed, const pynqs_reduce_io *io, void *stream) {
+  return pynqs_reduce_onepass_form(bra, nbatch, sorb, nele, noA, noB, plan, dtype, eps, eps_sample, seed, io, PYNQS_ROWOUT_TILEWISE, stream);
+}
+
+extern "C" int pynqs_reduce_onepass_form(const uint64_t *bra, int64_t nbatch, int sorb, int nele, int noA, int noB, const void *plan, int dtype,
+                                         double eps, int eps_sample, uint64_t seed, const pynqs_reduce_io *io, int rowout_form, void *stream) {
   pynqs::DeviceScope device_scope_(bra);
+  if (rowout_form != PYNQS_ROWOUT_TILEWISE && rowout_form != PYNQS_ROWOUT_PER_COLUMN) return set_error(PYNQS_EINVAL, "bad form");
   SDParams p;
   PlanLayout pl;
   if (!make_sd_params(sorb, nele, noA, noB, &p) || !make_plan_layout(sorb, &pl)) return set_error(PYNQS_EINVAL, "bad sorb/noA/noB (even sorb in [2, 192])");
@@ -986,7 +992,7 @@ extern "C" int pynqs_reduce_onepass(const uint64_t *bra, int64_t nbatch, int sor
             use_split ? "LIST + float32 row copy + sorted draws" : use_row32 ? (use_gtile ? "flushing LIST + float32 row copy (tile sums in global memory)" : "flushing LIST + float32 row copy") : use_flush ? "flushing LIST" : use_list ? (use_gtile ? "LIST (tile sums in global memory)" : "LIST") : "look-back", use_cache ? " with row cache" : "", lds, (size_t)lds_fixed_bytes(p), max_tiles, P, nchunks);
   // eloc.py:257-264: with draws and eps <= 0 nothing is kept (every column can be drawn); without draws |H| >= eps as it stands
   const double eps_eff = (sampled && !(eps > 0.0)) ? __builtin_inf() : eps;
-  if (use_split) return launch_reduce_rowout(bra, nbatch, p, pl, chunk_len, max_tiles, plan, dtype, eps_eff, eps_sample, seed, P, lds, io, fixed, st);
+  if (use_split) return launch_reduce_rowout(bra, nbatch, p, pl, chunk_len, max_tiles, plan, dtype, eps_eff, eps_sample, seed, P, lds, io, fixed, rowout_form, st);
   if (use_row32) return launch_reduce_flush_row32(bra, nbatch, p, pl, chunk_len, max_tiles, plan, dtype, eps_eff, eps_sample, seed, P, lds, io, fixed, use_gtile, st);
 #define PYNQS_OP_LAUNCH(TT, SM)                                                                                                      \
   do {                                                                                                                               \

@@ -117,6 +117,22 @@ struct sink_can_remap : std::false_type {};
 template <typename S>
 struct sink_can_remap<S, std::void_t<decltype(std::declval<S &>().remap(0u))>> : std::true_type {};
 
+// optional member of a sink: void full_tile(uint32_t col, const T (&h)[UU][2]) -- a FULL tile of paired doubles hands the lane's 2 UU values
+// over together instead of by UU calls of pair(): h[u][0], h[u][1] belong to columns col + 128 u and col + 128 u + 1 (the kets are not
+// formed).  For a sink that pays per call, not per column (the ROWOUT list of the REDUCE front end: one hand-off of the kept columns per tile).
+template <typename S, typename T, int UU, typename = void>
+struct sink_takes_full_tile : std::false_type {};
+template <typename S, typename T, int UU>
+struct sink_takes_full_tile<S, T, UU, std::void_t<decltype(std::declval<S &>().full_tile(0u, std::declval<const T (&)[UU][2]>()))>> : std::true_type {};
+
+// optional member of a sink: void settle() (wave-uniform) -- a sink that forms a tile's result in tile_begin of the NEXT tile may leave it
+// pending there; visit_tiles then calls settle() once the new tile's gathers have gone out (full tiles of paired doubles), or at once (every
+// other tile): the cross-lane work of the finished tile runs behind the gather latency of the new one.
+template <typename S, typename = void>
+struct sink_defers_tile_sum : std::false_type {};
+template <typename S>
+struct sink_defers_tile_sum<S, std::void_t<decltype(std::declval<S &>().settle())>> : std::true_type {};
+
 // UU: pair slots per lane and tile.  Everything that sizes buffers by the tile (the semi-stochastic forms' draw areas, the look-back buffers,
 // max_tiles_per_chunk) assumes PYNQS_U; a sink that keeps nothing per tile may ask for deeper tiles = more gathers in flight per lane.
 // The tiles of one workgroup (one chunk of a walker's row), as visit_tiles numbers them: tile 0 (column 0 and the unpaired doubles), tS tiles
@@ -219,6 +235,7 @@ __device__ __forceinline__ bool visit_tiles(const SDParams &p, const PlanLayout 
       if (sink.skip_tile(tile)) continue;
     }
     if (tile == 0) {
+      if constexpr (sink_defers_tile_sum<Sink>::value) sink.settle();
       // unpaired columns of the three classes: lanes 0..5
       if (kPaired && lane < 6) {
         const int k = lane >> 1;
@@ -255,6 +272,7 @@ __device__ __forceinline__ bool visit_tiles(const SDParams &p, const PlanLayout 
       continue;
     }
     if (tile <= tS) {
+      if constexpr (sink_defers_tile_sum<Sink>::value) sink.settle();
       const uint32_t r0 = (chunk + (tile - 1) * nchunks) * kSPT;
       if constexpr (EXACT) {
         singles_tile<T, QUARTER>(r0, min(r0 + kSPT, p.d1), p, pl, L, nocc, plan, [&](uint32_t r, T v, uint32_t e) {
@@ -288,6 +306,7 @@ __device__ __forceinline__ bool visit_tiles(const SDParams &p, const PlanLayout 
     const DoubleClass c = k == 2 ? make_opp_spin(p, pl) : make_same_spin(p, pl, k);
     const T *__restrict__ V = k == 2 ? Vab : Vss + (size_t)k * pl.NP * pl.NP;
     if constexpr (!kPaired) {
+      if constexpr (sink_defers_tile_sum<Sink>::value) sink.settle();
       // ranks first + (2u + v) * 64 + lane: every store instruction of the sink covers 64 neighbouring columns
       if (first + kSlots <= g.npairs) {
         PendingDouble<T> d[U][2];
@@ -317,9 +336,22 @@ __device__ __forceinline__ bool visit_tiles(const SDParams &p, const PlanLayout 
       PendingDouble<T> d[U][2];
 #pragma unroll
       for (int u = 0; u < U; ++u) fetch_double2<LEN, T>(g.r_e + 2 * (first + u * 64 + lane), c, L, V, d[u][0], d[u][1]);
+      if constexpr (sink_defers_tile_sum<Sink>::value) sink.settle();
+      if constexpr (sink_takes_full_tile<Sink, T, U>::value) {
+        T h[U][2];
 #pragma unroll
-      for (int u = 0; u < U; ++u) emit_pair(d[u][0], d[u][1], g.r_e + 2 * (first + u * 64 + lane) + 1, c);
+        for (int u = 0; u < U; ++u) {
+          uint64_t k0[LEN], k1[LEN];
+          h[u][0] = finish_double<LEN, T>(d[u][0], c, wk, k0);
+          h[u][1] = finish_double<LEN, T>(d[u][1], c, wk, k1);
+        }
+        sink.full_tile(g.r_e + 2 * (first + lane) + 1, h);
+      } else {
+#pragma unroll
+        for (int u = 0; u < U; ++u) emit_pair(d[u][0], d[u][1], g.r_e + 2 * (first + u * 64 + lane) + 1, c);
+      }
     } else {
+      if constexpr (sink_defers_tile_sum<Sink>::value) sink.settle();
       for (uint32_t m = first + lane; m < g.npairs; m += 64) {
         PendingDouble<T> d0, d1;
         fetch_double2<LEN, T>(g.r_e + 2 * m, c, L, V, d0, d1);

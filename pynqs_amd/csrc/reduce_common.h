@@ -34,15 +34,84 @@ __device__ __forceinline__ double op_scan(double v, int lane) {  // inclusive, l
   return v;
 }
 
-__device__ __forceinline__ uint32_t op_wave_sum(uint32_t v) {
+// What form 0 of the short-row semi-stochastic kernel consists of (reduce_list.h: RFORM), for measuring each part alone
+// (profiles/rowout_tiles_ab.txt): 1 the fixed-pattern wave sums and scans below, 2 one hand-off of the kept columns per tile, 4 the
+// finished tile's sum behind the next tile's gathers.
+#ifndef PYNQS_ROWOUT_LEVERS
+#define PYNQS_ROWOUT_LEVERS 7
+#endif
+
+// The wave's sum by a butterfly: six steps v += v[lane ^ d], d = 32 ... 1; every lane ends with the same bits.  The __shfl_xor form: each
+// step computes its partner's index again (xor, compare, select, shift) in front of one ds_bpermute_b32 per 32 bits: 34 vector
+// instructions and 12 permutes for a double.
+__device__ __forceinline__ uint32_t op_wave_sum_shfl(uint32_t v) {
 #pragma unroll
   for (int d = 32; d > 0; d >>= 1) v += __shfl_xor(v, d);
   return v;
 }
 
-__device__ __forceinline__ double op_wave_sum(double v) {
+__device__ __forceinline__ double op_wave_sum_shfl(double v) {
 #pragma unroll
   for (int d = 32; d > 0; d >>= 1) v += __shfl_xor(v, d);
+  return v;
+}
+
+// The same tree -- the same partner lane ^ d at every step, so the same bits -- with cross-lane moves whose pattern is part of the
+// instruction: no index arithmetic, and only the d = 4 step goes through the LDS crossbar.
+//   d = 32, 16 : v_permlane32_swap / v_permlane16_swap of a register with its own copy: afterwards one result holds the value of the lower
+//                half (of the wave / of each 32 lanes) in both halves, the other the upper half's; their sum is v + v[lane ^ d] in the
+//                lower half and v[lane ^ d] + v in the upper one, and an IEEE addition commutes
+//   d = 8      : DPP row_ror:8 (a rotation by 8 inside a row of 16 lanes is lane ^ 8)
+//   d = 4      : ds_swizzle_b32 in bit-mask mode (and 0x1f, or 0, xor 4)
+//   d = 2, 1   : DPP quad_perm [2,3,0,1] and [1,0,3,2]
+// All 64 lanes must be active.  tests/test_gpu_wave_sum_forms.py holds both forms to the butterfly emulated on the host, lane by lane.
+template <int CTRL>
+__device__ __forceinline__ uint32_t op_dpp_move(uint32_t x) {
+  return (uint32_t)__builtin_amdgcn_update_dpp((int)x, (int)x, CTRL, 0xf, 0xf, false);
+}
+constexpr int kDppXor1 = 0xB1, kDppXor2 = 0x4E, kDppRor8 = 0x128;  // quad_perm [1,0,3,2], quad_perm [2,3,0,1], row_ror:8
+constexpr int kSwizzleXor4 = (4 << 10) | 0x1f;                     // bit-mask mode: xor_mask << 10 | or_mask << 5 | and_mask
+
+__device__ __forceinline__ uint32_t op_wave_sum(uint32_t v) {
+  const auto s32 = __builtin_amdgcn_permlane32_swap(v, v, false, false);
+  v = s32[0] + s32[1];
+  const auto s16 = __builtin_amdgcn_permlane16_swap(v, v, false, false);
+  v = s16[0] + s16[1];
+  v += op_dpp_move<kDppRor8>(v);
+  v += (uint32_t)__builtin_amdgcn_ds_swizzle((int)v, kSwizzleXor4);
+  v += op_dpp_move<kDppXor2>(v);
+  v += op_dpp_move<kDppXor1>(v);
+  return v;
+}
+
+// Inclusive scan of an integer over the wave (exact in any order, so the tree is free): Kogge-Stone inside each row of 16 lanes by DPP
+// row_shr:1/2/4/8 (zeros shifted in), then lane 15 of rows 0 and 2 into rows 1 and 3 (row_bcast:15), then lane 31 into rows 2 and 3
+// (row_bcast:31) -- six moves without an index register, against six ds_bpermute_b32 with a compare and a select each.
+__device__ __forceinline__ uint32_t op_wave_scan(uint32_t v) {
+  v += (uint32_t)__builtin_amdgcn_update_dpp(0, (int)v, 0x111, 0xf, 0xf, true);
+  v += (uint32_t)__builtin_amdgcn_update_dpp(0, (int)v, 0x112, 0xf, 0xf, true);
+  v += (uint32_t)__builtin_amdgcn_update_dpp(0, (int)v, 0x114, 0xf, 0xf, true);
+  v += (uint32_t)__builtin_amdgcn_update_dpp(0, (int)v, 0x118, 0xf, 0xf, true);
+  v += (uint32_t)__builtin_amdgcn_update_dpp(0, (int)v, 0x142, 0xa, 0xf, false);
+  v += (uint32_t)__builtin_amdgcn_update_dpp(0, (int)v, 0x143, 0xc, 0xf, false);
+  return v;
+}
+
+__device__ __forceinline__ double op_wave_sum(double v) {
+  uint32_t lo = (uint32_t)__double2loint(v), hi = (uint32_t)__double2hiint(v);
+  const auto l32 = __builtin_amdgcn_permlane32_swap(lo, lo, false, false), h32 = __builtin_amdgcn_permlane32_swap(hi, hi, false, false);
+  v = __hiloint2double((int)h32[0], (int)l32[0]) + __hiloint2double((int)h32[1], (int)l32[1]);
+  lo = (uint32_t)__double2loint(v); hi = (uint32_t)__double2hiint(v);
+  const auto l16 = __builtin_amdgcn_permlane16_swap(lo, lo, false, false), h16 = __builtin_amdgcn_permlane16_swap(hi, hi, false, false);
+  v = __hiloint2double((int)h16[0], (int)l16[0]) + __hiloint2double((int)h16[1], (int)l16[1]);
+  lo = (uint32_t)__double2loint(v); hi = (uint32_t)__double2hiint(v);
+  v += __hiloint2double((int)op_dpp_move<kDppRor8>(hi), (int)op_dpp_move<kDppRor8>(lo));
+  lo = (uint32_t)__double2loint(v); hi = (uint32_t)__double2hiint(v);
+  v += __hiloint2double(__builtin_amdgcn_ds_swizzle((int)hi, kSwizzleXor4), __builtin_amdgcn_ds_swizzle((int)lo, kSwizzleXor4));
+  lo = (uint32_t)__double2loint(v); hi = (uint32_t)__double2hiint(v);
+  v += __hiloint2double((int)op_dpp_move<kDppXor2>(hi), (int)op_dpp_move<kDppXor2>(lo));
+  lo = (uint32_t)__double2loint(v); hi = (uint32_t)__double2hiint(v);
+  v += __hiloint2double((int)op_dpp_move<kDppXor1>(hi), (int)op_dpp_move<kDppXor1>(lo));
   return v;
 }
 
@@ -421,7 +490,7 @@ inline OnepassOut<T> make_out(const pynqs_reduce_io *io, int len, uint32_t fixed
 bool reduce_draw_supported(const SDParams &p, int eps_sample);
 int launch_reduce_rowout(const uint64_t *bra, int64_t nbatch, const SDParams &p, const PlanLayout &pl, uint32_t chunk_len, uint32_t max_tiles,
                          const void *plan, int dtype, double eps_eff, int eps_sample, uint64_t seed, uint32_t P, size_t lds,
-                         const pynqs_reduce_io *io, uint32_t fixed, hipStream_t st);
+                         const pynqs_reduce_io *io, uint32_t fixed, int form, hipStream_t st);
 // the flushing semi-stochastic form with the row's float32 copy (kernels_reduce_rowout.hip): as above, for rows of any length
 int launch_reduce_flush_row32(const uint64_t *bra, int64_t nbatch, const SDParams &p, const PlanLayout &pl, uint32_t chunk_len, uint32_t max_tiles,
                               const void *plan, int dtype, double eps_eff, int eps_sample, uint64_t seed, uint32_t P, size_t lds,

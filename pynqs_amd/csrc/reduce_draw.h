@@ -116,14 +116,20 @@ __device__ __forceinline__ void probe_k_oneword(const OnepassOut<T> &o, const ui
 }
 
 // inclusive block scan over the kBlock threads (fixed order of additions); *total = the sum.  Contains barriers.
-template <typename V>
+// FIXED (integers only: exact in any order): the wave's part by op_wave_scan's fixed-pattern moves instead of __shfl_up.
+template <typename V, bool FIXED = false>
 __device__ __forceinline__ V draw_block_scan(V v, V *s_part, V *total) {
+  static_assert(!FIXED || std::is_same<V, uint32_t>::value, "a float64 scan keeps its order of additions");
   const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
   V incl = v;
+  if constexpr (FIXED) {
+    incl = op_wave_scan(v);
+  } else {
 #pragma unroll
-  for (int d = 1; d < 64; d <<= 1) {
-    const V ov = __shfl_up(incl, d);
-    if (lane >= d) incl += ov;
+    for (int d = 1; d < 64; d <<= 1) {
+      const V ov = __shfl_up(incl, d);
+      if (lane >= d) incl += ov;
+    }
   }
   __syncthreads();  // (s_part free)
   if (lane == 63) s_part[wave] = incl;
@@ -142,7 +148,7 @@ __device__ __forceinline__ V draw_block_scan(V v, V *s_part, V *total) {
 // w: this walker's row of float32 elements, kDrawSeg-aligned and padded with zeros to a multiple of kDrawSeg.
 // rec: [nsample] words of LDS for the drawn records; kcol / nkept / seg_base: the kept records' columns in slot order (0xffffffff: an empty
 // slot), their number and the first slot of the segment -- they are resolved here, together with the drawn ones.
-template <int LEN, typename T>
+template <int LEN, typename T, int RFORM = 1>
 __device__ __forceinline__ void rowout_draws(unsigned char *lds, uint32_t *rec, const uint32_t *kcol, uint32_t nkept, int64_t seg_base, const SDParams &p,
                                              const LdsLayout &L, const Walker<LEN> &wk, const float *__restrict__ w, uint32_t nsample, uint64_t seed,
                                              uint64_t walker, double Srow, const OnepassOut<T> &o, uint32_t *bw_cnt, int32_t *bw_base, uint32_t *s_full,
@@ -241,7 +247,7 @@ __device__ __forceinline__ void rowout_draws(unsigned char *lds, uint32_t *rec, 
     if (k0 + K * NT >= nsample) {
       uint32_t dummy;
       const uint32_t c = tid < (int)nbw ? (uint32_t)__popc(bitmap[tid]) : 0u;
-      const uint32_t inc = draw_block_scan<uint32_t>(c, s_parti, &dummy);
+      const uint32_t inc = draw_block_scan<uint32_t, RFORM == 0 && (PYNQS_ROWOUT_LEVERS & 1)>(c, s_parti, &dummy);
       kpre[tid] = inc - c;
       __syncthreads();
     }

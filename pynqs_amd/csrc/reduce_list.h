@@ -63,8 +63,15 @@ constexpr size_t kCachedDrawLdsPerWave = (size_t)kOneTileCols * (8 + 2);
 // ROW32 (end of round 4): the flushing semi-stochastic form on long rows leaves the float32 copy of the row too (no bitmap: the kept records
 // go through the list and its flushes as before) -- the draws inside the drawn tiles then read their <= 256 columns back instead of
 // enumerating the tile a second time.
-template <int LEN, typename T, bool SAMPLED, bool CACHED = false, bool FLUSH = false, bool ROWOUT = false, bool ROW32 = false>
+// RFORM (ROWOUT only; pynqs_reduce_onepass_form): 0 = the tile sums by fixed-pattern cross-lane moves (op_wave_sum), ONE hand-off of a full
+// tile's kept columns (full_tile()), and the finished tile's sum formed behind the next tile's gathers (settle()); 1 = the tile loop as it
+// was (__shfl_xor butterflies, one hand-off per kept column, the sum in front of the next tile).  The same additions in the same order,
+// records placed by bitmap rank: bit for bit the same outputs (tests/test_gpu_rowout_forms.py).
+template <int LEN, typename T, bool SAMPLED, bool CACHED = false, bool FLUSH = false, bool ROWOUT = false, bool ROW32 = false, int RFORM = 1>
 struct ListKeepSink {
+  static constexpr bool kFixedSums = ROWOUT && RFORM == 0 && (PYNQS_ROWOUT_LEVERS & 1);
+  static constexpr bool kTilewise = ROWOUT && RFORM == 0 && (PYNQS_ROWOUT_LEVERS & 2);
+  static constexpr bool kDeferSum = ROWOUT && RFORM == 0 && (PYNQS_ROWOUT_LEVERS & 4);
   T eps;
   uint32_t *list_n;
   unsigned long long *list_key;  // LDS: column << 32 | position of the value in rec_w (unsorted), sorted afterwards
@@ -78,6 +85,8 @@ struct ListKeepSink {
   unsigned long long tag = 0ull;  // FLUSH: bit 63 for the entries of every tile but tile 0
   float *__restrict__ frow = nullptr;  // ROWOUT: this walker's row of float32 sub-eps elements (global)
   uint32_t *kbm = nullptr;             // ROWOUT: bitmap of the kept columns (LDS): a kept column's place among the records is the rank of its bit
+  double psub = 0.0;                   // kDeferSum: the finished tile's lane sums and its number, until settle()
+  uint32_t ptile = 0xffffffffu;
   template <bool F = FLUSH, typename = std::enable_if_t<F>>
   __device__ __forceinline__ bool pause() const {
     return __builtin_amdgcn_readfirstlane(__atomic_load_n(list_n, __ATOMIC_RELAXED)) > pause_at;
@@ -131,15 +140,79 @@ struct ListKeepSink {
       sub += (double)a;
     }
   }
+  // A full tile of doubles at once (plan_tiles.h: sink_takes_full_tile): the float32 row and `sub` exactly as PYNQS_U calls of pair() leave
+  // them (same stores, same additions in the same order: a kept column adds +0.0 to a sum that is never negative), then ALL kept columns
+  // of the wave's tile in one go -- one LDS atomic by one lane for the tile's total instead of one round trip per kept column slot (a
+  // given slot has a kept lane in 57 % of the Fe2S2 waves: 2.3 divergent blocks and atomics per tile), a lane's slots from the ballots.
+  // Which slot of the list a column gets has no meaning: list_key names the position of its value, ROWOUT places records by bitmap rank.
+  template <bool R = kTilewise, typename = std::enable_if_t<R>>
+  __device__ __forceinline__ void full_tile(uint32_t col, const T (&h)[PYNQS_U][2]) {
+    if ((reinterpret_cast<uintptr_t>(frow + col) & 7u) != 0) {  // (never in this kernel: the pairs start on even columns)
+#pragma unroll
+      for (int u = 0; u < PYNQS_U; ++u) {
+        uint64_t none[LEN];
+        pair(col + 128u * u, h[u][0], h[u][1], none, none);
+      }
+      return;
+    }
+    typedef float f2 __attribute__((ext_vector_type(2)));
+    bool kept[2 * PYNQS_U];
+    uint64_t m[2 * PYNQS_U], any = 0;  // (the ballots are the comparisons' own results: no instruction of their own)
+    uint32_t total = 0;
+#pragma unroll
+    for (int u = 0; u < PYNQS_U; ++u) {
+      const T a0 = fabs(h[u][0]), a1 = fabs(h[u][1]);
+      const bool k0 = a0 >= eps, k1 = a1 >= eps;
+      __builtin_nontemporal_store(f2{k0 ? 0.0f : (float)h[u][0], k1 ? 0.0f : (float)h[u][1]}, reinterpret_cast<f2 *>(frow + col + 128u * u));
+      sub += k0 ? 0.0 : (double)a0;
+      sub += k1 ? 0.0 : (double)a1;
+      kept[2 * u] = k0; kept[2 * u + 1] = k1;
+      m[2 * u] = __ballot(k0); m[2 * u + 1] = __ballot(k1);
+      any |= m[2 * u] | m[2 * u + 1];
+      total += (uint32_t)__popcll(m[2 * u]) + (uint32_t)__popcll(m[2 * u + 1]);
+    }
+    if (!any) return;  // (wave-uniform)
+    uint32_t k = 0;
+    if ((threadIdx.x & 63) == 0) k = atomicAdd(list_n, total);
+    k = __builtin_amdgcn_readfirstlane(k);
+#pragma unroll
+    for (int j = 0; j < 2 * PYNQS_U; ++j) k = __builtin_amdgcn_mbcnt_hi((uint32_t)(m[j] >> 32), __builtin_amdgcn_mbcnt_lo((uint32_t)m[j], k));
+#pragma unroll
+    for (int j = 0; j < 2 * PYNQS_U; ++j) {
+      if (kept[j]) {
+        const uint32_t c = col + 128u * (j >> 1) + (j & 1);
+        if (k < cap) {
+          list_key[k] = ((unsigned long long)c << 32) | k;
+          rec_w[k] = h[j >> 1][j & 1];
+        }
+        ++k;
+        atomicOr(&kbm[c >> 5], 1u << (c & 31u));
+      }
+    }
+  }
+  // The finished tile's sum, left pending by tile_begin (plan_tiles.h: sink_defers_tile_sum): visit_tiles asks for it once the new tile's
+  // gathers are out, so the six dependent cross-lane steps run behind their latency.  The same additions, the same tsum slot.
+  template <bool R = kDeferSum, typename = std::enable_if_t<R>>
+  __device__ __forceinline__ void settle() {
+    if (ptile == 0xffffffffu) return;
+    double s;
+    if constexpr (kFixedSums) s = op_wave_sum(psub); else s = op_wave_sum_shfl(psub);
+    if ((threadIdx.x & 63) == 0) tsum[ptile] = s;
+    ptile = 0xffffffffu;
+  }
   __device__ __forceinline__ void flush() {
+    if constexpr (kDeferSum) settle();
     if constexpr (SAMPLED && !CACHED) {
       if (tile == 0xffffffffu) return;
-      const double s = op_wave_sum(sub);
+      double s;
+      if constexpr (kFixedSums) s = op_wave_sum(sub); else s = op_wave_sum_shfl(sub);
       if ((threadIdx.x & 63) == 0) tsum[tile] = s;
     }
   }
   __device__ __forceinline__ void tile_begin(uint32_t t) {
-    flush(); tile = t; sub = 0.0;
+    if constexpr (kDeferSum) { psub = sub; ptile = tile; }
+    else flush();
+    tile = t; sub = 0.0;
     if constexpr (FLUSH) tag = t ? (1ull << 63) : 0ull;
   }
 };
@@ -349,7 +422,7 @@ __host__ __device__ constexpr uint32_t flush_list_slots(int len, bool sampled, b
 }
 static_assert((kBlock / 64) * 128 * PYNQS_U_LONG + 64 < 4096 && (kBlock / 64) * 128 * PYNQS_U + 64 < 2048, "the pause threshold of the flushing form");
 
-template <int LEN, typename T, bool SAMPLED, bool CACHED, bool FLUSH = false, bool GTILE = false, bool ROWOUT = false, bool ROW32 = false>
+template <int LEN, typename T, bool SAMPLED, bool CACHED, bool FLUSH = false, bool GTILE = false, bool ROWOUT = false, bool ROW32 = false, int RFORM = 1>
 __device__ __forceinline__ void reduce_onepass_list_body(const uint64_t *__restrict__ bra, const SDParams &p, const PlanLayout &pl, uint32_t nchunks,
                                                          uint32_t chunk_len, uint32_t max_tiles, const T *__restrict__ plan, T eps,
                                                          uint32_t nsample, uint64_t seed, uint32_t P, OnepassOut<T> o) {
@@ -414,7 +487,7 @@ __device__ __forceinline__ void reduce_onepass_list_body(const uint64_t *__restr
   for (;;) {
   const uint32_t room = FLUSH ? (cap > flushed ? min(cap - flushed, P) : 0u) : cap;
   {
-    ListKeepSink<LEN, T, SAMPLED, CACHED, FLUSH, ROWOUT, ROW32> sink{eps, &list_n, list_key, o.rec_w + seg_base + flushed, room, tsum, 0xffffffffu, 0.0,
+    ListKeepSink<LEN, T, SAMPLED, CACHED, FLUSH, ROWOUT, ROW32, RFORM> sink{eps, &list_n, list_key, o.rec_w + seg_base + flushed, room, tsum, 0xffffffffu, 0.0,
                                                                      CACHED ? o.row_cache + (size_t)walker * (p.nsd + 1) : nullptr};
     if constexpr (ROWOUT) { sink.frow = o.row_f32 + (size_t)walker * draw_row_stride(p.nsd + 1); sink.kbm = kbm; }
     if constexpr (ROW32) sink.frow = o.row_f32 + (size_t)walker * draw_row_stride(p.nsd + 1);
@@ -451,7 +524,7 @@ __device__ __forceinline__ void reduce_onepass_list_body(const uint64_t *__restr
     {
       uint32_t dummy;
       const uint32_t c = (uint32_t)__popc(kbm[tid]);
-      const uint32_t inc = draw_block_scan<uint32_t>(c, s_parti, &dummy);
+      const uint32_t inc = draw_block_scan<uint32_t, RFORM == 0 && (PYNQS_ROWOUT_LEVERS & 1)>(c, s_parti, &dummy);
       kpre[tid] = inc - c;
     }
     __syncthreads();
@@ -488,14 +561,14 @@ __device__ __forceinline__ void reduce_onepass_list_body(const uint64_t *__restr
     if (wave == 0) {
       double sl = 0.0;
       for (uint32_t i = lane; i < max_tiles; i += 64) sl += tsum[i];
-      sl = op_wave_sum(sl);
+      if constexpr (RFORM == 0 && (PYNQS_ROWOUT_LEVERS & 1)) sl = op_wave_sum(sl); else sl = op_wave_sum_shfl(sl);
       if (lane == 0) { s_part[kBlock / 64] = sl; if (o.row_sum) o.row_sum[walker] = sl; }
     }
     __syncthreads();  // (also: the row in global memory is complete, kcol is complete, the staging scratch / tile sums are done with)
     const double Srow = s_part[kBlock / 64];
     __syncthreads();
     PYNQS_STAMP(6);
-    rowout_draws<LEN, T>(smem + list_scratch_offset(p), drec, kcol, n, seg_base, p, L, wk, o.row_f32 + (size_t)walker * draw_row_stride(p.nsd + 1), nsample, seed,
+    rowout_draws<LEN, T, RFORM>(smem + list_scratch_offset(p), drec, kcol, n, seg_base, p, L, wk, o.row_f32 + (size_t)walker * draw_row_stride(p.nsd + 1), nsample, seed,
                          walker, Srow, o, &bw_cnt, &bw_base, &s_full, s_part, s_parti);
     PYNQS_STAMP(9);
     return;
@@ -596,7 +669,7 @@ __device__ __forceinline__ void reduce_onepass_list_body(const uint64_t *__restr
           const T a = c < ncomb ? fabs(hrow[c]) : T(0);
           sl += a >= eps ? 0.0 : (double)a;
         }
-        sl = op_wave_sum(sl);
+        sl = op_wave_sum_shfl(sl);
         if (lane == 0) tsum[t] = sl;
       }
       __syncthreads();

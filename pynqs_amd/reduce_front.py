@@ -30,6 +30,9 @@ ROW_F32_MAX_BYTES = int(os.environ.get("PYNQS_ROW_F32_MAX_BYTES", str(16 << 30))
 # the contraction kernel ReduceFrontEnd.contract takes when its caller names none: pynqs_reduce_contract_form's form, with or without
 # its placement flag (include/pynqs_amd.h; what each was worth on the flagship: profiles/contract_stream_ab.txt)
 CONTRACT_FORM = int(os.environ.get("PYNQS_CONTRACT_FORM", str(N.CONTRACT_BATCHED | N.CONTRACT_BY_XCD)), 0)
+# the tile loop ReduceFrontEnd.run takes in the short-row semi-stochastic kernel when its caller names none: pynqs_reduce_onepass_form's form
+# (0: tile sums by fixed-pattern cross-lane moves behind the next tile's gathers, one hand-off of the kept columns per tile; 1: the earlier loop; profiles/rowout_tiles_ab.txt)
+ROWOUT_FORM = int(os.environ.get("PYNQS_ROWOUT_FORM", str(N.ROWOUT_TILEWISE)), 0)
 TILE_SCRATCH_MIN_ROW = int(os.environ.get("PYNQS_TILE_SCRATCH_MIN_ROW", "65536"))  # columns per row from which the tile sums leave the LDS
 
 
@@ -187,18 +190,22 @@ class ReduceFrontEnd:
                 t.record_stream(stream)
 
     # ---- launches -------------------------------------------------------------------------------------------------------
-    def run(self, x: Tensor, plan: Tensor, eps: float, seed: int = 0, lut=None) -> None:
+    def run(self, x: Tensor, plan: Tensor, eps: float, seed: int = 0, lut=None, form: Optional[int] = None) -> None:
         """Enqueue the front end for the walkers `x` (uint8 [n, 8 len]).  `lut`: the hash table of a WavefunctionLUT (its
-        `.hashtable`): determinants found there take their amplitude from the table and do not enter the distinct list."""
+        `.hashtable`): determinants found there take their amplitude from the table and do not enter the distinct list.
+        form: the tile loop of the short-row semi-stochastic kernel, pynqs_reduce_onepass_form's (None: ROWOUT_FORM); the same
+        outputs bit for bit, and no effect on the other forms of the front end."""
+        if form is None:
+            form = ROWOUT_FORM
         if x.size(0) != self.n or not x.is_cuda or x.dtype != torch.uint8 or not x.is_contiguous():
             raise RuntimeError("x must be a contiguous uint8 CUDA tensor with the front end's number of walkers")
         code = N.PYNQS_F64 if self.h_dtype == torch.float64 else N.PYNQS_F32
         if lut is not self._lut:
             self._lut, self._io = lut, self._make_io(lut=lut)
         st = torch.cuda.current_stream(self.device).cuda_stream
-        N.check(N.lib().pynqs_reduce_onepass(x.data_ptr(), self.n, self.sorb, self.nele, self.noa, self.nob, plan.data_ptr(), code,
-                                             float(eps), self.eps_sample, int(seed) & (2**64 - 1), C.byref(self._io), st),
-                "pynqs_reduce_onepass")
+        N.check(N.lib().pynqs_reduce_onepass_form(x.data_ptr(), self.n, self.sorb, self.nele, self.noa, self.nob, plan.data_ptr(), code,
+                                                  float(eps), self.eps_sample, int(seed) & (2**64 - 1), C.byref(self._io), int(form), st),
+                "pynqs_reduce_onepass_form")
 
     def contract(self, values_unique: Tensor, values_table: Optional[Tensor] = None, divide: bool = True,
                  rec_w: Optional[Tensor] = None, srec_w: Optional[Tensor] = None, form: Optional[int] = None) -> Tuple[Tensor, Tensor]:
