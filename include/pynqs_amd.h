@@ -489,11 +489,7 @@ int pynqs_reduce_sample(const uint64_t *bra, int64_t nbatch, int sorb, int nele,
  * Capacities are the caller's; what was NEEDED comes back in seg_count / counters, so that an overflow is detected (and
  * the call repeated with larger buffers) without anything having been read back in between.
  *
- *   pynqs_reduce_onepass_geometry : [host] out[0] = segments (nbatch * chunks), out[1] = fixed slots per segment,
- *                                   out[2] = bytes of the de-duplication table for `dedup_slots` slots of this sorb
- *                                   (dedup_slots passed in out[2] on entry), out[3] = 1 if the fused form exists for
- *                                   this system (LDS budget; with draws on rows of more than 65536 columns: provided
- *                                   io->tile_scratch is given), else 0
+ *   pynqs_reduce_onepass_plan     : [host] what the launch will decide for a system, a batch and the caller's limits; what to allocate
  *   pynqs_reduce_onepass_list_capacity : [host] the largest io->cap_doubles with which pynqs_reduce_onepass keeps a segment's
  *                                   records in an LDS list -- its LIST form (one list per segment) or, without draws, the flushing
  *                                   form (the list is emptied as it fills: 2^30 - 1 = any capacity on rows of more than 65536
@@ -545,36 +541,63 @@ typedef struct pynqs_reduce_io {
   int32_t *uniq_parent; /* optional, [cap_unique]: the walker whose record put the row on the distinct list -- the row is that walker or a
                            single / double excitation of it, which lets an amplitude with cheap updates start from the walker's
                            intermediate values (pynqs_rbm_forward_children) */
-  void *tile_scratch;   /* optional, eps_sample > 0 without row_cache: pynqs_reduce_onepass_tile_scratch_bytes bytes.  The per-tile sums of
+  void *tile_scratch;   /* optional, eps_sample > 0 without row_cache: pynqs_reduce_plan.tile_scratch_bytes bytes.  The per-tile sums of
                            the sub-eps |H| and the tiles' draw counts then live there instead of the LDS (12 bytes per tile: 57 KB per
                            workgroup at sorb 120, which leaves one workgroup per CU); for rows of more than ~65536 columns */
   int64_t tile_scratch_bytes;
   float *row_f32;       /* optional, eps_sample > 0: float[nbatch][stride] scratch, stride = ncomb rounded up to a multiple of 16, 64-byte aligned
-                           (pynqs_reduce_onepass_row_f32_elements).  With it -- and where pynqs_reduce_onepass_wants_row_f32 says 1: rows of up to
+                           (pynqs_reduce_plan.row_f32_elements).  With it -- and in the form PYNQS_REDUCE_ROWOUT: rows of up to
                            8192 columns, Fe2S2 -- the enumeration leaves the row's sub-eps matrix elements there as float32 (kept columns: 0) and
                            the same workgroup then locates the N draws in it: segments of 16 columns, their sums in float64, one lane per draw
                            (binary search over the segments, 64 bytes of the row read back), hit counts by the rank of a column's bit in a bitmap.
                            P(column j) = float32(|H_j|) / sum of those (relative 6e-8 of the reference's |H_j| / S); the weight of a drawn record
                            is the reference's (c / N) sign(H_j) S with S summed in float64.  The drawn records fill the first slots of
                            srec_* in ascending column order.  row_cache / tile_scratch are not used then. */
+  int32_t form;         /* 0: the launch decides its form from the buffers given.  Otherwise the pynqs_reduce_form of the caller's plan: the
+                           launch must arrive at exactly this form from the buffers it was handed, else it returns PYNQS_EINVAL ("plan and
+                           buffers disagree") before anything is enqueued */
 } pynqs_reduce_io;
-int pynqs_reduce_onepass_geometry(int64_t nbatch, int sorb, int nele, int noA, int noB, int eps_sample, int64_t *out4);
-int64_t pynqs_reduce_onepass_tile_scratch_bytes(int64_t nbatch, int sorb, int nele, int noA, int noB, int eps_sample);
+/* The kernel families of the front end (DESIGN.md section 4.3 has the table: when each is taken, what it reads).  Whether the tile sums of
+ * a semi-stochastic call live in io->tile_scratch instead of the LDS is a flag beside the form (pynqs_reduce_plan.tile_sums_global). */
+typedef enum pynqs_reduce_form {
+  PYNQS_REDUCE_LOOKBACK = 1,    /* "lookback":    kept columns compacted by decoupled look-back; needs the de-duplication table */
+  PYNQS_REDUCE_LIST = 2,        /* "list":        a segment's records in an LDS list, no draws */
+  PYNQS_REDUCE_LIST_CACHE = 3,  /* "list_cache":  LIST, the draws read the row back from io->row_cache */
+  PYNQS_REDUCE_LIST_REDRAW = 4, /* "list_redraw": LIST, the drawn tiles are enumerated a second time */
+  PYNQS_REDUCE_FLUSH = 5,       /* "flush":       the list is emptied whenever it is nearly full (with draws: drawn tiles enumerated again) */
+  PYNQS_REDUCE_FLUSH_ROW32 = 6, /* "flush_row32": flushing, the draws read the drawn tiles back from io->row_f32 */
+  PYNQS_REDUCE_ROWOUT = 7       /* "rowout":      LIST with the row's float32 copy in io->row_f32 and sorted draws (short rows) */
+} pynqs_reduce_form;
+const char *pynqs_reduce_form_name(int form); /* the short names above; "?" for anything else.  PYNQS_OP_VERBOSE prints them */
+/* What the decision depends on.  The last five are the caller's permissions and limits (pynqs_amd/reduce_front.py keeps them as module
+ * constants): which optional buffers it is willing to allocate and up to which size, and the row length (columns; < 0: that of
+ * pynqs_reduce_onepass_long_row) from which the tile sums of a semi-stochastic call leave the LDS. */
+typedef struct pynqs_reduce_plan_request {
+  int64_t nbatch, sorb, nele, noA, noB, dtype /* of the integrals: PYNQS_F32 / PYNQS_F64 */, eps_sample, cap_doubles;
+  int64_t with_table, dedup_slots; /* whether io->dedup_table will be given; slots of that table (for table_bytes; 0: not asked) */
+  int64_t allow_row_f32, row_f32_max_bytes, allow_row_cache, row_cache_max_bytes, tile_scratch_min_row;
+} pynqs_reduce_plan_request;
+/* The answer: the form pynqs_reduce_onepass takes when it is handed exactly the optional buffers named here, and its launch parameters.
+ * The buffers are offered in this order: io->row_f32 where the call would use it (row_f32_form 1: whatever its size; 2: within
+ * row_f32_max_bytes), else io->row_cache where the draws are dense in the row (eps_sample * 64 >= columns) and it is within
+ * row_cache_max_bytes, then io->tile_scratch on rows of more than tile_scratch_min_row columns unless the row cache or the sorted-draws
+ * form makes it useless.  The form depends on the offer; an offered buffer is not always read by the final form. */
+typedef struct pynqs_reduce_plan {
+  int64_t form, tile_sums_global; /* pynqs_reduce_form; 1: tile sums and draw counts in io->tile_scratch */
+  int64_t serves, long_row;       /* 0: the front end has no form for this system (LDS), use the multi-pass entry points -- a coarser test
+                                     than the decision: float64 integrals, any cap_doubles; 1: more columns than pynqs_reduce_onepass_long_row() */
+  int64_t segments, nchunks, chunk_len, max_tiles, fixed;
+  int64_t list_slots, lds_bytes, table_bytes; /* P; dynamic LDS per workgroup; bytes of a de-duplication table of request.dedup_slots slots */
+  int64_t row_f32_form; /* what io->row_f32 was wanted for: 1 sorted draws, 2 flushing form, 0 not (2 stays when row_f32_max_bytes forbids it) */
+  int64_t row_f32_elements, row_cache_elements, tile_scratch_bytes; /* to allocate: floats / elements of the integral dtype / bytes; 0: none */
+} pynqs_reduce_plan;
+int pynqs_reduce_onepass_plan(const pynqs_reduce_plan_request *request, pynqs_reduce_plan *plan);
+int64_t pynqs_reduce_onepass_long_row(void); /* columns */
 int pynqs_reduce_onepass_list_capacity(int64_t nbatch, int sorb, int nele, int noA, int noB, int dtype, int eps_sample,
                                        int with_row_cache, int without_table, int64_t *cap_doubles);
-/* 1 when a call with these arguments takes the round-4 semi-stochastic form if io->row_f32 is given (rows of up to 8192 columns, at most
- * 16383 draws, kept records within the list: Fe2S2); 2 when it takes the flushing form (rows of any length, kept records beyond the list),
- * whose draws then read the drawn tiles back from io->row_f32 instead of enumerating them a second time (4 bytes per column and walker:
- * the caller decides whether that is affordable; io->tile_scratch is still wanted on long rows); 0 when the buffer would not be used
- * (leave row_f32 NULL then), -1 on bad arguments;
- * ..._row_f32_elements: floats io->row_f32 must hold for nbatch walkers (-1 on bad arguments). */
-int pynqs_reduce_onepass_wants_row_f32(int64_t nbatch, int sorb, int nele, int noA, int noB, int dtype, int eps_sample, int64_t cap_doubles,
-                                       int with_tile_scratch /* whether the call will also pass io->tile_scratch */,
-                                       int without_table /* whether io->dedup_table will be NULL */);
-int64_t pynqs_reduce_onepass_row_f32_elements(int64_t nbatch, int sorb, int nele, int noA, int noB);
 int pynqs_reduce_onepass(const uint64_t *bra, int64_t nbatch, int sorb, int nele, int noA, int noB, const void *plan,
                          int dtype, double eps, int eps_sample, uint64_t seed, const pynqs_reduce_io *io, void *stream);
-/* the same with the tile loop of the short-row semi-stochastic kernel (the form that ..._wants_row_f32 answers 1 for) chosen per call; the
+/* the same with the tile loop of the short-row semi-stochastic kernel (PYNQS_REDUCE_ROWOUT) chosen per call; the
  * other forms of the front end have one tile loop and ignore the choice.  PYNQS_ROWOUT_TILEWISE (what pynqs_reduce_onepass takes): the tile
  * sums by cross-lane moves of a fixed pattern and formed behind the next tile's gathers, the kept columns of a full tile of doubles handed
  * to the list together (one LDS atomic per tile).  PYNQS_ROWOUT_PER_COLUMN: __shfl_xor butterflies in front of the next tile, one hand-off
@@ -608,7 +631,7 @@ int64_t pynqs_reduce_contract_group(int64_t b, int64_t B);
 int pynqs_reduce_contract_form(int64_t nbatch, int sorb, int nele, int noA, int noB, int dtype, int eps_sample,
                                const pynqs_reduce_io *io, const double *psi_unique, const double *psi_table, int psi_is_complex,
                                int divide, double *eloc, double *psi_x, int form, void *stream);
-/* ---- the draw law of the short-row form (pynqs_reduce_onepass where pynqs_reduce_onepass_wants_row_f32 says 1 and io->row_f32 is given:
+/* ---- the draw law of the short-row form (pynqs_reduce_onepass in its form PYNQS_REDUCE_ROWOUT:
  * rows of at most 8192 columns, at most 16383 draws, the kept records within the list; pynqs_amd/csrc/reduce_draw.h).  This form's random
  * STREAM is part of the contract: which columns walker i draws, and how often, is a pure function of (seed, *io->seed_dev, i, the row).
  * tests/reduce_replay.py replays it on the host; tests/test_gpu_reduce_replay.py compares every record.
@@ -636,7 +659,7 @@ int pynqs_reduce_contract_form(int64_t nbatch, int sorb, int nele, int noA, int 
  *    the exact sub-eps |H_j| (within ncomb 2^-52 relative of the exact sum; the weight within (ncomb + 2) 2^-52 relative).
  *  - Limits: ncomb <= 8192 columns and N <= 16383 draws (a record waits as count << 16 | sign << 15 | column); beyond either the call
  *    takes one of the forms below.
- * The other semi-stochastic forms -- the flushing and look-back forms of this entry point (wants_row_f32 = 2 or 0), the LIST form with
+ * The other semi-stochastic forms -- the flushing and look-back forms of this entry point, the LIST form with
  * io->row_cache or io->tile_scratch, and the multi-pass pynqs_reduce_count_sums / pynqs_reduce_sample -- draw HIERARCHICALLY: first the tile
  * (in proportion to the tiles' sums of sub-eps |H|), then the column inside the tile in the tile's enumeration order, with streams keyed by (seed, walker
  * or slot, tile, k).  Only their LAW is contractual -- P(column j) = |H_j| / S, N draws per walker with replacement, the same records and

@@ -96,15 +96,27 @@ class ReduceIO(C.Structure):
                 ("srec_col", _vp), ("srec_w", _vp), ("srec_onv", _vp), ("srec_link", _vp), ("row_sum", _vp),
                 ("dedup_table", _vp), ("uniq_onv", _vp), ("uniq_pm1", _vp), ("pm1_dtype", C.c_int32), ("lut_is_hash", C.c_int32),
                 ("lut_table", _vp), ("lut_nkeys", _i64), ("counters", _vp), ("seed_dev", _vp), ("row_cache", _vp), ("uniq_parent", _vp),
-                ("tile_scratch", _vp), ("tile_scratch_bytes", _i64), ("row_f32", _vp)]
+                ("tile_scratch", _vp), ("tile_scratch_bytes", _i64), ("row_f32", _vp), ("form", C.c_int32)]
+
+
+class ReducePlanRequest(C.Structure):
+    """include/pynqs_amd.h: pynqs_reduce_plan_request"""
+    _fields_ = [(f, _i64) for f in ("nbatch", "sorb", "nele", "noA", "noB", "dtype", "eps_sample", "cap_doubles", "with_table", "dedup_slots",
+                                    "allow_row_f32", "row_f32_max_bytes", "allow_row_cache", "row_cache_max_bytes", "tile_scratch_min_row")]
+
+
+class ReducePlan(C.Structure):
+    """include/pynqs_amd.h: pynqs_reduce_plan"""
+    _fields_ = [(f, _i64) for f in ("form", "tile_sums_global", "serves", "long_row", "segments", "nchunks", "chunk_len", "max_tiles", "fixed",
+                                    "list_slots", "lds_bytes", "table_bytes", "row_f32_form", "row_f32_elements", "row_cache_elements",
+                                    "tile_scratch_bytes")]
 
 
 SIGNATURES.update({
-    "pynqs_reduce_onepass_geometry": (_int, [_i64, _int, _int, _int, _int, _int, C.POINTER(_i64)]),
-    "pynqs_reduce_onepass_tile_scratch_bytes": (_i64, [_i64, _int, _int, _int, _int, _int]),
+    "pynqs_reduce_onepass_plan": (_int, [C.POINTER(ReducePlanRequest), C.POINTER(ReducePlan)]),
+    "pynqs_reduce_form_name": (C.c_char_p, [_int]),
+    "pynqs_reduce_onepass_long_row": (_i64, []),
     "pynqs_reduce_onepass_list_capacity": (_int, [_i64, _int, _int, _int, _int, _int, _int, _int, _int, C.POINTER(_i64)]),
-    "pynqs_reduce_onepass_wants_row_f32": (_int, [_i64, _int, _int, _int, _int, _int, _int, _i64, _int, _int]),
-    "pynqs_reduce_onepass_row_f32_elements": (_i64, [_i64, _int, _int, _int, _int]),
     "pynqs_reduce_onepass": (_int, [_vp, _i64, _int, _int, _int, _int, _vp, _int, _dbl, _int, C.c_uint64, C.POINTER(ReduceIO), _vp]),
     "pynqs_reduce_onepass_form": (_int, [_vp, _i64, _int, _int, _int, _int, _vp, _int, _dbl, _int, C.c_uint64, C.POINTER(ReduceIO), _int, _vp]),
     "pynqs_debug_wave_sum": (_int, [_vp, _vp, _i64, _int, _vp]),

@@ -740,192 +740,176 @@ __global__ __launch_bounds__(kBlock) void reduce_clear_kernel(uint4 *__restrict_
 
 using namespace pynqs;
 
-static int onepass_geometry(int64_t nbatch, const SDParams &p, bool sampled, uint32_t *nchunks, uint32_t *chunk_len, uint32_t *max_tiles,
-                            uint32_t *fixed) {
+struct OnepassGeometry { uint32_t nchunks, chunk_len, max_tiles, fixed; };
+static OnepassGeometry onepass_geometry(int64_t nbatch, const SDParams &p, bool sampled) {
+  OnepassGeometry g;
   const uint32_t ncomb = p.nsd + 1;
   if (sampled) {  // the draws need the sums of the WHOLE row in one workgroup's LDS
-    *nchunks = 1;
-    *chunk_len = (ncomb + 255u) & ~255u;
+    g.nchunks = 1;
+    g.chunk_len = (ncomb + 255u) & ~255u;
   } else {
-    plan_chunks(nbatch, ncomb, nchunks, chunk_len);
+    plan_chunks(nbatch > 0 ? nbatch : 1, ncomb, &g.nchunks, &g.chunk_len);  // (no walkers: one walker's chunks; plan_chunks divides by the count)
   }
-  *max_tiles = max_tiles_per_chunk(p, *nchunks, *chunk_len);
+  g.max_tiles = max_tiles_per_chunk(p, g.nchunks, g.chunk_len);
   const uint32_t tS_all = (p.d1 + kSinglesPerTile - 1) / kSinglesPerTile;
-  *fixed = kFixedHead + ((tS_all + *nchunks - 1) / *nchunks) * kSinglesPerTile;
-  return 0;
+  g.fixed = kFixedHead + ((tS_all + g.nchunks - 1) / g.nchunks) * kSinglesPerTile;
+  return g;
 }
 
 static size_t onepass_static_lds(int) { return 16 + (kBlock / 64) * 4 + (kBlock / 64 + 1) * 12 + 64; }
 
-extern "C" int pynqs_reduce_onepass_geometry(int64_t nbatch, int sorb, int nele, int noA, int noB, int eps_sample, int64_t *out4) {
-  SDParams p;
-  PlanLayout pl;
-  if (!out4) return set_error(PYNQS_EINVAL, "null pointer");
-  if (!make_sd_params(sorb, nele, noA, noB, &p) || !make_plan_layout(sorb, &pl)) return set_error(PYNQS_EINVAL, "bad sorb/noA/noB (even sorb in [2, 192])");
-  if (nbatch < 0 || nbatch > 0x7fffffffll || eps_sample < 0 || eps_sample > 65535) return set_error(PYNQS_EINVAL, "bad nbatch / eps_sample (at most 65535 draws)");
-  uint32_t nchunks, chunk_len, max_tiles, fixed;
-  onepass_geometry(nbatch, p, eps_sample > 0, &nchunks, &chunk_len, &max_tiles, &fixed);
-  const int len = (sorb - 1) / 64 + 1;
-  const int64_t slots = out4[2];
-  out4[0] = nbatch * (int64_t)nchunks;
-  out4[1] = fixed;
-  out4[2] = slots > 0 ? slots * dedup_slot_words(len) * 8 : 0;
-  // the look-back form, or (draws on long rows, io->tile_scratch given) the flushing LIST form with its tile sums in global memory
-  const bool lookback = onepass_lds(p, 8, max_tiles, eps_sample > 0, winner_list_cap(eps_sample)) + onepass_static_lds(len) <= 160 * 1024;
-  const bool flushing = eps_sample > 0 && p.nsd + 1 > 65536 &&
-                        onepass_list_lds(p, 8, max_tiles, true, 2048, (uint32_t)eps_sample, false, true) + 256 + onepass_static_lds(len) <= 160 * 1024;
-  out4[3] = lookback || flushing ? 1 : 0;
-  return PYNQS_OK;
+// ---- which form a call takes: ONE decision for the launch and pynqs_reduce_onepass_plan alike (the table and the measurements: DESIGN.md 4.3)
+constexpr uint32_t kLongRow = 65536;  // columns from which the look-back form is the slow one
+// what a call hands the launch / what a plan offers it: io->row_cache, no io->dedup_table, io->tile_scratch (large enough), io->row_f32
+struct OnepassOffer { bool row_cache, no_table, tile_scratch, row_f32; };
+// form: pynqs_reduce_form; gtile: tile sums in global memory; P: list slots (look-back: slots of the winner list); lds: dynamic LDS bytes
+struct OnepassDecision { int form; bool gtile; uint32_t P; size_t lds; };
+
+// the overrides of the decision (development; DESIGN.md section 4.3 says what each value does): -1 unset
+struct OnepassEnv { int list, cache, flush, row32; };
+static const OnepassEnv &onepass_env() {
+  auto get = [](const char *name) { const char *v = getenv(name); return v ? atoi(v) : -1; };
+  static const OnepassEnv env = {get("PYNQS_OP_LIST"), get("PYNQS_OP_CACHE"), get("PYNQS_OP_FLUSH"), get("PYNQS_OP_ROW32")};
+  return env;
 }
 
-// Which of the two forms a call takes.  LIST form when a segment's records fit an LDS list (PYNQS_OP_LIST=0 / 1 overrides; 1 only where it
-// fits): up to 1024 slots per segment, up to 2048 on rows of more than kLongRow columns -- there the look-back form is the slow one (sorb 80
-// / 120: 2 to 4 times slower than the multi-pass entry points, tools/reduce_big_paths.py; energy.py routes such calls away from it), on short
-// rows a list of 2048 costs more than it saves.  With a row cache (io->row_cache: [nbatch][ncomb] elements of the integral dtype) the draws
-// read the row back instead of visiting the drawn tiles a second time (PYNQS_OP_CACHE=0 ignores the buffer); LIST form only.
-constexpr uint32_t kLongRow = 65536;
-struct OnepassForm {
-  uint32_t P;
-  bool use_list, use_cache, use_flush, use_gtile;
-  size_t lds;
-  bool use_split = false;  // LIST kernel with the row's float32 copy in global memory and the draws of reduce_draw.h (kernels_reduce_rowout.hip)
-  bool use_row32 = false;  // flushing semi-stochastic form whose draws read the drawn tiles back from the row's float32 copy (same file)
-};
-// (list slots of the flushing form: flush_list_slots(), reduce_list.h)
-static OnepassForm onepass_form(const SDParams &p, size_t esz, uint32_t max_tiles, uint32_t fixed, uint64_t cap_doubles, int eps_sample,
-                                bool have_cache, uint32_t chunk_len, bool no_table, bool have_tile_scratch = false, bool have_row_f32 = false) {
-  static const int list_env = getenv("PYNQS_OP_LIST") ? atoi(getenv("PYNQS_OP_LIST")) : -1;
-  static const int cache_env = getenv("PYNQS_OP_CACHE") ? atoi(getenv("PYNQS_OP_CACHE")) : -1;
-  static const int flush_env = getenv("PYNQS_OP_FLUSH") ? atoi(getenv("PYNQS_OP_FLUSH")) : -1;
+// dynamic LDS of a form with P list slots (the only place that spells onepass_list_lds' flags out)
+static size_t onepass_form_lds(const SDParams &p, size_t esz, uint32_t max_tiles, int eps_sample, int form, bool gtile, uint32_t P) {
   const bool sampled = eps_sample > 0;
-  const uint64_t seg_cap = (uint64_t)fixed + cap_doubles;
-  OnepassForm f;
-  f.P = 64;
-  while (f.P < seg_cap && f.P < (1u << 20)) f.P <<= 1;
-  const bool want_cache = sampled && have_cache && cache_env != 0;
-  const bool gtile = sampled && !want_cache && have_tile_scratch;  // tile sums / draw counts in global memory (long rows)
-  const size_t lds_list = onepass_list_lds(p, esz, max_tiles, sampled, f.P, (uint32_t)eps_sample, want_cache, gtile);
-  const bool list_fits = seg_cap <= 2048 && lds_list + 256 <= 160 * 1024;
-  f.use_list = list_env == 0 ? false : (list_fits && (list_env == 1 || seg_cap <= 1024 || p.nsd + 1 > kLongRow));
-  f.use_cache = want_cache && f.use_list;
-  f.use_gtile = gtile && f.use_list;
-  f.lds = f.use_list ? lds_list : onepass_lds(p, esz, max_tiles, sampled, winner_list_cap(eps_sample));
-  // the two-kernel form takes over from the row cache / the re-enumerating form when the caller passed io->row_f32 and the kept records fit
-  // the list (PYNQS_OP_SPLIT=0 ignores the buffer)
-  static const int split_env = getenv("PYNQS_OP_SPLIT") ? atoi(getenv("PYNQS_OP_SPLIT")) : -1;
-  if (sampled && have_row_f32 && split_env != 0 && list_env != 0 && seg_cap <= 1024 && reduce_draw_supported(p, eps_sample)) {
-    // (no sort in this form: the list needs as many slots as a segment has records, not a power of two)
-    const uint32_t slots = ((uint32_t)seg_cap + 1u) & ~1u;
-    const size_t lds_a = onepass_list_lds(p, esz, max_tiles, true, slots, (uint32_t)eps_sample, false, false, true);
-    if (lds_a + 256 <= 160 * 1024) {
-      f.P = slots;
-      f.use_list = true; f.use_split = true; f.use_cache = f.use_gtile = f.use_flush = false; f.lds = lds_a;
-      return f;
-    }
+  const uint32_t ns = (uint32_t)eps_sample;
+  switch (form) {
+    case PYNQS_REDUCE_LIST: return onepass_list_lds(p, esz, max_tiles, false, P, ns, false, false);
+    case PYNQS_REDUCE_LIST_CACHE: return onepass_list_lds(p, esz, max_tiles, true, P, ns, true, false);
+    case PYNQS_REDUCE_LIST_REDRAW: return onepass_list_lds(p, esz, max_tiles, true, P, ns, false, gtile);
+    case PYNQS_REDUCE_FLUSH: return onepass_list_lds(p, esz, max_tiles, sampled, P, ns, false, gtile);
+    case PYNQS_REDUCE_FLUSH_ROW32: return onepass_list_lds(p, esz, max_tiles, true, P, ns, false, gtile, false, true);
+    case PYNQS_REDUCE_ROWOUT: return onepass_list_lds(p, esz, max_tiles, true, P, ns, false, false, true);
+    default: return onepass_lds(p, esz, max_tiles, sampled, P);
   }
-  // the flushing LIST form: deterministic calls whose kept columns do not fit the list -- on long rows, on any row when at most a tenth
-  // of a segment's columns can be kept (a flush costs a sort of 2048 entries; the look-back form pays per tile instead: Fe2S2 with 9 % kept
-  // 0.81 look-back against 2.45 ms, sorb 56 with 6 % 6.5 against 3.7, sorb 80 with 10 % / 40 % 103 / 292 against 71 / 269), and whenever
-  // there is no de-duplication table (the look-back form needs one).  PYNQS_OP_FLUSH=0 / 1: never / wherever possible.
-  // With draws the kept list is flushed during the enumeration in the same way, under the same rule; the draws follow as before (sorb 56,
-  // 200 draws, 2 % / 6 % kept: 6.2 / 7.1 ms look-back -> 1.6 / 2.2 flushing and table-less; Fe2S2, 9 %: 1.37 stays).  A row cache is not
-  // used by this form: when the LIST form with the cache does not fit, flushing without it beats the look-back form (sorb 56, 1000 draws:
-  // 6.2 / 3.8 -> 2.6 / 1.9 ms).
-  const bool gtile_f = sampled && have_tile_scratch;
-  const uint32_t flush_P = flush_list_slots((p.sorb - 1) / 64 + 1, sampled);
-  const size_t lds_flush = onepass_list_lds(p, esz, max_tiles, sampled, flush_P, (uint32_t)eps_sample, false, gtile_f);
-  const bool long_row = p.nsd + 1 > kLongRow;
-  f.use_flush = !f.use_list && flush_env != 0 && lds_flush + 256 <= 160 * 1024 &&
-                (long_row || flush_env == 1 || no_table || cap_doubles * 10 <= (uint64_t)chunk_len);
-  if (f.use_flush) { f.use_gtile = gtile_f; f.use_cache = false; }
-  if (f.use_flush) { f.P = flush_P; f.lds = lds_flush; }
-  // (PYNQS_OP_ROW32=0: the drawn tiles are enumerated a second time, as before the end of round 4)
-  static const int row32_env = getenv("PYNQS_OP_ROW32") ? atoi(getenv("PYNQS_OP_ROW32")) : -1;
-  // The copy costs 4 bytes of stores per column; it pays where it puts more workgroups on a CU (no draw areas of their own: sorb 120 four
-  // instead of two, 6.30 -> 4.79 ms per 1024 walkers) or where a good part of the tiles is drawn (sorb 56 / 80, 1000 draws: 1.81 -> 1.34 /
-  // 3.41 -> 2.54 ms); at sorb 184 (26146 tiles, two workgroups per CU either way) 1000 draws re-enumerate 4 % of the row and the copy is
-  // the dearer of the two (13.1 -> 13.9 ms per 512 walkers): not used there.  PYNQS_OP_ROW32=1: wherever it fits.
-  // The LIST form that enumerates the drawn tiles again (kept records within the list, no row cache) gives way to the same kernel under
-  // the same rule: a list that never fills is never flushed.
-  const bool from_list = f.use_list && !f.use_cache && flush_env != 0;
-  if ((f.use_flush || from_list) && sampled && have_row_f32 && row32_env != 0 && row32_fits(esz, flush_P, (uint32_t)eps_sample, gtile_f)) {
-    const size_t lds_r = onepass_list_lds(p, esz, max_tiles, true, flush_P, (uint32_t)eps_sample, false, gtile_f, false, true);
-    const size_t wg_old = (size_t)160 * 1024 / ((f.use_flush ? lds_flush : f.lds) + 512), wg_new = (size_t)160 * 1024 / (lds_r + 512);
-    if (lds_r + 256 <= 160 * 1024 && (row32_env == 1 || wg_new > wg_old || (uint64_t)eps_sample * 8 >= max_tiles)) {
-      f.use_row32 = true; f.use_flush = true; f.use_list = false; f.use_cache = false; f.use_gtile = gtile_f; f.P = flush_P; f.lds = lds_r;
-    }
-  }
-  return f;
 }
 
-extern "C" int64_t pynqs_reduce_onepass_tile_scratch_bytes(int64_t nbatch, int sorb, int nele, int noA, int noB, int eps_sample) {
-  SDParams p;
-  PlanLayout pl;
-  if (!make_sd_params(sorb, nele, noA, noB, &p) || !make_plan_layout(sorb, &pl) || nbatch < 0 || nbatch > 0x7fffffffll || eps_sample < 0 || eps_sample > 65535) {
-    set_error(PYNQS_EINVAL, "bad arguments");
-    return -1;
+static OnepassDecision onepass_decide(const SDParams &p, size_t esz, const OnepassGeometry &g, uint64_t cap_doubles, int eps_sample, const OnepassOffer &o) {
+  const OnepassEnv &env = onepass_env();
+  constexpr size_t kLds = 160 * 1024 - 256;  // (what a list form may ask for)
+  const bool sampled = eps_sample > 0, long_row = p.nsd + 1 > kLongRow;
+  const uint64_t seg_cap = (uint64_t)g.fixed + cap_doubles;
+  auto with = [&](int form, bool gtile, uint32_t P) { return OnepassDecision{form, gtile, P, onepass_form_lds(p, esz, g.max_tiles, eps_sample, form, gtile, P)}; };
+  // sorted draws from the row's float32 copy: short rows whose kept records fit a list of as many slots as the segment has records
+  if (sampled && o.row_f32 && env.list != 0 && seg_cap <= 1024 && reduce_draw_supported(p, eps_sample)) {
+    const OnepassDecision d = with(PYNQS_REDUCE_ROWOUT, false, ((uint32_t)seg_cap + 1u) & ~1u);
+    if (d.lds <= kLds) return d;
   }
-  if (eps_sample == 0) return 0;
-  uint32_t nchunks, chunk_len, max_tiles, fixed;
-  onepass_geometry(nbatch, p, true, &nchunks, &chunk_len, &max_tiles, &fixed);
-  return (int64_t)((size_t)nbatch * tile_scratch_stride(max_tiles));
+  // a list per segment: up to 1024 slots, up to 2048 on long rows
+  const bool cache = sampled && o.row_cache && env.cache != 0;
+  uint32_t P = 64;
+  while (P < seg_cap && P < (1u << 20)) P <<= 1;
+  const OnepassDecision list = with(cache ? PYNQS_REDUCE_LIST_CACHE : sampled ? PYNQS_REDUCE_LIST_REDRAW : PYNQS_REDUCE_LIST, sampled && !cache && o.tile_scratch, P);
+  const bool use_list = env.list != 0 && seg_cap <= 2048 && list.lds <= kLds && (env.list == 1 || seg_cap <= 1024 || long_row);
+  // the flushing list where the records do not fit one: on long rows, without a table, or when at most a tenth of the columns can be kept
+  const bool gtile_f = sampled && o.tile_scratch;
+  const uint32_t flush_P = flush_list_slots((p.sorb - 1) / 64 + 1, sampled);
+  const OnepassDecision flush = with(PYNQS_REDUCE_FLUSH, gtile_f, flush_P);
+  const bool use_flush = !use_list && env.flush != 0 && flush.lds <= kLds &&
+                         (long_row || env.flush == 1 || o.no_table || cap_doubles * 10 <= (uint64_t)g.chunk_len);
+  // either gives way to the flushing form that reads the drawn tiles back from the float32 copy, where that puts more workgroups on a CU or
+  // a good part of the tiles is drawn (a list that never fills is never flushed)
+  if ((use_flush || (use_list && !cache && env.flush != 0)) && sampled && o.row_f32 && env.row32 != 0 && row32_fits(esz, flush_P, (uint32_t)eps_sample, gtile_f)) {
+    const OnepassDecision row32 = with(PYNQS_REDUCE_FLUSH_ROW32, gtile_f, flush_P);
+    const size_t wg_old = (size_t)160 * 1024 / ((use_flush ? flush.lds : list.lds) + 512), wg_new = (size_t)160 * 1024 / (row32.lds + 512);
+    if (row32.lds <= kLds && (env.row32 == 1 || wg_new > wg_old || (uint64_t)eps_sample * 8 >= g.max_tiles)) return row32;
+  }
+  if (use_flush) return flush;
+  if (use_list) return list;
+  return with(PYNQS_REDUCE_LOOKBACK, false, winner_list_cap(eps_sample));
+}
+
+extern "C" int64_t pynqs_reduce_onepass_long_row(void) { return kLongRow; }
+
+extern "C" const char *pynqs_reduce_form_name(int form) {
+  static const char *const names[] = {"?", "lookback", "list", "list_cache", "list_redraw", "flush", "flush_row32", "rowout"};
+  return names[form >= PYNQS_REDUCE_LOOKBACK && form <= PYNQS_REDUCE_ROWOUT ? form : 0];
+}
+
+// the system and the sizes every host entry point of the front end takes
+static bool onepass_arguments(int64_t nbatch, int64_t sorb, int64_t nele, int64_t noA, int64_t noB, int64_t dtype, int64_t eps_sample, SDParams *p) {
+  PlanLayout pl;
+  for (int64_t v : {sorb, nele, noA, noB})
+    if (v < 0 || v > 1024) return false;
+  return make_sd_params((int)sorb, (int)nele, (int)noA, (int)noB, p) && make_plan_layout((int)sorb, &pl) && nbatch >= 0 && nbatch <= 0x7fffffffll &&
+         eps_sample >= 0 && eps_sample <= 65535 && (dtype == PYNQS_F32 || dtype == PYNQS_F64);
+}
+
+extern "C" int pynqs_reduce_onepass_plan(const pynqs_reduce_plan_request *r, pynqs_reduce_plan *out) {
+  SDParams p;
+  if (!r || !out) return set_error(PYNQS_EINVAL, "null pointer");
+  if (!onepass_arguments(r->nbatch, r->sorb, r->nele, r->noA, r->noB, r->dtype, r->eps_sample, &p) || r->cap_doubles < 0 || r->dedup_slots < 0)
+    return set_error(PYNQS_EINVAL, "bad sorb/noA/noB (even sorb in [2, 192]) / nbatch / eps_sample (at most 65535 draws) / dtype / capacities");
+  const int eps_sample = (int)r->eps_sample, len = ((int)r->sorb - 1) / 64 + 1;
+  const bool sampled = eps_sample > 0;
+  const int64_t n = r->nbatch, ncomb = (int64_t)p.nsd + 1;
+  const size_t esz = r->dtype == PYNQS_F64 ? 8 : 4;
+  const OnepassGeometry g = onepass_geometry(n, p, sampled);
+  *out = pynqs_reduce_plan{};
+  out->segments = n * (int64_t)g.nchunks;
+  out->nchunks = g.nchunks; out->chunk_len = g.chunk_len; out->max_tiles = g.max_tiles; out->fixed = g.fixed;
+  out->table_bytes = r->dedup_slots * dedup_slot_words(len) * 8; out->long_row = ncomb > kLongRow;
+  // serves: a coarser test than onepass_decide(), as it always was (float64 integrals, 2048 slots, any cap_doubles): the look-back form fits,
+  // or (draws on long rows) the flushing form with its tile sums in global memory does
+  const bool lookback = onepass_form_lds(p, 8, g.max_tiles, eps_sample, PYNQS_REDUCE_LOOKBACK, false, winner_list_cap(eps_sample)) + onepass_static_lds(len) <= 160 * 1024;
+  const bool flushing = sampled && out->long_row &&
+                        onepass_form_lds(p, 8, g.max_tiles, eps_sample, PYNQS_REDUCE_FLUSH, true, 2048) + 256 + onepass_static_lds(len) <= 160 * 1024;
+  out->serves = lookback || flushing;
+  auto decide = [&](bool row_cache, bool tile_scratch, bool row_f32) {
+    return onepass_decide(p, esz, g, (uint64_t)r->cap_doubles, eps_sample, OnepassOffer{row_cache, !r->with_table, tile_scratch, row_f32});
+  };
+  // what to offer.  First the float32 row copy, where a call that gets it would use it (the flushing form is asked with the tile scratch it
+  // would also get); then the row cache, where the draws are dense in the row; then, on long rows, the tile scratch
+  const bool tiles_row = sampled && ncomb > (r->tile_scratch_min_row < 0 ? (int64_t)kLongRow : r->tile_scratch_min_row);
+  if (sampled && r->allow_row_f32)
+    out->row_f32_form = decide(false, false, true).form == PYNQS_REDUCE_ROWOUT ? 1 : decide(false, tiles_row, true).form == PYNQS_REDUCE_FLUSH_ROW32 ? 2 : 0;
+  const int64_t row_f32 = n * (int64_t)draw_row_stride((uint32_t)ncomb);
+  if (out->row_f32_form == 1 || (out->row_f32_form == 2 && 4 * row_f32 <= r->row_f32_max_bytes)) out->row_f32_elements = row_f32 > 1 ? row_f32 : 1;
+  if (!out->row_f32_elements && sampled && r->allow_row_cache && (int64_t)eps_sample * 64 >= ncomb && n * ncomb * (int64_t)esz <= r->row_cache_max_bytes)
+    out->row_cache_elements = n * ncomb > 1 ? n * ncomb : 1;
+  if (tiles_row && !out->row_cache_elements && (!out->row_f32_elements || out->row_f32_form == 2))
+    out->tile_scratch_bytes = n * (int64_t)tile_scratch_stride(g.max_tiles);
+  const OnepassDecision d = decide(out->row_cache_elements > 0, out->tile_scratch_bytes > 0, out->row_f32_elements > 0);
+  out->form = d.form; out->tile_sums_global = d.gtile; out->list_slots = d.P; out->lds_bytes = (int64_t)d.lds;
+  return PYNQS_OK;
 }
 
 extern "C" int pynqs_reduce_onepass_list_capacity(int64_t nbatch, int sorb, int nele, int noA, int noB, int dtype, int eps_sample,
                                                   int with_row_cache, int without_table, int64_t *cap_doubles) {
   SDParams p;
-  PlanLayout pl;
   if (!cap_doubles) return set_error(PYNQS_EINVAL, "null pointer");
-  if (!make_sd_params(sorb, nele, noA, noB, &p) || !make_plan_layout(sorb, &pl)) return set_error(PYNQS_EINVAL, "bad sorb/noA/noB (even sorb in [2, 192])");
-  if (nbatch < 0 || nbatch > 0x7fffffffll || eps_sample < 0 || eps_sample > 65535 || (dtype != PYNQS_F32 && dtype != PYNQS_F64))
-    return set_error(PYNQS_EINVAL, "bad nbatch / eps_sample / dtype");
-  uint32_t nchunks, chunk_len, max_tiles, fixed;
-  onepass_geometry(nbatch, p, eps_sample > 0, &nchunks, &chunk_len, &max_tiles, &fixed);
-  const size_t esz = dtype == PYNQS_F64 ? 8 : 4;
+  if (!onepass_arguments(nbatch, sorb, nele, noA, noB, dtype, eps_sample, &p)) return set_error(PYNQS_EINVAL, "bad sorb/noA/noB (even sorb in [2, 192]) / nbatch / eps_sample / dtype");
+  const OnepassGeometry g = onepass_geometry(nbatch, p, eps_sample > 0);
   auto listed = [&](uint64_t cap) {
-    // (with draws and no row cache the caller is expected to pass io->tile_scratch: pynqs_reduce_onepass_tile_scratch_bytes)
-    const OnepassForm f = onepass_form(p, esz, max_tiles, fixed, cap, eps_sample, with_row_cache != 0, chunk_len, without_table != 0,
-                                       eps_sample > 0 && with_row_cache == 0);
-    return (f.use_list || f.use_flush) && f.lds + onepass_static_lds(0) <= 160 * 1024;
+    // (with draws and no row cache the caller is expected to pass io->tile_scratch)
+    const OnepassDecision d = onepass_decide(p, dtype == PYNQS_F64 ? 8 : 4, g, cap, eps_sample,
+                                             OnepassOffer{with_row_cache != 0, without_table != 0, eps_sample > 0 && with_row_cache == 0, false});
+    return d.form != PYNQS_REDUCE_LOOKBACK && d.lds + onepass_static_lds(0) <= 160 * 1024;
   };
   *cap_doubles = -1;
   // (the forms are monotonic in the capacity: LIST up to a limit, then possibly the flushing form up to another, or without one)
   if (listed((uint64_t)1 << 29)) { *cap_doubles = ((int64_t)1 << 30) - 1; return PYNQS_OK; }
-  for (uint32_t seg = 2048; seg >= 128; seg >>= 1) {
-    if (seg < fixed) break;
-    if (listed(seg - fixed)) { *cap_doubles = (int64_t)(seg - fixed); break; }
-  }
-  if ((int64_t)(chunk_len / 10) > *cap_doubles && listed(chunk_len / 10)) *cap_doubles = chunk_len / 10;
+  for (uint32_t seg = 2048; seg >= 128 && seg >= g.fixed; seg >>= 1)
+    if (listed(seg - g.fixed)) { *cap_doubles = (int64_t)(seg - g.fixed); break; }
+  if ((int64_t)(g.chunk_len / 10) > *cap_doubles && listed(g.chunk_len / 10)) *cap_doubles = g.chunk_len / 10;
   return PYNQS_OK;
 }
 
-extern "C" int pynqs_reduce_onepass_wants_row_f32(int64_t nbatch, int sorb, int nele, int noA, int noB, int dtype, int eps_sample, int64_t cap_doubles,
-                                                  int with_tile_scratch, int without_table) {
-  SDParams p;
-  PlanLayout pl;
-  if (!make_sd_params(sorb, nele, noA, noB, &p) || !make_plan_layout(sorb, &pl) || nbatch < 0 || nbatch > 0x7fffffffll || eps_sample < 0 ||
-      eps_sample > 65535 || cap_doubles < 0 || (dtype != PYNQS_F32 && dtype != PYNQS_F64)) {
-    set_error(PYNQS_EINVAL, "bad arguments");
-    return -1;
+// the kernels of this file by form (the two with the float32 row copy have launchers of their own: kernels_reduce_rowout.hip); the cases stand
+// in the order in which the kernels have always been instantiated, which keeps the device code the same file byte for byte
+template <int LEN, typename TT, bool SM>
+static auto onepass_kernel(const OnepassDecision &d) -> decltype(&reduce_onepass_kernel<LEN, TT, SM>) {
+  switch (d.form) {
+    case PYNQS_REDUCE_FLUSH: return d.gtile ? reduce_onepass_list_flush_kernel<LEN, TT, SM, SM> : reduce_onepass_list_flush_kernel<LEN, TT, SM, false>;
+    case PYNQS_REDUCE_LIST_REDRAW: return d.gtile ? reduce_onepass_list_redraw_kernel<LEN, TT, true> : reduce_onepass_list_redraw_kernel<LEN, TT, false>;
+    case PYNQS_REDUCE_LIST: return reduce_onepass_list_kernel<LEN, TT, false, false>;
+    case PYNQS_REDUCE_LIST_CACHE: return reduce_onepass_list_kernel<LEN, TT, SM, SM>;
+    default: return reduce_onepass_kernel<LEN, TT, SM>;
   }
-  if (eps_sample == 0) return 0;
-  uint32_t nchunks, chunk_len, max_tiles, fixed;
-  onepass_geometry(nbatch, p, true, &nchunks, &chunk_len, &max_tiles, &fixed);
-  const size_t esz = dtype == PYNQS_F64 ? 8 : 4;
-  const OnepassForm f = onepass_form(p, esz, max_tiles, fixed, (uint64_t)cap_doubles, eps_sample, false, chunk_len, without_table != 0, false, true);
-  if (f.use_split) return 1;
-  // the flushing form with draws: with io->tile_scratch its draw slots need twice the room (the list of the drawn tiles)
-  const OnepassForm g = with_tile_scratch ? onepass_form(p, esz, max_tiles, fixed, (uint64_t)cap_doubles, eps_sample, false, chunk_len, without_table != 0, true, true) : f;
-  return g.use_row32 ? 2 : 0;
-}
-
-extern "C" int64_t pynqs_reduce_onepass_row_f32_elements(int64_t nbatch, int sorb, int nele, int noA, int noB) {
-  SDParams p;
-  if (!make_sd_params(sorb, nele, noA, noB, &p) || nbatch < 0 || nbatch > 0x7fffffffll) {
-    set_error(PYNQS_EINVAL, "bad arguments");
-    return -1;
-  }
-  return (int64_t)((size_t)nbatch * draw_row_stride(p.nsd + 1));
 }
 
 extern "C" int pynqs_reduce_onepass(const uint64_t *bra, int64_t nbatch, int sorb, int nele, int noA, int noB, const void *plan, int dtype,
@@ -955,6 +939,12 @@ extern "C" int pynqs_reduce_onepass_form(const uint64_t *bra, int64_t nbatch, in
   if (io->lut_table && io->lut_nkeys < 0) return set_error(PYNQS_EINVAL, "bad lut_nkeys");
   hipStream_t st = (hipStream_t)stream;
   const int len = (sorb - 1) / 64 + 1;
+  // the form, from the buffers given; a caller that planned (io->form) is held to its plan before anything is enqueued
+  const OnepassGeometry g = onepass_geometry(nbatch, p, sampled);
+  const bool have_tiles = io->tile_scratch != nullptr && io->tile_scratch_bytes >= (int64_t)((size_t)nbatch * tile_scratch_stride(g.max_tiles));
+  const OnepassDecision d = onepass_decide(p, dtype == PYNQS_F64 ? 8 : 4, g, (uint64_t)io->cap_doubles, eps_sample,
+                                           OnepassOffer{io->row_cache != nullptr, io->dedup_table == nullptr, have_tiles, io->row_f32 != nullptr});
+  if (io->form != 0 && nbatch > 0 && io->form != d.form) return set_error(PYNQS_EINVAL, "plan and buffers disagree");
   // one clear kernel instead of two memsets (Fe2S2, 64 MB table: no slower than the runtime's fill of the table alone, and one launch
   // less); PYNQS_REDUCE_CLEAR_KERNEL=0 brings the memsets back
   static const bool clear_kernel = !(getenv("PYNQS_REDUCE_CLEAR_KERNEL") && atoi(getenv("PYNQS_REDUCE_CLEAR_KERNEL")) == 0);
@@ -970,42 +960,33 @@ extern "C" int pynqs_reduce_onepass_form(const uint64_t *bra, int64_t nbatch, in
   }
   if (nbatch == 0) return PYNQS_OK;
   if (!bra || !plan) return set_error(PYNQS_EINVAL, "null pointer");
-  uint32_t nchunks, chunk_len, max_tiles, fixed;
-  onepass_geometry(nbatch, p, sampled, &nchunks, &chunk_len, &max_tiles, &fixed);
-  const uint64_t grid = (uint64_t)nbatch * nchunks;
+  const uint64_t grid = (uint64_t)nbatch * g.nchunks;
   if (grid > 0x7fffffffull) return set_error(PYNQS_EINVAL, "grid too large");
-  if (grid * ((uint64_t)fixed + (uint64_t)io->cap_doubles) > 0x7fffffffull * 16ull) return set_error(PYNQS_EINVAL, "record arrays too large");
-  const size_t esz = dtype == PYNQS_F64 ? 8 : 4;
-  const bool have_tiles = io->tile_scratch != nullptr && io->tile_scratch_bytes >= (int64_t)((size_t)nbatch * tile_scratch_stride(max_tiles));
-  const OnepassForm form = onepass_form(p, esz, max_tiles, fixed, (uint64_t)io->cap_doubles, eps_sample, io->row_cache != nullptr, chunk_len,
-                                        io->dedup_table == nullptr, have_tiles, io->row_f32 != nullptr);
-  const uint32_t P = form.P;
-  const bool use_list = form.use_list || form.use_flush, use_cache = form.use_cache, use_flush = form.use_flush, use_gtile = form.use_gtile;
-  const bool use_split = form.use_split, use_row32 = form.use_row32;
-  const size_t lds = form.lds;
-  if (lds + onepass_static_lds(len) > 160 * 1024) return set_error(PYNQS_EINVAL, "row too long for the fused form (LDS): use the multi-pass entry points");
-  if (!io->dedup_table && !use_list)
+  if (grid * ((uint64_t)g.fixed + (uint64_t)io->cap_doubles) > 0x7fffffffull * 16ull) return set_error(PYNQS_EINVAL, "record arrays too large");
+  if (d.lds + onepass_static_lds(len) > 160 * 1024) return set_error(PYNQS_EINVAL, "row too long for the fused form (LDS): use the multi-pass entry points");
+  if (!io->dedup_table && d.form == PYNQS_REDUCE_LOOKBACK)
     return set_error(PYNQS_EINVAL, "no de-duplication table: only the LIST forms run without one (cap_doubles <= pynqs_reduce_onepass_list_capacity)");
   static const bool verbose = getenv("PYNQS_OP_VERBOSE") != nullptr;
   if (verbose)
-    fprintf(stderr, "pynqs_reduce_onepass: %s form%s, LDS %zu bytes per workgroup (walker tables %zu, max_tiles %u, list P %u), %u chunk(s) per walker\n",
-            use_split ? "LIST + float32 row copy + sorted draws" : use_row32 ? (use_gtile ? "flushing LIST + float32 row copy (tile sums in global memory)" : "flushing LIST + float32 row copy") : use_flush ? "flushing LIST" : use_list ? (use_gtile ? "LIST (tile sums in global memory)" : "LIST") : "look-back", use_cache ? " with row cache" : "", lds, (size_t)lds_fixed_bytes(p), max_tiles, P, nchunks);
+    fprintf(stderr, "pynqs_reduce_onepass: form %s%s, LDS %zu bytes per workgroup (walker tables %zu, max_tiles %u, list P %u), %u chunk(s) per walker\n",
+            pynqs_reduce_form_name(d.form), d.gtile ? " (tile sums in global memory)" : "", d.lds, (size_t)lds_fixed_bytes(p), g.max_tiles, d.P, g.nchunks);
   // eloc.py:257-264: with draws and eps <= 0 nothing is kept (every column can be drawn); without draws |H| >= eps as it stands
   const double eps_eff = (sampled && !(eps > 0.0)) ? __builtin_inf() : eps;
-  if (use_split) return launch_reduce_rowout(bra, nbatch, p, pl, chunk_len, max_tiles, plan, dtype, eps_eff, eps_sample, seed, P, lds, io, fixed, rowout_form, st);
-  if (use_row32) return launch_reduce_flush_row32(bra, nbatch, p, pl, chunk_len, max_tiles, plan, dtype, eps_eff, eps_sample, seed, P, lds, io, fixed, use_gtile, st);
+  switch (d.form) {
+    case PYNQS_REDUCE_ROWOUT:
+      return launch_reduce_rowout(bra, nbatch, p, pl, g.chunk_len, g.max_tiles, plan, dtype, eps_eff, eps_sample, seed, d.P, d.lds, io, g.fixed, rowout_form, st);
+    case PYNQS_REDUCE_FLUSH_ROW32:
+      return launch_reduce_flush_row32(bra, nbatch, p, pl, g.chunk_len, g.max_tiles, plan, dtype, eps_eff, eps_sample, seed, d.P, d.lds, io, g.fixed, d.gtile, st);
+    default: break;  // PYNQS_REDUCE_LOOKBACK, _LIST, _LIST_CACHE, _LIST_REDRAW, _FLUSH: the kernels of this file, onepass_kernel()
+  }
 #define PYNQS_OP_LAUNCH(TT, SM)                                                                                                      \
   do {                                                                                                                               \
-    auto kfn = use_flush ? (use_gtile ? reduce_onepass_list_flush_kernel<LEN, TT, SM, SM> : reduce_onepass_list_flush_kernel<LEN, TT, SM, false>) \
-             : use_list ? (use_cache ? reduce_onepass_list_kernel<LEN, TT, SM, SM>                                                   \
-                                     : (SM ? (use_gtile ? reduce_onepass_list_redraw_kernel<LEN, TT, true> : reduce_onepass_list_redraw_kernel<LEN, TT, false>) \
-                                           : reduce_onepass_list_kernel<LEN, TT, false, false>)) \
-                        : reduce_onepass_kernel<LEN, TT, SM>;                                                                        \
-    if (lds > 64 * 1024 && hipFuncSetAttribute(reinterpret_cast<const void *>(kfn), hipFuncAttributeMaxDynamicSharedMemorySize,      \
-                                               (int)lds) != hipSuccess)                                                              \
+    auto kfn = onepass_kernel<LEN, TT, SM>(d);                                                                                       \
+    if (d.lds > 64 * 1024 && hipFuncSetAttribute(reinterpret_cast<const void *>(kfn), hipFuncAttributeMaxDynamicSharedMemorySize,    \
+                                                 (int)d.lds) != hipSuccess)                                                          \
       return check_launch("hipFuncSetAttribute");                                                                                   \
-    hipLaunchKernelGGL(kfn, dim3((uint32_t)grid), dim3(kBlock), lds, st, bra, p, pl, nchunks, chunk_len, max_tiles, (const TT *)plan, \
-                       (TT)eps_eff, (uint32_t)eps_sample, seed, use_list ? P : winner_list_cap(eps_sample), make_out<TT>(io, len, fixed, use_gtile ? max_tiles : 0u));                \
+    hipLaunchKernelGGL(kfn, dim3((uint32_t)grid), dim3(kBlock), d.lds, st, bra, p, pl, g.nchunks, g.chunk_len, g.max_tiles, (const TT *)plan, \
+                       (TT)eps_eff, (uint32_t)eps_sample, seed, d.P, make_out<TT>(io, len, g.fixed, d.gtile ? g.max_tiles : 0u));    \
   } while (0)
   DISPATCH_LEN(len, {
     if (dtype == PYNQS_F64) { if (sampled) PYNQS_OP_LAUNCH(double, true); else PYNQS_OP_LAUNCH(double, false); }
@@ -1030,8 +1011,8 @@ extern "C" int pynqs_reduce_contract_form(int64_t nbatch, int sorb, int nele, in
   if (!io || !io->rec_col || !io->rec_w || !io->rec_link || !io->seg_count || !psi_unique || !eloc || !psi_x ||
       (eps_sample > 0 && (!io->srec_col || !io->srec_w || !io->srec_link)) || (io->lut_table && !psi_table))
     return set_error(PYNQS_EINVAL, "null pointer");
-  uint32_t nchunks, chunk_len, max_tiles, fixed;
-  onepass_geometry(nbatch, p, eps_sample > 0, &nchunks, &chunk_len, &max_tiles, &fixed);
+  const OnepassGeometry g = onepass_geometry(nbatch, p, eps_sample > 0);
+  const uint32_t nchunks = g.nchunks, fixed = g.fixed;
   const int len = (sorb - 1) / 64 + 1;
   hipStream_t st = (hipStream_t)stream;
   const uint32_t grid = (uint32_t)((nbatch + kBlock / 64 - 1) / (kBlock / 64));

@@ -95,8 +95,17 @@ def _side_stream(device):
 # 0.56 / 1.14, 8.4 / 43.6, 5.7 / 6.4, sampled 0.9 / 2.6 and 6.2 / 9.0); rows of 2.3e5 and 1.2e6 columns (sorb 80, 120): LIST form 5.3 / 6.4,
 # 10.6 / 10.4, sampled 13.0 / 14.6, 2.7 / 3.0 -- its other (look-back) form 22 / 6.1, 94 / 30, 96 / 38, sampled 68 / 14 and 54 / 16.
 FRONT_ROUTE = True
-FRONT_LONG_ROW = 65536   # (= kLongRow of kernels_reduce_onepass.hip)
 FRONT_SAMPLED_MIN_WALKERS = 512   # long rows with draws: the whole row is one workgroup's, fewer walkers than this leave CUs idle
+
+
+def __getattr__(name):
+    # FRONT_LONG_ROW is the library's own constant (the plan's long_row flag compares with it), read when first asked for.  It is not a module
+    # global: `import *` does not export it, and setting it changes nothing that _long_row_cap decides (that is the plan's flag)
+    if name == "FRONT_LONG_ROW":
+        return int(N.lib().pynqs_reduce_onepass_long_row())
+    raise AttributeError(name)
+
+
 _FRONT_DENSE: "set[tuple]" = set()   # long-row systems whose kept records outgrew the LDS list (this process)
 # De-duplication of the x' costs random probes into a table of 2-4 slots per distinct determinant: 64 MB for Fe2S2 (8192 walkers, 1.5 M distinct
 # of 10 M records: it stays in the 256 MB cache and saves 85 % of the amplitude evaluations), 1.6 GB at sorb 80 with 4096 walkers, where
@@ -566,7 +575,7 @@ def _dense_key(device, sorb, nele, noa, nob, eps_sample) -> tuple:
 
 def _long_row_cap(n, h1e, sorb, nele, noa, nob, eps_sample) -> Optional[int]:
     """None on rows the one-launch front end serves in either form; else the cap_doubles up to which it is used (-1: never)"""
-    if not FRONT_ROUTE or get_Num_SinglesDoubles(sorb, noa, nob) + 1 <= FRONT_LONG_ROW:
+    if not FRONT_ROUTE or not RF.plan(n, sorb, nele, noa, nob, int(eps_sample), h1e.dtype).long_row:
         return None
     return RF.list_capacity(n, sorb, nele, noa, nob, int(eps_sample), h1e.dtype)
 

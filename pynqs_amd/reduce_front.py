@@ -33,7 +33,7 @@ CONTRACT_FORM = int(os.environ.get("PYNQS_CONTRACT_FORM", str(N.CONTRACT_BATCHED
 # the tile loop ReduceFrontEnd.run takes in the short-row semi-stochastic kernel when its caller names none: pynqs_reduce_onepass_form's form
 # (0: tile sums by fixed-pattern cross-lane moves behind the next tile's gathers, one hand-off of the kept columns per tile; 1: the earlier loop; profiles/rowout_tiles_ab.txt)
 ROWOUT_FORM = int(os.environ.get("PYNQS_ROWOUT_FORM", str(N.ROWOUT_TILEWISE)), 0)
-TILE_SCRATCH_MIN_ROW = int(os.environ.get("PYNQS_TILE_SCRATCH_MIN_ROW", "65536"))  # columns per row from which the tile sums leave the LDS
+TILE_SCRATCH_MIN_ROW = int(os.environ.get("PYNQS_TILE_SCRATCH_MIN_ROW", "-1"))  # columns per row from which the tile sums leave the LDS (-1: the library's long-row length)
 
 
 def _pow2_at_least(v: int) -> int:
@@ -43,39 +43,45 @@ def _pow2_at_least(v: int) -> int:
     return c
 
 
+def plan(n: int, sorb: int, nele: int, noa: int, nob: int, eps_sample: int, h_dtype: torch.dtype = torch.float64, cap_doubles: int = 0,
+         dedup_slots: int = 0, dedup: bool = True, row_f32: Optional[bool] = None) -> N.ReducePlan:
+    """pynqs_reduce_onepass_plan under this module's switches and limits: the form a call takes, its launch parameters and the optional
+    buffers to allocate for it (include/pynqs_amd.h: pynqs_reduce_plan).  row_f32: overrides ROW_F32."""
+    req = N.ReducePlanRequest(n, sorb, nele, noa, nob, N.PYNQS_F64 if h_dtype == torch.float64 else N.PYNQS_F32, int(eps_sample), cap_doubles,
+                              int(dedup), dedup_slots, int(ROW_F32 if row_f32 is None else row_f32), ROW_F32_MAX_BYTES, int(ROW_CACHE),
+                              ROW_CACHE_MAX_BYTES, TILE_SCRATCH_MIN_ROW)
+    out = N.ReducePlan()
+    N.check(N.lib().pynqs_reduce_onepass_plan(C.byref(req), C.byref(out)), "pynqs_reduce_onepass_plan")
+    return out
+
+
+def form_name(form: int) -> str:
+    return N.lib().pynqs_reduce_form_name(int(form)).decode()
+
+
 def geometry(n: int, sorb: int, nele: int, noa: int, nob: int, eps_sample: int, dedup_slots: int = 0) -> Tuple[int, int, int, bool]:
     """(segments, fixed slots per segment, bytes of a de-duplication table of `dedup_slots` slots, fused form available)."""
-    out = (C.c_int64 * 4)(0, 0, dedup_slots, 0)
-    N.check(N.lib().pynqs_reduce_onepass_geometry(n, sorb, nele, noa, nob, int(eps_sample), out), "pynqs_reduce_onepass_geometry")
-    return int(out[0]), int(out[1]), int(out[2]), bool(out[3])
+    p = plan(n, sorb, nele, noa, nob, eps_sample, dedup_slots=dedup_slots)
+    return int(p.segments), int(p.fixed), int(p.table_bytes), bool(p.serves)
 
 
 def supported(n: int, sorb: int, nele: int, noa: int, nob: int, eps_sample: int) -> bool:
-    if sorb % 2 or not 0 <= eps_sample <= 65535:
-        return False
-    try:
+    try:  # (an odd sorb or more than 65535 draws: refused like any other bad argument)
         return geometry(n, sorb, nele, noa, nob, eps_sample)[3]
     except RuntimeError:
         return False
-
-
-def wants_row_cache(n: int, ncomb: int, eps_sample: int, nchunks: int, esz: int) -> bool:
-    """the semi-stochastic kernel's row cache: worth it when the draws are dense in the row (>= one draw per 64 columns) and the
-    [n, ncomb] scratch is affordable (<= ROW_CACHE_MAX_BYTES)"""
-    return bool(eps_sample > 0 and nchunks == 1 and ROW_CACHE and eps_sample * 64 >= ncomb and n * ncomb * esz <= ROW_CACHE_MAX_BYTES)
 
 
 def list_capacity(n: int, sorb: int, nele: int, noa: int, nob: int, eps_sample: int, h_dtype: torch.dtype = torch.float64,
                   without_table: bool = False) -> int:
     """Largest cap_doubles with which the kernel keeps a segment's records in an LDS list (its LIST form or the flushing form;
     pynqs_reduce_onepass_list_capacity), or -1.  without_table: for a front end built with dedup=False."""
-    ncomb = int(N.lib().pynqs_num_sd(sorb, noa, nob)) + 1
-    esz = 8 if h_dtype == torch.float64 else 4
-    nseg = geometry(n, sorb, nele, noa, nob, eps_sample)[0]
-    cache = wants_row_cache(n, ncomb, int(eps_sample), nseg // max(n, 1) if n else 1, esz)
+    # (the row cache as it is offered to a call that gets no float32 row copy)
+    cache = plan(n, sorb, nele, noa, nob, eps_sample, h_dtype, row_f32=False).row_cache_elements > 0
     out = C.c_int64(-1)
-    N.check(N.lib().pynqs_reduce_onepass_list_capacity(n, sorb, nele, noa, nob, N.PYNQS_F64 if esz == 8 else N.PYNQS_F32, int(eps_sample),
-                                                       int(cache), int(without_table), C.byref(out)), "pynqs_reduce_onepass_list_capacity")
+    N.check(N.lib().pynqs_reduce_onepass_list_capacity(n, sorb, nele, noa, nob, N.PYNQS_F64 if h_dtype == torch.float64 else N.PYNQS_F32,
+                                                       int(eps_sample), int(cache), int(without_table), C.byref(out)),
+            "pynqs_reduce_onepass_list_capacity")
     return int(out.value)
 
 
@@ -95,9 +101,11 @@ class ReduceFrontEnd:
         self.L = (sorb - 1) // 64 + 1
         self.cap_doubles, self.cap_unique = max(int(cap_doubles), 0), max(int(cap_unique), 1)
         self.dedup_slots = _pow2_at_least(2 * self.cap_unique)
-        self.nseg, self.fixed, table_bytes, ok = geometry(self.n, sorb, nele, noa, nob, self.eps_sample, self.dedup_slots)
-        if not ok:
+        self.plan = pl = plan(self.n, sorb, nele, noa, nob, self.eps_sample, h_dtype, self.cap_doubles, self.dedup_slots, bool(dedup))
+        if not pl.serves:
             raise RuntimeError("row too long for the fused REDUCE front end (LDS): use reduce_compact / reduce_compact_sampled")
+        self.form = form_name(pl.form)  # the kernel family run() launches: "lookback", "list", "list_cache", "list_redraw", "flush", "flush_row32", "rowout"
+        self.nseg, self.fixed, table_bytes = int(pl.segments), int(pl.fixed), int(pl.table_bytes)
         self.nchunks = self.nseg // max(self.n, 1) if self.n else 1
         self.stride = self.fixed + self.cap_doubles
         dev, L = self.device, self.L
@@ -130,31 +138,12 @@ class ReduceFrontEnd:
         self.uniq_parent = torch.zeros(self.cap_unique, dtype=torch.int32, device=dev)  # the walker each distinct row descends from
         self.counters = torch.zeros(4, dtype=torch.int32, device=dev)
         self.seed_dev = torch.zeros(1, dtype=torch.int64, device=dev)  # added to run()'s seed: bump it between the replays of a captured step
-        # row cache of the semi-stochastic kernel: the draws read the row back instead of enumerating the drawn tiles again
-        ncomb = int(N.lib().pynqs_num_sd(sorb, noa, nob)) + 1
-        esz = 8 if h_dtype == torch.float64 else 4
-        self.row_cache = None
-        # the two-kernel semi-stochastic form (round 4; rows of up to 32768 columns): the enumerating kernel leaves the row's sub-eps elements as
-        # float32 here, the draw kernel reads them once into registers; neither the float64 row cache nor the tile scratch is needed then
-        # (2: the flushing form -- rows of any length, kept columns beyond the LDS list -- whose draws read the drawn tiles back from the same
-        # float32 copy instead of enumerating them again; on long rows it still keeps its tile sums in the tile scratch)
-        self.row_f32, self.row_f32_form = None, 0
-        if self.eps_sample > 0 and ROW_F32:
-            self.row_f32_form = int(N.lib().pynqs_reduce_onepass_wants_row_f32(
-                self.n, sorb, nele, noa, nob, N.PYNQS_F64 if esz == 8 else N.PYNQS_F32, self.eps_sample, self.cap_doubles,
-                int(ncomb > TILE_SCRATCH_MIN_ROW), int(not self.dedup)))
-            if self.row_f32_form in (1, 2):
-                nel = int(N.lib().pynqs_reduce_onepass_row_f32_elements(self.n, sorb, nele, noa, nob))
-                if self.row_f32_form == 1 or 4 * nel <= ROW_F32_MAX_BYTES:
-                    self.row_f32 = torch.empty(max(nel, 1), dtype=torch.float32, device=dev)
-        if self.row_f32 is None and wants_row_cache(self.n, ncomb, self.eps_sample, self.nchunks, esz):
-            self.row_cache = torch.empty(max(self.n * ncomb, 1), dtype=h_dtype, device=dev)
-        # long rows with draws and no row cache: the tile sums / draw counts of the kernel in global memory instead of the LDS
-        self.tile_scratch = None
-        if self.eps_sample > 0 and self.row_cache is None and (self.row_f32 is None or self.row_f32_form == 2) and ncomb > TILE_SCRATCH_MIN_ROW:
-            nb = int(N.lib().pynqs_reduce_onepass_tile_scratch_bytes(self.n, sorb, nele, noa, nob, self.eps_sample))
-            if nb > 0:
-                self.tile_scratch = torch.empty(nb, dtype=torch.uint8, device=dev)
+        # the optional buffers of the semi-stochastic forms, as the plan offers them (include/pynqs_amd.h: pynqs_reduce_plan): the row's
+        # float32 copy (sorted draws on short rows; the flushing form's read-back of the drawn tiles), else the row cache of the integral
+        # dtype, and on long rows the tile sums / draw counts in global memory instead of the LDS
+        self.row_f32 = torch.empty(pl.row_f32_elements, dtype=torch.float32, device=dev) if pl.row_f32_elements else None
+        self.row_cache = torch.empty(pl.row_cache_elements, dtype=h_dtype, device=dev) if pl.row_cache_elements else None
+        self.tile_scratch = torch.empty(pl.tile_scratch_bytes, dtype=torch.uint8, device=dev) if pl.tile_scratch_bytes else None
         self._lut = None
         self._io = self._make_io()
 
@@ -180,7 +169,13 @@ class ReduceFrontEnd:
         io.tile_scratch = self.tile_scratch.data_ptr() if self.tile_scratch is not None else None
         io.tile_scratch_bytes = self.tile_scratch.numel() if self.tile_scratch is not None else 0
         io.row_f32 = self.row_f32.data_ptr() if self.row_f32 is not None else None
+        io.form = int(self.plan.form)  # (the launch checks that it arrives at the plan's form from these buffers)
         return io
+
+    @property
+    def row_f32_form(self) -> int:
+        """what the plan wanted the float32 row copy for: 1 sorted draws, 2 the flushing form, 0 not wanted"""
+        return int(self.plan.row_f32_form)
 
     def record_stream(self, stream) -> None:
         """The buffers are (also) used on `stream`: when this front end was allocated under another stream's context (total_energy's

@@ -307,7 +307,9 @@ R_SEEDS = 8
 class Hier:
     """how: "multi" = energy.reduce_compact_sampled; "energy" = energy.reduce_front (the library picks the buffers); else a ReduceFrontEnd
     built with cap_doubles / dedup under the module switches row_f32 / row_cache / tile_min_row of pynqs_amd.reduce_front.
-    expect: (row_f32_form, row_cache present, tile_scratch present) as the library must answer."""
+    expect: (row_f32_form, row_cache present, tile_scratch present) as the library must answer; form / tile_sums_global: the kernel family
+    the plan names (ReduceFrontEnd.form) and whether its tile sums live in global memory -- shape by shape what the parent of the plan's
+    introduction printed for these launches (profiles/reduce_plan_parent_forms.txt)."""
     name: str
     sorb: int
     noA: int
@@ -322,6 +324,8 @@ class Hier:
     row_cache: bool = True
     tile_min_row: int = 65536
     expect: tuple = (0, False, False)
+    form: str = ""
+    tile_sums_global: bool = False
 
 
 HIER = [
@@ -334,12 +338,12 @@ HIER = [
     # the forms of the one-launch front end, asked of the library by its switches at the smallest row with several tiles (sorb 24, 4 + 4
     # electrons: 1425 columns in 6 tiles).  The shapes of tests/test_gpu_reduce_route.py (30724 columns and more) are of no use to this
     # statistic: with R N <= 24000 draws no column of theirs reaches an expectation of 5, every column falls into the pooled cell, dof = 0.
-    Hier("flush_row_f32", 24, 4, 4, 8, 0.45, 3000, cap_doubles=1100, dedup=False, expect=(2, False, False)),
-    Hier("flush_reenumerate", 24, 4, 4, 8, 0.45, 4000, cap_doubles=1100, dedup=False, expect=(0, True, False)),
-    Hier("lookback", 24, 4, 4, 8, 0.45, 4000, cap_doubles=1100, expect=(0, True, False)),
-    Hier("list_row_cache", 24, 4, 4, 8, 0.45, 4000, cap_doubles=600, row_f32=False, expect=(0, True, False)),
-    Hier("list_reenumerate", 24, 4, 4, 8, 0.45, 4000, cap_doubles=600, row_f32=False, row_cache=False, expect=(0, False, False)),
-    Hier("list_tile_sums_global", 24, 4, 4, 8, 0.45, 4000, cap_doubles=600, row_f32=False, row_cache=False, tile_min_row=64, expect=(0, False, True)),
+    Hier("flush_row_f32", 24, 4, 4, 8, 0.45, 3000, cap_doubles=1100, dedup=False, expect=(2, False, False), form="flush_row32"),
+    Hier("flush_reenumerate", 24, 4, 4, 8, 0.45, 4000, cap_doubles=1100, dedup=False, expect=(0, True, False), form="flush"),
+    Hier("lookback", 24, 4, 4, 8, 0.45, 4000, cap_doubles=1100, expect=(0, True, False), form="lookback"),
+    Hier("list_row_cache", 24, 4, 4, 8, 0.45, 4000, cap_doubles=600, row_f32=False, expect=(0, True, False), form="list_cache"),
+    Hier("list_reenumerate", 24, 4, 4, 8, 0.45, 4000, cap_doubles=600, row_f32=False, row_cache=False, expect=(0, False, False), form="list_redraw"),
+    Hier("list_tile_sums_global", 24, 4, 4, 8, 0.45, 4000, cap_doubles=600, row_f32=False, row_cache=False, tile_min_row=64, expect=(0, False, True), form="list_redraw", tile_sums_global=True),
 ]
 HIER_BY_NAME = {h.name: h for h in HIER}
 

@@ -29,7 +29,7 @@ def _compare(case, fe, ref, lut=None):
     """all records of the front end's last run against the replay `ref`; returns the worst (weight error / bound, row_sum error / bound)"""
     n, ncomb = ref.hm.shape
     nu, flags, mx = fe.counters_host()
-    assert fe.row_f32_form == 1 and fe.row_f32 is not None
+    assert fe.row_f32_form == 1 and fe.row_f32 is not None and fe.form == "rowout"
     assert flags == 0 and not fe.overflowed((nu, flags, mx))
     walker, col, w, link, onv, drawn = fe.records()
     rows_own = fe.rows_of(link[link >= 0]).cpu().numpy()
@@ -197,6 +197,7 @@ def test_hierarchical_forms_follow_the_law(shape, monkeypatch):
         fe = RF.ReduceFrontEnd(n, shape.sorb, nele, shape.noA, shape.noB, shape.N, torch.float64, x.device, shape.cap_doubles,
                                n * (kept_max + shape.N) + 64, want_pm1=False, dedup=shape.dedup)
         assert (fe.row_f32_form, fe.row_cache is not None, fe.tile_scratch is not None) == shape.expect
+        assert (fe.form, bool(fe.plan.tile_sums_global)) == (shape.form, shape.tile_sums_global)
         assert (shape.cap_doubles > RF.list_capacity(n, shape.sorb, nele, shape.noA, shape.noB, shape.N)) == (shape.cap_doubles > 1000)
         plan = cx.plan_for(h1g, h2g, shape.sorb, x.device).buf
     for r in range(1, RR.R_SEEDS + 1):

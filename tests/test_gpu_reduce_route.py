@@ -197,6 +197,8 @@ def test_semi_stochastic_flushing_form(sorb, no, n, eps, ns):
     assert fe.cap_doubles + fe.fixed > 2048 and (fe.tile_scratch is not None) == long_row
     # (end of round 4: the draws read the drawn tiles back from the row's float32 copy instead of enumerating them again)
     assert (fe.row_f32 is not None) == (fe.row_f32_form == 2) and fe.row_cache is None and (fe.row_f32_form == 2) == (ns <= 1000)
+    # (the plain flushing form's flag rests on the plan alone: the parent's verbose line did not print it for that form)
+    assert fe.form == ("flush_row32" if ns <= 1000 else "flush") and bool(fe.plan.tile_sums_global) == long_row
     assert fe.cap_doubles <= RF.list_capacity(n, sorb, 2 * no, no, no, ns)
     w, col, h, link, onv, drawn = fe.records()
     row, col2, onv2, h2_, counts = E.reduce_compact(x, h1, h2, sorb, 2 * no, no, no, eps, sort=True)
@@ -237,6 +239,7 @@ def test_tile_sums_in_global_memory_draw_the_same_records(monkeypatch):
             monkeypatch.setattr(RF, "TILE_SCRATCH_MIN_ROW", min_row)
             fe = RF.ReduceFrontEnd(n, sorb, 2 * no, no, no, ns, torch.float64, x.device, 600, 3000 * n, want_pm1=False)
             assert (fe.tile_scratch is not None) == (min_row == 65536)
+            assert fe.form == "flush_row32" and bool(fe.plan.tile_sums_global) == (min_row == 65536)
             fe.run(x, plan, eps, seed=11)
             nu, flags, _ = fe.counters_host()
             assert flags == 0

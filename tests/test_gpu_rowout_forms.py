@@ -31,7 +31,7 @@ def _run(case, form, eps, cap_doubles, cap_unique, seed):
     x = _dev(xh)
     fe = RF.ReduceFrontEnd(case.n, case.sorb, case.noA + case.noB, case.noA, case.noB, case.N, torch.float64, x.device, cap_doubles, cap_unique,
                            want_pm1=False, dedup=case.dedup)
-    assert fe.row_f32_form == 1 and fe.row_f32 is not None, "not the short-row semi-stochastic kernel"
+    assert fe.row_f32_form == 1 and fe.row_f32 is not None and fe.form == "rowout", "not the short-row semi-stochastic kernel"
     fe.row_f32.fill_(float("nan"))  # (whatever the kernel does not write shows)
     plan = cx.plan_for(_dev(h1), _dev(h2), case.sorb, x.device).buf
     fe.run(x, plan, eps, seed, None, form=form)

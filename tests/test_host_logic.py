@@ -1,6 +1,7 @@
 """CPU-only checks: the C ABI library loads and exports every symbol include/pynqs_amd.h declares, host-side
 entry points (no GPU needed) behave like the reference, and the product refuses to compute without a GPU."""
 import ctypes
+import functools
 import os
 import re
 
@@ -387,7 +388,7 @@ def test_reduce_front_list_capacity_is_host_arithmetic():
     """pynqs_reduce_onepass_list_capacity: the kept doubles per segment up to which the one-launch front end runs in one of its LIST forms.
     Short rows: 1024 slots minus the fixed ones; without draws the flushing form extends that to a tenth of a segment's columns, and to any
     capacity without a de-duplication table.  Rows of more than 65536 columns: any capacity (flushing form; with draws it keeps its tile sums
-    in io->tile_scratch, which also makes sorb 184 with whole rows possible: pynqs_reduce_onepass_geometry's out[3])."""
+    in io->tile_scratch, which also makes sorb 184 with whole rows possible: pynqs_reduce_plan.serves)."""
     from pynqs_amd import reduce_front as RF
 
     any_cap = (1 << 30) - 1
@@ -401,8 +402,89 @@ def test_reduce_front_list_capacity_is_host_arithmetic():
     for args in ((2048, 80, 40, 20, 20, 0), (4096, 120, 60, 30, 30, 0), (256, 120, 60, 30, 30, 0), (4096, 184, 92, 46, 46, 0),
                  (2048, 80, 40, 20, 20, 1000), (4096, 120, 60, 30, 30, 1000), (4096, 184, 92, 46, 46, 1000)):
         assert RF.list_capacity(*args) == any_cap and RF.supported(*args)
-    assert int(N_lib().pynqs_reduce_onepass_tile_scratch_bytes(10, 120, 60, 30, 30, 0)) == 0
-    assert int(N_lib().pynqs_reduce_onepass_tile_scratch_bytes(10, 120, 60, 30, 30, 1000)) % 160 == 0 > -1
+    assert int(RF.plan(10, 120, 60, 30, 30, 0).tile_scratch_bytes) == 0
+    assert int(RF.plan(10, 120, 60, 30, 30, 1000).tile_scratch_bytes) % 160 == 0 > -1 and RF.plan(10, 120, 60, 30, 30, 1000).tile_scratch_bytes > 0
+
+
+@functools.lru_cache(maxsize=None)
+def _reduce_front_record():
+    """the recorder of tests/golden/reduce_front_*.npz and what the library answers over its grid now: computed once, shared, not modified"""
+    import importlib.util
+
+    from pynqs_amd import reduce_front as RF
+
+    spec = importlib.util.spec_from_file_location("make_golden_reduce_front", os.path.join(ROOT, "tests", "golden", "make_golden_reduce_front.py"))
+    rec = importlib.util.module_from_spec(spec)
+    spec.loader.exec_module(rec)
+    assert not any(k.startswith(rec.OVERRIDES) for k in os.environ), f"unset the overrides {rec.OVERRIDES}"
+    g = rec.grid(RF)
+    names, plans = rec.record_plans(RF, g)
+    load = lambda f: dict(np.load(os.path.join(ROOT, "tests", "golden", f)))  # noqa: E731
+    return rec, g, names, plans, load("reduce_front_parent.npz"), load("reduce_front_plans.npz")
+
+
+def test_reduce_front_plans_are_unchanged():
+    """pynqs_reduce_onepass_plan over the recorder's grid against the plans recorded from the first build that had the entry point, where it
+    only wrapped the unmoved decision (tests/golden/reduce_front_plans.npz): every field of every point equal, no tolerance."""
+    rec, g, names, plans, _, B = _reduce_front_record()
+    assert list(B["in_cols"]) == list(rec.IN_COLS) and np.array_equal(B["inputs"], g)
+    assert list(B["cols"]) == names and B["values"].shape == plans.shape
+    diff = np.argwhere(B["values"] != plans)
+    assert not len(diff), [(g[i].tolist(), names[j], int(B["values"][i, j]), int(plans[i, j])) for i, j in diff[:10]]
+
+
+def test_reduce_front_answers_what_the_parent_answered():
+    """ReduceFrontEnd (built on device "meta"), list_capacity and supported over the same grid against what the parent of the plan's
+    introduction answered through its five queries and its allocation in Python (tests/golden/reduce_front_parent.npz): the float32 form,
+    the elements of every optional buffer, segments, fixed slots, chunks, table, capacities -- and the refusals."""
+    from pynqs_amd import reduce_front as RF
+
+    rec, g, _, _, A, _ = _reduce_front_record()
+    assert list(A["in_cols"]) == list(rec.IN_COLS) and np.array_equal(A["inputs"], g) and list(A["cols"]) == list(rec.A_COLS)
+    got = rec.record_parent(RF, g)
+    diff = np.argwhere(A["values"] != got)
+    assert got.shape == A["values"].shape and not len(diff), [(g[i].tolist(), rec.A_COLS[j], int(A["values"][i, j]), int(got[i, j])) for i, j in diff[:10]]
+
+
+def test_reduce_front_records_agree_and_cover_every_form():
+    """What ties the recorded plans (B) to the parent's answers (A), which know no form names: the two forms with the float32 row copy are
+    where the parent asked for that copy and allocated it; a list form is planned exactly up to the parent's list_capacity wherever the
+    plan offers the buffers that query assumes (no float32 copy; with draws the row cache or else the tile scratch).  And the record is
+    not trivial: all seven forms, the tile-sums flag in both states and refusals occur."""
+    from pynqs_amd import reduce_front as RF
+
+    rec, g, names, _, A, B = _reduce_front_record()
+    a = {c: A["values"][:, j] for j, c in enumerate(rec.A_COLS)}
+    b = {c: B["values"][:, j] for j, c in enumerate(names)}
+    i = {c: g[:, j] for j, c in enumerate(rec.IN_COLS)}
+    code = {RF.form_name(f): f for f in range(1, 8)}
+    assert sorted(code) == sorted(["lookback", "list", "list_cache", "list_redraw", "flush", "flush_row32", "rowout"]) and RF.form_name(0) == RF.form_name(8) == "?"
+    ok = a["refused"] == 0
+    assert np.array_equal(ok, b["serves"] == 1) and 0 < int((~ok).sum()) < len(ok) // 10
+    assert np.array_equal((b["form"] == code["rowout"])[ok], ((a["row_f32_form"] == 1) & (a["row_f32"] >= 0))[ok])
+    assert np.array_equal((b["form"] == code["flush_row32"])[ok], ((a["row_f32_form"] == 2) & (a["row_f32"] >= 0))[ok])
+    same_offer = ok & (b["row_f32_elements"] == 0) & ((i["eps_sample"] == 0) | (b["row_cache_elements"] > 0) | (b["tile_scratch_bytes"] > 0))
+    cap = np.where(i["table"] == 1, a["list_capacity"], a["list_capacity_tableless"])
+    assert int(same_offer.sum()) > len(ok) // 2
+    assert np.array_equal((b["form"] != code["lookback"])[same_offer], (i["cap_doubles"] <= cap)[same_offer])
+    for f in code.values():
+        assert int(((b["form"] == f) & ok).sum()) >= 100, RF.form_name(f)
+    flag = b["tile_sums_global"][ok]
+    assert set(np.unique(flag)) == {0, 1} and set(np.unique(b["form"][ok][flag == 1])) == {code["list_redraw"], code["flush"], code["flush_row32"]}
+
+
+def test_reduce_front_plan_for_no_walkers_returns():
+    """Zero walkers: the plan, list_capacity and supported answer with the chunks of one walker (the split of a row into chunks divides by the
+    walker count; the launch, which decides before it clears, goes the same way: tests/test_gpu_reduce_plan.py)."""
+    from pynqs_amd import reduce_front as RF
+
+    for ns in (0, 100):
+        p, one = RF.plan(0, 12, 5, 3, 2, ns, cap_doubles=64), RF.plan(1, 12, 5, 3, 2, ns, cap_doubles=64)
+        assert p.segments == 0 and p.tile_scratch_bytes == 0 and p.serves == 1
+        assert (p.form, p.nchunks, p.chunk_len, p.max_tiles, p.fixed, p.list_slots, p.lds_bytes) == (one.form, one.nchunks, one.chunk_len, one.max_tiles, one.fixed, one.list_slots, one.lds_bytes)
+        assert RF.supported(0, 12, 5, 3, 2, ns) and RF.list_capacity(0, 12, 5, 3, 2, ns) == RF.list_capacity(1, 12, 5, 3, 2, ns)
+        fe = RF.ReduceFrontEnd(0, 12, 5, 3, 2, ns, torch.float64, "meta", 64, 128)
+        assert (fe.nseg, fe.nchunks, fe.fixed) == (0, 1, one.fixed)
 
 
 def N_lib():

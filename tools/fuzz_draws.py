@@ -68,10 +68,10 @@ while time.time() - t0 < budget:
     fe.run(x, plan, eps, seed, None)
     nu, flags, _ = fe.counters_host()
     assert flags == 0, (sorb, noA, noB, n, eps, ns, flags)
-    forms += fe.row_f32_form == 1
+    forms += fe.form == "rowout"
     walker, col, w, link, onv, drawn = fe.records()
     wk, cl, ww, dr, ov = walker.cpu(), col.cpu().long(), w.cpu(), drawn.cpu(), onv.cpu()
-    tag = f"sorb {sorb} {noA}a{noB}b n {n} eps {eps} N {ns} f32 {f32} dedup {dedup} seed {seed}"
+    tag = f"sorb {sorb} {noA}a{noB}b n {n} eps {eps} N {ns} f32 {f32} dedup {dedup} seed {seed} form {fe.form}"
     got = torch.zeros_like(keep)
     got[wk[~dr], cl[~dr]] = True
     assert torch.equal(got, keep), "kept set: " + tag
@@ -93,8 +93,8 @@ while time.time() - t0 < budget:
     assert not bool(keep[dw, dc].any()) and bool((ho[dw, dc] != 0).all()), "drawn columns: " + tag
     flat = dw * ho.shape[1] + dc
     # (ascending columns: the round-4 kernel's order; the other forms -- taken when the kept records outgrow 1024 slots: the flushing form with
-    # or without the row's float32 copy, row_f32_form 2 / 0 -- emit tile by tile)
-    if not (flat.unique().numel() == flat.numel() and (fe.row_f32_form != 1 or bool((flat[1:] > flat[:-1]).all()))):
+    # or without the row's float32 copy -- emit tile by tile)
+    if not (flat.unique().numel() == flat.numel() and (fe.form != "rowout" or bool((flat[1:] > flat[:-1]).all()))):
         badi = int((flat[1:] <= flat[:-1]).nonzero()[0])
         print("drawn order:", tag, "ncomb", ho.shape[1], "unique", flat.unique().numel(), "of", flat.numel(), "at", badi, "walkers", dw[badi - 2: badi + 4].tolist(),
               "cols", dc[badi - 2: badi + 4].tolist(), "w", dh[badi - 2: badi + 4].tolist())

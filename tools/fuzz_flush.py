@@ -10,7 +10,7 @@ from pynqs_amd import C_extension as cx, energy as E, reduce_front as RF
 budget = float(sys.argv[1]) if len(sys.argv) > 1 else 60.0
 rng = np.random.default_rng(int(sys.argv[2]) if len(sys.argv) > 2 else 1)
 dev = torch.device("cuda")
-t0, cases, flushed, sampled_cases = time.time(), 0, 0, 0
+t0, cases, flushed, sampled_cases, forms = time.time(), 0, 0, 0, {}
 while time.time() - t0 < budget:
     sorb = int(rng.choice([4, 6, 8, 12, 16, 20, 24, 30, 36, 40, 56, 66, 70, 80, 130]))
     K = sorb // 2
@@ -37,12 +37,12 @@ while time.time() - t0 < budget:
     fe = RF.ReduceFrontEnd(n, sorb, noA + noB, noA, noB, ns, dt, dev, cap_d, int(counts.sum()) + n * ns + 64, want_pm1=False, dedup=dedup)
     fe.run(x, cx.plan_for(h1, h2, sorb, dev).buf, eps, seed=int(rng.integers(1 << 40)))
     nu, flags, _ = fe.counters_host()
-    assert flags == 0, (sorb, noA, noB, n, eps, ns, flags)
+    assert flags == 0, (sorb, noA, noB, n, eps, ns, flags, fe.form)
     w, col, h, link, onv, drawn = fe.records()
     kw, kc, kh, ko = w[~drawn], col[~drawn], h[~drawn], onv[~drawn]
     k1 = torch.argsort((kw << 32) | kc.long(), stable=True)
     ok = kw.numel() == row.numel() and torch.equal(kw[k1], row) and torch.equal(kc[k1], col2) and torch.equal(kh[k1], hh) and torch.equal(ko[k1], onv2)
-    assert ok, ("kept records differ", sorb, noA, noB, n, eps, ns, str(dt), dedup)
+    assert ok, ("kept records differ", sorb, noA, noB, n, eps, ns, str(dt), dedup, fe.form)
     rows = fe.rows_of(link)
     assert torch.equal(fe.uniq_onv[rows], onv), ("rows", sorb, noA, noB, n, eps, ns)
     if not dedup:
@@ -57,6 +57,7 @@ while time.time() - t0 < budget:
         has = S > 0
         assert bool((tot[has] == ns).all()) and bool((tot[~has] == 0).all()), ("draw counts", sorb, noA, noB, n, eps, ns)
     flushed += int(cap_d + fe.fixed > 2048)
+    forms[fe.form] = forms.get(fe.form, 0) + 1
     cases += 1
     del fe
-print(f"fuzz ok: {cases} systems in {time.time() - t0:.0f} s ({flushed} with more than one flush per segment, {sampled_cases} with draws)")
+print(f"fuzz ok: {cases} systems in {time.time() - t0:.0f} s ({flushed} with more than one flush per segment, {sampled_cases} with draws; forms {forms})")

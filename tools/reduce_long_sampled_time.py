@@ -32,5 +32,5 @@ for i in range(5):
     fe.run(x, plan.buf, eps, 100 + i, None)
 b.record(); b.synchronize()
 print(f"sorb {sorb} x {nw} walkers, eps {eps}, {ns} draws (ROW32={os.environ.get('PYNQS_OP_ROW32', '1')}): local_energy {el * 1e3:.3f} ms, front end alone {a.elapsed_time(b) / 5:.3f} ms; "
-      f"row_f32 {'yes' if fe.row_f32 is not None else 'no'} (form {fe.row_f32_form}), tile scratch {'yes' if fe.tile_scratch is not None else 'no'}, table {'yes' if fe.dedup else 'no'}, "
+      f"form {fe.form}{' (tile sums in global memory)' if fe.plan.tile_sums_global else ''}, table {'yes' if fe.dedup else 'no'}, "
       f"finite {int(torch.isfinite(e).sum())}, mean {float(e[torch.isfinite(e)].mean()):.6f}")

@@ -1,6 +1,7 @@
 """LDS-row form of the semi-stochastic REDUCE front end (round 4) on 8192 Fe2S2 walkers: structure of its records against the CPU oracle's
 rows on the first walkers (kept records exact, drawn records sub-eps with whole hit counts adding up to N, weights (c / N) sign(H) S),
-the law of the draws (z-scores of the per-column hit counts over many seeds), and its time.  PYNQS_OP_ROWLDS=0 runs the row-cache form."""
+the law of the draws (z-scores of the per-column hit counts over many seeds), and its time.  PYNQS_ROW_F32=0 (pynqs_amd.reduce_front.ROW_F32)
+runs the row-cache form instead; the form taken is printed."""
 import os, sys
 import numpy as np, torch
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
@@ -16,7 +17,7 @@ x = torch.from_numpy(xh).to(dev)
 h1, h2 = torch.from_numpy(d["h1e"]).to(dev), torch.from_numpy(d["h2e"]).to(dev)
 plan = cx.plan_for(h1, h2, 40, dev).buf
 fe = RF.ReduceFrontEnd(n, 40, 30, 15, 15, N, torch.float64, dev, 246, 1900000, want_pm1=False)
-print("row_f32", fe.row_f32 is not None, "row_cache", fe.row_cache is not None)
+print("form", fe.form)
 fe.run(x, plan, eps, 3, None)
 torch.cuda.synchronize()
 print("counters", fe.counters.tolist())

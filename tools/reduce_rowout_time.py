@@ -1,4 +1,4 @@
-"""time of the semi-stochastic front end on 8192 Fe2S2 walkers (PYNQS_OP_DEBUG / PYNQS_OP_ROWLDS ablations)"""
+"""time of the semi-stochastic front end on 8192 Fe2S2 walkers (PYNQS_OP_DEBUG ablations; PYNQS_ROW_F32=0 times the row-cache form)"""
 import os, sys
 import numpy as np, torch
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
