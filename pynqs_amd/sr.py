@@ -162,7 +162,7 @@ class _FusedSR:
             used = int(st[_ITER])
         self.iterations = int(st[_ITER])
         self.converged = bool(st[_CONVERGED])
-        self.residual = (st[_TRUE2] / st[_RHS2]) ** 0.5 if st[_RHS2] > 0 else 0.0
+        self.residual = 0.0 if st[_RHS2] == 0 else (st[_TRUE2] / st[_RHS2]) ** 0.5  # (not a number when rhs holds one: not 0)
         if not self.converged:
             warnings.warn(f"{self._who}: conjugate gradients stopped after {self.iterations} iterations at a relative residual of "
                           f"{self.residual:.3e} (tol {self.tol:.1e}, max_iter {self.max_iter}); the last iterate is used", RuntimeWarning, stacklevel=2)

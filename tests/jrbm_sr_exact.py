@@ -118,6 +118,10 @@ def gradient_bound(se: JSrExact, M: np.ndarray, prob, eloc, e_total) -> np.ndarr
 # 32-hidden-unit pass and the LDS limit for Z (sorb 120 stages it, sorb 184 reads it from global memory)
 CASES = [(12, 3, 5, 64), (40, 15, 80, 1000), (40, 15, 37, 31), (40, 15, 80, 1), (66, 10, 7, 33), (72, 6, 9, 65), (120, 30, 70, 300),
          (184, 46, 33, 130)]
+# (sorb, electrons per spin, H, n) for the product tests alone: sorb 13, the row of the paired-rows triangle that pairs with itself (odd
+# sorb); sorb 128, the largest Z staged in LDS (66 048 bytes); sorb 129, the first read from global memory, odd and three words; n = 2049,
+# 65 workgroups: the reduce kernel's second trip with its (i, j) and (j, i) writes.  H = 33: one unit in a second pass.
+PRODUCT_SHAPES = [(13, 3, 5, 64), (128, 30, 33, 64), (129, 30, 33, 65), (12, 3, 5, 2049)]
 # the real saturated regimes of rbm_sr_exact.SATURATED: (sorb, H, n, regime)
 SATURATED = [c[1:] for c in SE.SATURATED if c[0] == "real"]
 
@@ -125,6 +129,8 @@ SATURATED = [c[1:] for c in SE.SATURATED if c[0] == "real"]
 def case_inputs(sorb: int, no: int, H: int, n: int):
     """(rbm, M, words, prob, eloc, e_total): rbm_sr_exact.case_inputs("real", ...) and M from jrbm_exact.jastrow_params("j-asym")"""
     rbm, words, prob, eloc, e_total = SE.case_inputs("real", sorb, no, H, n)
+    if sorb % 2:  # bench.synth_walkers fills sorb // 2 orbitals per spin: the last orbital of an odd sorb would be empty in every walker
+        words = R.rand_words(n, sorb, 17)
     return rbm, J.jastrow_params("j-asym", sorb), words, prob, eloc, e_total
 
 

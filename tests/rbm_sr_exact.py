@@ -217,6 +217,13 @@ def flat_of(tensors) -> np.ndarray:
 CASES = [("complex", 40, 15, 40, 1000), ("complex", 40, 15, 37, 777), ("complex", 12, 3, 5, 64), ("complex", 120, 30, 70, 300),
          ("complex", 184, 46, 33, 130), ("real", 40, 15, 80, 1000), ("real", 72, 6, 9, 65),
          ("real", 40, 15, 80, 1), ("complex", 40, 15, 37, 31), ("real", 66, 10, 7, 33)]
+# (kind, sorb, electrons per spin, H, n) for the product tests alone (the longdouble dense solve of the solve tests would be too slow at these
+# P): where the kernels' control flow depends on the sizes.  rbm_sr_reduce_kernel gives each of its 4 waves a slice of the ceil(n / 32)
+# workgroups' partial sums and loads 16 of them per trip: n = 2049 is 65 workgroups, 17 per slice, a second trip of one; n = 4100 is 129
+# workgroups, 33 per slice, three trips, and a last workgroup of 4 walkers.  The product kernel passes over 32 hidden units at a time:
+# H = 32 and 64 are whole passes, H = 129 leaves one unit to a fifth (P = 5329 real, 2 x 5329 complex).
+PRODUCT_SHAPES = [(kind, 12, 3, 5, n) for n in (2049, 4100) for kind in ("real", "complex")] + \
+                 [(kind, 40, 15, H, 64) for H in (32, 64, 129) for kind in ("real", "complex")]
 # (kind, sorb, H, n, regime of rbm_exact.regime_params): hidden units at theta = -50 ... -362
 SATURATED = [("real", 40, 80, 257, "chunk-50"), ("complex", 40, 40, 255, "two-200"), ("real", 40, 40, 100, "one-338-w"),
              ("complex", 130, 9, 65, "one-338")]

@@ -22,6 +22,7 @@ pytestmark = pytest.mark.gpu
 
 U = R.U
 ALL_CASES = [("case",) + c for c in JS.CASES] + [("saturated",) + c for c in JS.SATURATED]
+PRODUCT_CASES = ALL_CASES + [("case",) + c for c in JS.PRODUCT_SHAPES]  # (the size branches of the kernels: the product tests alone)
 _ids = lambda c: "-".join(map(str, c[1:]))  # noqa: E731
 
 
@@ -68,7 +69,7 @@ def _flat(tensors):
     return np.concatenate([t.detach().cpu().numpy().reshape(-1) for t in tensors])
 
 
-@pytest.mark.parametrize("case", ALL_CASES, ids=_ids)
+@pytest.mark.parametrize("case", PRODUCT_CASES, ids=_ids)
 def test_prepare_and_product_meet_the_rounding_bound(case):
     from pynqs_amd.rbm import RealRBM
     from pynqs_amd.sr import FusedJastrowRbmSR, FusedRbmSR

@@ -23,6 +23,7 @@ pytestmark = pytest.mark.gpu
 
 U = R.U
 ALL_CASES = [("case",) + c for c in SE.CASES] + [("saturated",) + c for c in SE.SATURATED]
+PRODUCT_CASES = ALL_CASES + [("case",) + c for c in SE.PRODUCT_SHAPES]  # (the size branches of the kernels: the product tests alone)
 
 
 def _dev(a):
@@ -67,7 +68,7 @@ def _flat(tensors):
     return np.concatenate([t.detach().cpu().numpy().reshape(-1) for t in tensors])
 
 
-@pytest.mark.parametrize("case", ALL_CASES, ids=lambda c: "-".join(map(str, c[1:])))
+@pytest.mark.parametrize("case", PRODUCT_CASES, ids=lambda c: "-".join(map(str, c[1:])))
 def test_prepare_and_product_meet_the_rounding_bound(case):
     from pynqs_amd.sr import FusedRbmSR
 

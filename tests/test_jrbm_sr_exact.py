@@ -88,7 +88,7 @@ def _check_bound(se, what):
         assert bool((err <= b).all()), (what, name, float((err / b).max()))
 
 
-@pytest.mark.parametrize("sorb,no,H,n", JS.CASES)
+@pytest.mark.parametrize("sorb,no,H,n", JS.CASES + JS.PRODUCT_SHAPES)
 def test_bound_is_tight_enough_to_mean_something(sorb, no, H, n):
     se, *_ = _case(sorb, no, H, n)
     _check_bound(se, f"{sorb}x{H} n {n}")

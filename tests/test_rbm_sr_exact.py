@@ -50,7 +50,7 @@ def _float64_product(se, v):
     return np.asarray(se.to_flat(y), dtype=np.float64)
 
 
-@pytest.mark.parametrize("kind,sorb,no,H,n", SE.CASES)
+@pytest.mark.parametrize("kind,sorb,no,H,n", SE.CASES + SE.PRODUCT_SHAPES)
 def test_bound_is_tight_enough_to_mean_something(kind, sorb, no, H, n):
     se, *_ = _case(kind, sorb, no, H, n)
     _check_bound(se, f"{kind} {sorb}x{H} n {n}")
